@@ -21,12 +21,22 @@ measured train samples/s/client at the same k times N (408k / 398k 
 264k; the reference's time excludes its eval and FedAvg, ours includes them).  The
 early-stop rule (C:181-192, atol 1e-4 on the 4-metric vector) is evaluated on the device in
 every timed round, with a patience no timed round can exhaust, so every timed round is live.
-Companion key ``weak_8000_rows_per_client``: the same round with 8000 rows on every client
-(per-GPU work fixed).  After the timed region, rounds-to-target on the real income CSV
-(compat mode, this client count, the same shards) is measured and reported as
-``rounds_to_target``.
+
+A plain run sets up, warms up, times the ``--steps`` rounds, writes ``--dump-outputs`` if asked
+and prints the record.  Everything else is measured only with ``--full``, after the timed region
+and untimed for the headline: the companion key ``weak_8000_rows_per_client`` (the same round with
+8000 rows on every client, per-GPU work fixed), the per-kernel trace, the same-box eager torch
+anchor, the fp32 round, the N > 1 plane companions, and rounds-to-target on the real income CSV
+(compat mode, this client count, the same shards; ``rounds_to_target``).  Without ``--full`` those
+keys are ``null``.
+
+``--dump-outputs DIR`` writes what the timed path computed as ``DIR/<name>.npy`` (rank 0's view):
+the global and local weights after the last timed round and the metric / loss history rows of
+the timed rounds.  The inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 
     python bench.py --gpus 1 --steps 2000 --warmup 200
+    python bench.py --gpus 1 --steps 2000 --warmup 200 --full
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 ...
 """
 from __future__ import annotations
@@ -96,6 +106,29 @@ def rounds_to_target(comm, targets=(0.80, 0.83), max_rounds=300, dtype="fp32", l
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Write ``arrays`` as ``out_dir/<name>.npy`` (float64 stays, everything else becomes
+    float32).  An array over its share of ``limit`` is replaced by a fixed sample of its
+    elements (seeded, ascending flat indices), the same elements in every run.  Returns
+    ``{name: shape written}``."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    written = {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        arr = np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32)
+        keep = (share - 4096) // arr.itemsize   # (4096: room for the .npy header)
+        if arr.size > keep:
+            idx = np.sort(np.random.default_rng(seed).choice(arr.size, size=keep, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
 _T_START = time.perf_counter()
 
 
@@ -163,8 +196,17 @@ def main(argv=None):
                     help="rows on every client (0: the reference's chunking of --total-rows over the N clients, "
                          "C:57-60 -- 8000 // N each, the last rank takes the remainder)")
     ap.add_argument("--total-rows", type=int, default=REF_TRAIN_ROWS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what is not the headline (untimed for it): the "
+                         "weak-scaling companion, the per-kernel trace, the eager torch anchor, the fp32 round, "
+                         "rounds-to-target and, at N > 1 on the xGMI plane, the plane companions; each has its own "
+                         "--no-* switch.  Off: those keys of the record are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed (rank 0's weights after the "
+                         "last timed step, the timed steps' metric and loss rows) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all (a fixed seeded sample of a larger array)")
     ap.add_argument("--no-weak", action="store_true",
-                    help="skip the companion run with 8000 rows on every client (weak scaling)")
+                    help="--full: skip the companion run with 8000 rows on every client (weak scaling)")
     ap.add_argument("--no-early-stop", dest="early_stop", action="store_false",
                     help="do not evaluate the early-stop rule in the timed rounds")
     ap.add_argument("--patience", type=int, default=0,
@@ -186,19 +228,20 @@ def main(argv=None):
                     help="untimed replays of the timed region's graph after its capture (warm-up; 1 / 2 / 3 "
                          "measured the same at 20 steps, profiles/prime_replays_ab_r5.log)")
     ap.add_argument("--trace-rounds", type=int, default=8,
-                    help="after the timed region (untimed): this many rounds of the same round design issued "
+                    help="--full, after the timed region (untimed): this many rounds of the same round design issued "
                          "eagerly with a hipEvent per launch (HipRoundEngine.trace) -> per-kernel us per round in "
                          "the record's kernel_trace_us (0: off)")
     ap.add_argument("--no-plane-companions", action="store_true",
-                    help="N > 1 on the xGMI plane: skip the untimed-for-the-headline companions that time the same "
+                    help="--full, N > 1 on the xGMI plane: skip the untimed-for-the-headline companions that time the same "
                          "shard with the pull protocol (FEDMI_PEER_LL=0) and with classic rounds (lagged_eval off)")
     ap.add_argument("--companion-timeout", type=float, default=300.0,
-                    help="seconds the untimed extras (the weak-scaling companion, the eager anchor, the fp32 round, "
+                    help="--full: seconds the untimed extras (the weak-scaling companion, the eager anchor, the fp32 round, "
                          "rounds-to-target, the N > 1 plane companions) may take before a watchdog prints the "
                          "headline record and exits with status 3")
-    ap.add_argument("--no-convergence", action="store_true")
-    ap.add_argument("--no-anchor", action="store_true", help="skip the same-box eager torch anchor")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the untimed fp32-kernel round (one client)")
+    ap.add_argument("--no-convergence", action="store_true", help="--full: skip rounds-to-target on the real CSV")
+    ap.add_argument("--no-anchor", action="store_true", help="--full: skip the same-box eager torch anchor")
+    ap.add_argument("--no-fp32", action="store_true",
+                    help="--full: skip the untimed fp32-kernel round (one client)")
     ap.add_argument("--config", default="c", choices=["c", "wide", "sweep"],
                     help="c: the reference [C] workload (default, the headline metric) | wide: BASELINE config 3, "
                          "MLP 14-4096-4096-4096-2 on --wide-rows synthetic rows per client, bf16 NT GEMMs, "
@@ -267,10 +310,13 @@ def main(argv=None):
     # a GPU, the companion run's engine on a fresh stream ran 2.3x slower)
     stream = torch.cuda.Stream(device=dev)
 
-    def timed_rounds(rows_local: int, rows_total: int, dtype: str = a.dtype, trace: int = 0, lagged_eval: bool = True):
+    def timed_rounds(rows_local: int, rows_total: int, dtype: str = a.dtype, trace: int = 0, lagged_eval: bool = True,
+                     outputs: dict = None):
         """Build a client with `rows_local` rows (FedAvg weight rows_local / rows_total), warm up,
         time exactly a.steps rounds (max over ranks), then (untimed) trace `trace` rounds, close +
-        check; returns (dt, engine, primed, trace record or None)."""
+        check; returns (dt, engine, primed, trace record or None).  `outputs` (a dict) is filled
+        with what the timed rounds computed: this rank's global and local weights after the last
+        timed round, and the timed rounds' rows of the metric and loss history."""
         _progress(f"engine: {rows_local} rows, {dtype}, lagged_eval={lagged_eval}")
         X, y = synth_shard(rows_local, comm.rank, dev)
         cfg = EngineConfig(hidden=tuple(a.hidden), max_rounds=max_rounds, early_stop=a.early_stop,
@@ -298,6 +344,9 @@ def main(argv=None):
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if outputs is not None:  # before the trace and the closing round train on
+            outputs["global_weights"] = eng.global_flat()
+            outputs["local_weights"] = eng.local_flat()
         tr, traced = None, 0
         if trace > 0 and (eng._engine_reduces() or N == 1):
             # per-kernel breakdown of the same round design (eager, events per launch); the max
@@ -321,14 +370,21 @@ def main(argv=None):
         # every timed round was live and folded (a stop would leave rounds_run short)
         assert h["rounds_run"] == a.warmup + primed + a.steps + traced + 1 and h["stop_round"] < 0, \
             (h["rounds_run"], primed, h["stop_round"])
+        if outputs is not None:
+            lo = a.warmup + primed
+            outputs["metrics_global"] = h["global"][lo:lo + a.steps]      # [steps, 4] float64
+            outputs["metrics_per_rank"] = h["per_rank"][lo:lo + a.steps]  # [steps, N, 4] float64
+            outputs["loss"] = h["loss"][lo:lo + a.steps]                  # [steps] float32
         return dt, eng, primed, tr
 
     rows_local = a.rows_per_client or reference_rows(a.total_rows, N, comm.rank)
     rows_total = a.rows_per_client * N if a.rows_per_client else a.total_rows
     from fedmi.parallel.peer import PeerFailure
     plane_failure = None
+    trace_rounds = max(0, a.trace_rounds) if a.full else 0
+    outputs = {} if a.dump_outputs else None
     try:
-        dt, eng, primed, ktrace = timed_rounds(rows_local, rows_total, trace=max(0, a.trace_rounds))
+        dt, eng, primed, ktrace = timed_rounds(rows_local, rows_total, trace=trace_rounds, outputs=outputs)
     except PeerFailure as e:
         # The xGMI plane reported a failure (a wait timed out): every rank's failure word is set,
         # so every rank lands here together.  Re-run the timed rounds on the next data plane (RCCL,
@@ -340,7 +396,7 @@ def main(argv=None):
               file=sys.stderr, flush=True)
         comm.peer_allreduce = False
         gc.collect()
-        dt, eng, primed, ktrace = timed_rounds(rows_local, rows_total, trace=max(0, a.trace_rounds))
+        dt, eng, primed, ktrace = timed_rounds(rows_local, rows_total, trace=trace_rounds, outputs=outputs)
     h = eng.history()
     # every rank must hold the same global model and metric history (raises otherwise: no number
     # is reported for a run whose FedAvg was not FedAvg)
@@ -428,7 +484,15 @@ def main(argv=None):
             rec["warning"] = ("FedAvg went through the HOST plane (gloo all-gather, rank-order sums): the xGMI "
                               "peer set-up and the RCCL bootstrap were both unavailable; this is not the device "
                               "data plane's number")
-    # The untimed extras run under a watchdog once the headline record exists: rank 0 prints it
+    if outputs is not None and comm.rank == 0:
+        rec["outputs_dumped"] = dump_outputs(a.dump_outputs, outputs)
+    if not a.full:
+        # a plain run ends here: nothing but the headline was measured
+        if rec is not None:
+            print(json.dumps(rec), flush=True)
+        comm.close()
+        return 0
+    # --full: the untimed extras run under a watchdog once the headline record exists: rank 0 prints it
     # exactly once whatever happens to them (an extra that raises is recorded; one stuck in a
     # collective or a peer wait ends the process when the budget runs out) -- the weak-scaling
     # companion, the eager anchor and the fp32 round included, so no extra can cost the headline.
@@ -636,6 +700,12 @@ def main_wide(a) -> None:
     last_loss = c.loss()
     from fedmi.parallel.consistency import check_replicas
     replicas_ok = check_replicas(comm, [c.params])
+    if a.dump_outputs and comm.rank == 0:
+        m = c.metrics()
+        dump_outputs(a.dump_outputs, {
+            "weights": c.params.detach().float().cpu().numpy(),
+            "loss_last_round": np.array([last_loss], dtype=np.float64),
+            "local_metrics": np.array([m[k] for k in sorted(m)], dtype=np.float64)})
     if comm.rank == 0:
         print(json.dumps({
             "metric": "train samples/s, wide-MLP FedAvg (BASELINE config 3)", "value": value,
@@ -710,6 +780,11 @@ def main_sweep(a) -> int:
     from fedmi.parallel.consistency import check_replicas
     replicas_ok = check_replicas(comm, [e.global_flat() for e in grp.engines])
     best = grp.best()
+    if a.dump_outputs and comm.rank == 0:
+        # every trial's global model after the last timed round, and that round's metrics
+        arrays = {f"trial{i:02d}_global_weights": e.global_flat() for i, e in enumerate(grp.engines)}
+        arrays["final_metrics"] = np.array([[t.final[k] for k in sorted(t.final)] for t in trials], dtype=np.float64)
+        dump_outputs(a.dump_outputs, arrays)
     if comm.rank == 0:
         print(json.dumps({
             "metric": "trial-rounds/s, packed federated hyperparameter sweep (BASELINE config 5)", "value": value,

@@ -30,13 +30,11 @@ DEFAULT_LABEL = "income"
 
 
 def find_dataset(name: str = DEFAULT_DATASET) -> str:
-    """Locate the dataset: explicit path, CWD, the repo's ``data/`` dir, then the
-    read-only reference checkout."""
+    """Locate the dataset: explicit path, CWD, then the repo's ``data/`` dir."""
     candidates = [name, os.path.join(os.getcwd(), name)]
     here = os.path.dirname(os.path.abspath(__file__))
     repo = os.path.dirname(os.path.dirname(here))
     candidates.append(os.path.join(repo, "data", os.path.basename(name)))
-    candidates.append(os.path.join("/root/reference", os.path.basename(name)))
     for c in candidates:
         if os.path.isfile(c):
             return c

@@ -19,18 +19,18 @@ run_tests() {
     local rc=$?; tail -3 $out/pytest_gpu.log; return $rc
 }
 run_bench() {
-    cd $R && timeout -k 10 400 python -u bench.py $BENCH_ARGS > $out/bench.json 2> $out/bench.err
+    cd $R && timeout -k 10 400 python -u bench.py --full $BENCH_ARGS > $out/bench.json 2> $out/bench.err
     local rc=$?; cat $out/bench.json; return $rc
 }
 run_n8() {
     # a whole node's world (8 ranks) on the box's one GPU: peer self-test at world 8, classic rounds,
     # replica check (the driver's SCALE run uses 8 real GPUs)
-    cd $R && timeout -k 10 500 python -u bench.py --gpus 8 --share-gpu --steps 400 --warmup 50 --no-anchor \
+    cd $R && timeout -k 10 500 python -u bench.py --gpus 8 --share-gpu --steps 400 --warmup 50 --full --no-anchor \
         --no-convergence > $out/bench_n8_share.json 2> $out/bench_n8_share.err
     local rc=$?; cat $out/bench_n8_share.json; return $rc
 }
 run_fp32() {
-    cd $R && timeout -k 10 400 python -u bench.py --dtype fp32 --steps 2000 --warmup 200 --no-anchor \
+    cd $R && timeout -k 10 400 python -u bench.py --dtype fp32 --steps 2000 --warmup 200 --full --no-anchor \
         > $out/bench_fp32.json 2> $out/bench_fp32.err
     local rc=$?; cat $out/bench_fp32.json; return $rc
 }

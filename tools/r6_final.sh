@@ -21,9 +21,9 @@ run_tests() {      # the whole GPU suite
 }
 run_bench() {      # the driver's shape x 3, the steady state x 1
     for i in 1 2 3; do
-        timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $out/bench_driver_shape_$i.json 2> $out/bench_driver_shape_$i.err || return 1
+        timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --full > $out/bench_driver_shape_$i.json 2> $out/bench_driver_shape_$i.err || return 1
     done
-    timeout -k 10 400 python -u bench.py --steps 2000 --warmup 200 --no-convergence > $out/bench_steady_2000.json 2> $out/bench_steady_2000.err
+    timeout -k 10 400 python -u bench.py --steps 2000 --warmup 200 --full --no-convergence > $out/bench_steady_2000.json 2> $out/bench_steady_2000.err
 }
 run_prof() {       # kernel summary of the bench
     cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv \
@@ -32,10 +32,10 @@ run_prof() {       # kernel summary of the bench
 }
 run_share() {      # N = 2 / 4 / 8 ranks sharing the GPU: the N > 1 round designs incl. the plane companions
     for n in 2 4; do
-        timeout -k 10 600 python -u bench.py --gpus $n --share-gpu --steps 400 --warmup 50 --no-anchor --no-convergence \
+        timeout -k 10 600 python -u bench.py --gpus $n --share-gpu --steps 400 --warmup 50 --full --no-anchor --no-convergence \
             > $out/bench_n${n}_share.json 2> $out/bench_n${n}_share.err || return 1
     done
-    timeout -k 10 700 python -u bench.py --gpus 8 --share-gpu --steps 400 --warmup 50 --no-anchor --no-convergence \
+    timeout -k 10 700 python -u bench.py --gpus 8 --share-gpu --steps 400 --warmup 50 --full --no-anchor --no-convergence \
         --companion-timeout 400 > $out/bench_n8_share.json 2> $out/bench_n8_share.err
 }
 run_sk() {         # [S] 5 rounds and [H] 90 trials, k = 1, whole script; [H] k = 8 sharing the GPU
