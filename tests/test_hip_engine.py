@@ -9,6 +9,8 @@ from fedmi.fl.engine import EngineConfig, HipRoundEngine, TorchRoundEngine
 from fedmi.models.mlp import init_flat
 from fedmi.ops import native
 
+from .reference_oracle import _bf, _split_bf16_reference_grad  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 DIMS = [14, 50, 200, 2]
@@ -697,46 +699,6 @@ def test_bf16_engine_layout_fits_one_cu():
     lay = e.engine.layout()
     assert lay["dtype"] == 1 and lay["lds_bytes"] <= 158 * 1024, lay["lds_bytes"]
     assert lay["eval_lds_bytes"] <= lay["lds_bytes"]
-
-
-def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float64)
-
-
-def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False):
-    """Host model of the bf16 train kernel's arithmetic (fl_kernels_bf16.hip), in float64:
-    split-bf16 forward (hi.hi + lo.hi + hi.lo, hidden outputs split into hi/lo after ReLU),
-    softmax-CE deltas rounded to bf16, backward on the hi parts with bf16 deltas."""
-    from fedmi.models.mlp import flat_to_dict
-    d = flat_to_dict(flat, dims)
-    L = len(dims) - 1
-    Ws = [torch.as_tensor(d[f"model.{2 * l}.weight"], dtype=torch.float64) for l in range(L)]
-    bs = [torch.as_tensor(d[f"model.{2 * l}.bias"], dtype=torch.float64) for l in range(L)]
-    a = torch.as_tensor(X, dtype=torch.float32).to(torch.float64)
-    yt = torch.as_tensor(y, dtype=torch.long)
-    his, pre = [], []
-    for l in range(L):
-        ah, wh = _bf(a), _bf(Ws[l])
-        al, wl = _bf(a - ah), _bf(Ws[l] - wh)
-        z = ah @ wh.T + (al @ wh.T + ah @ wl.T) + bs[l]
-        his.append(ah)
-        pre.append(z)
-        a = torch.relu(z).to(torch.float32).to(torch.float64)
-    n = len(y)
-    p = torch.softmax(z, 1)
-    dz = p.clone()
-    dz[torch.arange(n), yt] -= 1.0
-    # fp16 slab: the kernels back-propagate the unscaled delta (Adam applies the 1/n); fp32
-    # slab: the delta of the mean loss
-    sc = 1.0 if scaled_delta else float(n)
-    dz = _bf(dz / n) if scaled_delta else _bf(dz)
-    gW, gb = [None] * L, [None] * L
-    for l in range(L - 1, -1, -1):
-        gW[l] = dz.T @ his[l] / sc
-        gb[l] = dz.sum(0) / sc
-        if l:
-            dz = _bf((dz @ _bf(Ws[l])) * (his[l] > 0))
-    return torch.cat([torch.cat([gW[l].reshape(-1), gb[l]]) for l in range(L)]).numpy()
 
 
 @pytest.mark.parametrize("R,slab", [(16, "fp16"), (32, "fp16"), (32, "fp32")])
