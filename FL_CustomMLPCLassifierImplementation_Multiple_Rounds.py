@@ -55,6 +55,13 @@ def parse_args(argv=None):
     ap.add_argument("--fedprox-mu", type=float, default=0.0)
     ap.add_argument("--participation", type=float, default=1.0,
                     help="fraction of clients sampled per round (both engines; 1.0 = all, the reference)")
+    ap.add_argument("--dp-clip", type=float, default=0.0,
+                    help="differential privacy: L2 bound S of every client's round update (0 = off)")
+    ap.add_argument("--dp-noise", type=float, default=0.0,
+                    help="differential privacy: noise multiplier z (needs --dp-clip; 0 = clipping only)")
+    ap.add_argument("--dp-delta", type=float, default=1e-5, help="delta of the reported (epsilon, delta)")
+    ap.add_argument("--dp-seed", type=int, default=None,
+                    help="noise seed for reproducible experiments (default: a private seed per client)")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -144,6 +151,17 @@ def _dataset(a, comm):
     return SimpleNamespace(X_train=X, y_train=y, X_test=Xt, y_test=yt)
 
 
+def _dp_fields(a) -> dict:
+    return dict(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_seed=a.dp_seed)
+
+
+def _print_privacy(a, rounds: int) -> None:
+    """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
+    if a.dp_clip > 0.0:
+        from fedmi.privacy.accountant import privacy_statement
+        print(privacy_statement(a.dp_noise, rounds, a.dp_delta), flush=True)
+
+
 def main_clients(a, comm):
     """--clients K: K clients of one federation in this process (reference semantics client for
     client: own shard, local step, local evaluation, sample-weighted FedAvg, early stop on the
@@ -157,7 +175,8 @@ def main_clients(a, comm):
     ds = load_tabular(a.data, label=a.label, with_mean=True)
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
-                       patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype)
+                       patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
+                       **_dp_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -169,6 +188,7 @@ def main_clients(a, comm):
     if not a.quiet:
         print_history(h, a.patience)
     print(f"{a.clients} simulated clients ({backend}): {h['rounds_run']} rounds in {wall:.2f} s", flush=True)
+    _print_privacy(a, int(h["rounds_run"]))
     if a.jsonl:
         w = JsonlWriter(a.jsonl)
         w.history(h, clients=a.clients, script="C-clients", aggregation="in-process", wall_s=wall)
@@ -184,6 +204,10 @@ def main(argv=None):
         os.environ["FEDMI_PEER_TIMEOUT_S"] = str(a.peer_timeout_s)   # read by fedmi.parallel.peer
     if not 0.0 < a.participation <= 1.0:
         raise SystemExit("--participation must be in (0, 1]")
+    if a.dp_noise > 0.0 and not a.dp_clip > 0.0:
+        raise SystemExit("--dp-noise needs --dp-clip > 0")
+    if a.wide and a.dp_clip > 0.0:
+        raise SystemExit("--dp-clip is not supported with --wide")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -203,7 +227,7 @@ def main(argv=None):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, participation=a.participation, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
-                       debug=a.debug, dtype=a.dtype)
+                       debug=a.debug, dtype=a.dtype, **_dp_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,
@@ -244,6 +268,8 @@ def main(argv=None):
                   allreduce_bytes_per_round=4 * comm_floats if size > 1 else 0,
                   wall_s=t_train, samples_per_s_per_client=len(trainer.X_local) * rounds_run / max(t_train, 1e-9))
         w.close()
+    if rank == 0:
+        _print_privacy(a, int(trainer.history()["rounds_run"]))   # resumed rounds count too
     if a.save:
         save_checkpoint(a.save, trainer)   # collective: every client writes its optimizer state
     if a.timing and rank == 0:

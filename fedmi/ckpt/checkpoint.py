@@ -128,11 +128,16 @@ def save_checkpoint(path: str, trainer) -> None:
     os.makedirs(path, exist_ok=True)
     save_file, _ = _st()
     cname = f"client{eng.rank}.safetensors"
+    # differential privacy: the client's noise seed (two 32-bit words; private unless the config
+    # names one) and its own update norms stay in the client's file
+    dp = {} if "dp_seed" not in st else {
+        "dp_seed": np.asarray([int(st["dp_seed"]) & 0xFFFFFFFF, int(st["dp_seed"]) >> 32], np.int64),
+        "update_norm": np.asarray(st["history"]["update_norm"], np.float32)}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
         {"local": np.asarray(st["local"], np.float32), "exp_avg": np.asarray(st["exp_avg"], np.float32),
          "exp_avg_sq": np.asarray(st["exp_avg_sq"], np.float32),
          # this client's own Adam step count (differs from rounds x local_steps when clients are sampled)
-         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64)}, tmp, metadata={"round": str(R)}))
+         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp}, tmp, metadata={"round": str(R)}))
     gflat = flat_to_dict(st["global"], eng.dims)
     if eng.rank == 0:
         _atomic(os.path.join(path, tagged("weights.safetensors", R)), lambda tmp: save_weights(tmp, gflat, R))
@@ -196,6 +201,10 @@ def resume(path: str, trainer) -> int:
                       "per_rank": np.asarray(h["per_rank"]), "loss": np.asarray(h["loss"])}}
     if "opt_steps" in c:
         st["opt_steps"] = int(np.asarray(c["opt_steps"]).reshape(-1)[0])
+    if "dp_seed" in c:
+        lo, hi = (int(x) for x in np.asarray(c["dp_seed"]).reshape(-1)[:2])
+        st["dp_seed"] = lo | (hi << 32)
+        st["history"]["update_norm"] = np.asarray(c["update_norm"], np.float32)
     eng.load_portable_state(st)
     return st["rounds"]
 

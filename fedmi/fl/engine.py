@@ -21,6 +21,7 @@ weights averaged with weights n_i / N (C:110-116), early stop with patience/atol
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field, asdict
 from typing import Dict, List, Optional, Sequence
 
@@ -98,6 +99,19 @@ class EngineConfig:
     # valid (never for one fused client, whose evaluation IS the training forward).  The engine's
     # layout()["plain_fwd"] reports what runs; bench records and checkpoints carry it.
     plain_fwd: Optional[bool] = None
+    # Client-level differential privacy (DP-FedAvg with distributed noise; fedmi/privacy): every
+    # sampled client clips its round update D = local - (the image the round trained from) to
+    # ||D||_2 <= dp_clip and adds N(0, sigma_r^2 I), sigma_r = dp_noise * dp_clip * max_j w_j(r) /
+    # sqrt(K_r), to its FedAvg contribution w_i (x + c D) BEFORE the exchange, so the all-reduced sum
+    # carries noise of dp_noise times its sensitivity to one client and no rank sees an un-noised
+    # peer update.  dp_clip = 0: off (nothing of a round changes).  dp_noise needs dp_clip > 0;
+    # dp_noise = 0 is clipping only.  dp_seed: None = a private 64-bit seed per rank from
+    # os.urandom (kept in the portable state, so a resume continues the stream), an int =
+    # reproducible runs.  The local model, Adam moments, local metrics are untouched; rounds are
+    # classic (no fused / lagged evaluation); history()["update_norm"] holds the pre-clip norms.
+    dp_clip: float = 0.0
+    dp_noise: float = 0.0
+    dp_seed: Optional[int] = None
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -122,8 +136,24 @@ def _dtype_id(dtype: str) -> int:
     return 0 if dtype == "fp32" else 1
 
 
+def dp_enabled(cfg: EngineConfig) -> bool:
+    """Validate the DP fields; True when differential privacy is on (``dp_clip > 0``)."""
+    S, z = float(cfg.dp_clip), float(cfg.dp_noise)
+    if not (math.isfinite(S) and S >= 0.0):
+        raise ValueError(f"dp_clip must be a finite number >= 0, got {cfg.dp_clip!r}")
+    if not (math.isfinite(z) and z >= 0.0):
+        raise ValueError(f"dp_noise must be a finite number >= 0, got {cfg.dp_noise!r}")
+    if z > 0.0 and S == 0.0:
+        raise ValueError("dp_noise > 0 needs dp_clip > 0 (the noise is scaled by the clipping bound)")
+    if cfg.dp_seed is not None and not (0 <= int(cfg.dp_seed) < 2 ** 64):
+        raise ValueError(f"dp_seed must be None or an integer in [0, 2**64), got {cfg.dp_seed!r}")
+    return S > 0.0
+
+
 class _History:
-    def __init__(self, max_rounds: int, world: int):
+    def __init__(self, max_rounds: int, world: int, dp: bool = False):
+        # DP engines: this client's pre-clip update norm per round (0: not sampled)
+        self.norm = np.zeros(max_rounds, dtype=np.float32) if dp else None
         self.glob = np.zeros((max_rounds, 4))
         self.rank = np.zeros((max_rounds, world, 4))
         self.loss = np.zeros(max_rounds, dtype=np.float32)
@@ -133,7 +163,7 @@ class _History:
 
     def as_dict(self) -> dict:
         n = self.rounds_run
-        return {
+        out = {
             "rounds_run": n,
             "stop_round": self.stop_round,
             "stop_trigger": self.stop_trigger,
@@ -141,6 +171,9 @@ class _History:
             "per_rank": self.rank[:n].copy(),
             "loss": self.loss[:n].copy(),
         }
+        if self.norm is not None:
+            out["update_norm"] = self.norm[:n].copy()
+        return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
         """Same structure as the reference's returned ``global_metrics`` (C:124)."""
@@ -150,8 +183,9 @@ class _History:
 
 class RoundEngineBase:
     def __init__(self, X: np.ndarray, y: np.ndarray, n_classes: int, cfg: EngineConfig, comm,
-                 init_flat: np.ndarray, n_total: Optional[int] = None):
+                 init_flat: np.ndarray, n_total: Optional[int] = None, client_sizes=None):
         self.cfg = cfg
+        self.dp = dp_enabled(cfg)
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
@@ -166,8 +200,36 @@ class RoundEngineBase:
         self.n_total = int(n_total)
         self.agg_scale = float(self.n_local) / float(self.n_total)
         self.tail_stride = self.n_classes * self.n_classes + 1
-        self.hist = _History(cfg.max_rounds, self.world)
+        self.hist = _History(cfg.max_rounds, self.world, dp=self.dp)
         assert init_flat.shape == (self.P,)
+        if self.dp:
+            if self.world > 1 and client_sizes is None:
+                if not hasattr(comm, "allgather"):
+                    raise ValueError("differential privacy needs client_sizes (the noise scale follows max_j n_j / N)")
+                client_sizes = comm.allgather(self.n_local)
+            self._client_sizes = None if client_sizes is None else [int(n) for n in client_sizes]
+            self.dp_seed = (int.from_bytes(os.urandom(8), "little") if cfg.dp_seed is None
+                            else int(cfg.dp_seed))
+            self.dp_sigma = self._dp_sigma_table(client_sizes)
+
+    def _dp_sigma_table(self, client_sizes) -> np.ndarray:
+        """Per-round noise std of ONE client's share, sigma_r = z * S * max_{j in P_r} w_j(r) / sqrt(K_r),
+        with the round's FedAvg weights as ``_round_tables`` builds them; computed in double, rounded
+        to fp32 once (both engines use these fp32 values)."""
+        cfg = self.cfg
+        mr = max(1, int(cfg.max_rounds))
+        z, S = float(cfg.dp_noise), float(cfg.dp_clip)
+        sigma = np.zeros(mr, np.float32)
+        for r in range(mr):
+            part = self.participants(r)
+            if self.world == 1:
+                wmax = float(self.n_local) / float(self.n_total)
+            else:
+                denom = float(self.n_total) if len(part) == self.world else \
+                    float(sum(int(client_sizes[k]) for k in part))
+                wmax = max(int(client_sizes[k]) for k in part) / denom
+            sigma[r] = z * S * wmax / math.sqrt(len(part))
+        return sigma
 
     def participants(self, r: int) -> np.ndarray:
         """Ranks that train and are averaged in round r (all of them unless sampling): the same
@@ -239,6 +301,17 @@ class RoundEngineBase:
             self.hist.loss[:n] = np.asarray(h["loss"], dtype=np.float32).reshape(n)
         self.hist.stop_round = int(h.get("stop_round", -1))
         self.hist.stop_trigger = int(h.get("stop_trigger", -1))
+        if self.hist.norm is not None and n and "update_norm" in h:
+            self.hist.norm[:n] = np.asarray(h["update_norm"], dtype=np.float32).reshape(n)
+
+    def _load_dp_seed(self, st: dict) -> None:
+        """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
+        construction is replaced by the saved one)."""
+        if self.dp and st.get("dp_seed") is not None:
+            self._set_dp_seed(int(st["dp_seed"]))
+
+    def _set_dp_seed(self, seed: int) -> None:
+        self.dp_seed = int(seed)
 
 
 # ---------------------------------------------------------------------------------------
@@ -246,8 +319,8 @@ class RoundEngineBase:
 # ---------------------------------------------------------------------------------------
 class TorchRoundEngine(RoundEngineBase):
     def __init__(self, X, y, n_classes, cfg: EngineConfig, comm, init_flat, n_total=None,
-                 device="cpu", X_dtype=torch.float32):
-        super().__init__(X, y, n_classes, cfg, comm, init_flat, n_total)
+                 device="cpu", X_dtype=torch.float32, client_sizes=None):
+        super().__init__(X, y, n_classes, cfg, comm, init_flat, n_total, client_sizes)
         self.device = torch.device(device)
         self.X = torch.as_tensor(np.asarray(X), dtype=X_dtype, device=self.device)
         self.y = torch.as_tensor(np.asarray(y), dtype=torch.long, device=self.device)
@@ -312,6 +385,8 @@ class TorchRoundEngine(RoundEngineBase):
     def step_train(self) -> None:
         r = self.rounds_issued
         self._active = self.rank in self.participants(r)
+        if self.dp:
+            self._dp_input = self.model.flat.detach().cpu().clone()   # the image the round trains from
         if self._active:
             self._loss = self.train_one_epoch()
         else:
@@ -327,16 +402,46 @@ class TorchRoundEngine(RoundEngineBase):
         [w * n_i/N | per-rank (confusion, loss) tails] (+ n_i when sampling clients)."""
         sampling = float(self.cfg.participation) < 1.0 and self.world > 1
         buf = torch.zeros(self.P + self.world * self.tail_stride + int(sampling), dtype=torch.float32)
+        active = getattr(self, "_active", True)
+        model = self.model.flat.detach().cpu()
+        noise = None
+        if self.dp:
+            # DP-FedAvg: the clipped model x + c (local - x) takes the local model's place, and the
+            # client's share of the round's Gaussian noise (the device's Philox stream) is added
+            r = self.rounds_issued
+            self.hist.norm[r] = 0.0
+            if active:
+                model, noise = self._dp_clip_and_noise(r, model)
         if not sampling:
-            buf[:self.P] = self.model.flat.detach().cpu() * self.agg_scale
-        elif getattr(self, "_active", True):
+            buf[:self.P] = model * self.agg_scale
+            if noise is not None:
+                buf[:self.P] += noise
+        elif active:
             # weights n_i * w_i and, in the last slot, n_i: divided by the sampled total after the sum
-            buf[:self.P] = self.model.flat.detach().cpu() * float(self.n_local)
+            buf[:self.P] = model * float(self.n_local)
+            if noise is not None:
+                buf[:self.P] += noise * float(sum(self._client_sizes[k] for k in self.participants(r)))
             buf[-1] = float(self.n_local)
         t0 = self.P + self.rank * self.tail_stride
         buf[t0:t0 + self.n_classes ** 2] = torch.as_tensor(self._cm.reshape(-1), dtype=torch.float32)
         buf[t0 + self.n_classes ** 2] = self._loss
         return buf
+
+    def _dp_clip_and_noise(self, r: int, local: torch.Tensor):
+        """(x + c (local - x), this client's noise vector or None) of round r; records the pre-clip
+        norm.  An unclipped round keeps the local model as it is (c = 1)."""
+        from ..privacy.philox import dp_normals
+        x = self._dp_input.to(local.dtype)
+        delta = local - x
+        norm = float(torch.linalg.vector_norm(delta.double()))
+        self.hist.norm[r] = norm
+        S = float(self.cfg.dp_clip)
+        if norm > S:
+            local = x + delta * (S / norm)
+        if float(self.cfg.dp_noise) == 0.0:
+            return local, None
+        xi = float(self.dp_sigma[r]) * dp_normals(self.P, r, self.rank, self.dp_seed)
+        return local, torch.as_tensor(xi).to(local.dtype)
 
     def step_aggregate(self) -> None:
         # one SUM all-reduce of [w * n_i/N | per-rank (confusion, loss) tails]
@@ -443,6 +548,7 @@ class TorchRoundEngine(RoundEngineBase):
                    "prev": [0.0] * 4 if sp.prev is None else [float(x) for x in sp.prev],
                    "stopped": bool(sp.stopped), "stop_round": int(self.hist.stop_round)},
             "history": self.hist.as_dict(),
+            **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
@@ -474,6 +580,7 @@ class TorchRoundEngine(RoundEngineBase):
         self.stopper.stopped = bool(es["stopped"])
         self.rounds_issued = r
         self._load_history(st["history"])
+        self._load_dp_seed(st)
 
 
 # ---------------------------------------------------------------------------------------
@@ -509,7 +616,9 @@ class HipRoundEngine(RoundEngineBase):
             Xshape1 = X.shape[1]
         else:
             Xn_len, Xshape1 = X.shape
-        super().__init__(_ShapeOnly(Xn_len, Xshape1), y, n_classes, cfg, comm, init_flat, n_total)
+        super().__init__(_ShapeOnly(Xn_len, Xshape1), y, n_classes, cfg, comm, init_flat, n_total, client_sizes)
+        if self.dp and client_sizes is None:
+            client_sizes = self._client_sizes
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         self.X = (X if isinstance(X, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(X, np.float32))).to(**f32).contiguous()
@@ -531,8 +640,9 @@ class HipRoundEngine(RoundEngineBase):
         # (with early stopping the native engine runs lagged rounds with the Adam-fused exchange,
         # which folds each round's metrics in time, or over RCCL, folded one round late with the
         # round run past a stop discarded bit-exactly: FLEngine.late_fold)
+        # (differential privacy: classic rounds, see fl_engine.cpp)
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
-                     and comm_buffers is None and bool(cfg.lagged_eval))
+                     and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp)
         comm_len = self.Pimg + self.world * self.tail_stride * (2 if self._lag else 1)
         if comm_buffers is None:
             self.params = [torch.zeros(comm_len, **f32), torch.zeros(comm_len, **f32)]
@@ -592,6 +702,13 @@ class HipRoundEngine(RoundEngineBase):
             "params1": self.params[1].data_ptr(), "state0": self.state[0].data_ptr(),
             "state1": self.state[1].data_ptr(),
         }
+        if self.dp:
+            # per-round noise std (host table like `sched`) and this client's pre-clip update norms
+            self.dp_sigma_dev = torch.as_tensor(self.dp_sigma, device=dev)
+            self.dp_norm = torch.zeros(mr, dtype=torch.float32, device=dev)
+            ecfg.update({"dp_clip": float(cfg.dp_clip), "dp_noise": float(cfg.dp_noise) > 0.0,
+                         "dp_seed": int(self.dp_seed)})
+            bufs.update({"dp_sigma": self.dp_sigma_dev.data_ptr(), "dp_norm": self.dp_norm.data_ptr()})
         for i, R in enumerate(R_try):
             self.slab = torch.zeros(((self.n_local + R - 1) // R) * slab_stride, **f32)
             ecfg["R"] = R
@@ -974,6 +1091,8 @@ class HipRoundEngine(RoundEngineBase):
                     m["glob"].copy_(self.h_global, non_blocking=True)
                     m["rank"].copy_(self.h_rank, non_blocking=True)
                     m["loss"].copy_(self.h_loss, non_blocking=True)
+                    if self.dp:
+                        m["norm"].copy_(self.dp_norm, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -1007,7 +1126,8 @@ class HipRoundEngine(RoundEngineBase):
             pin = torch.cuda.is_available()
             mk = lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
             self._mirror = [{"state": mk(self.state[0]), "glob": mk(self.h_global), "rank": mk(self.h_rank),
-                             "loss": mk(self.h_loss)} for _ in range(2)]
+                             "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {})}
+                            for _ in range(2)]
         return self._mirror
 
     def _fold_mirror(self, m) -> None:
@@ -1018,6 +1138,8 @@ class HipRoundEngine(RoundEngineBase):
             self.hist.glob[:n] = m["glob"][:n * 4].numpy().reshape(n, 4)
             self.hist.rank[:n] = m["rank"][:n * self.world * 4].numpy().reshape(n, self.world, 4)
             self.hist.loss[:n] = m["loss"][:n].numpy()
+            if self.dp:
+                self.hist.norm[:n] = m["norm"][:n].numpy()
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1044,6 +1166,8 @@ class HipRoundEngine(RoundEngineBase):
             self.hist.glob[:n] = self.h_global[:n * 4].cpu().numpy().reshape(n, 4)
             self.hist.rank[:n] = self.h_rank[:n * self.world * 4].cpu().numpy().reshape(n, self.world, 4)
             self.hist.loss[:n] = self.h_loss[:n].cpu().numpy()
+            if self.dp:
+                self.hist.norm[:n] = self.dp_norm[:n].cpu().numpy()
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1100,6 +1224,7 @@ class HipRoundEngine(RoundEngineBase):
                    "prev": [float(x) for x in st["prev"]], "stopped": bool(st["stopped"]),
                    "stop_round": int(st["stop_round"])},
             "history": self.hist.as_dict(),
+            **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
@@ -1133,11 +1258,19 @@ class HipRoundEngine(RoundEngineBase):
                 self.h_global[:n * 4].copy_(torch.as_tensor(self.hist.glob[:n].reshape(-1), device=dev))
                 self.h_rank[:n * self.world * 4].copy_(torch.as_tensor(self.hist.rank[:n].reshape(-1), device=dev))
                 self.h_loss[:n].copy_(torch.as_tensor(self.hist.loss[:n], device=dev))
+                if self.dp:
+                    self.dp_norm[:n].copy_(torch.as_tensor(self.hist.norm[:n], device=dev))
         self.stream.synchronize()
+        self._load_dp_seed(st)
         self.engine.invalidate()
         self.engine.reset_pending()
         self.rounds_issued = r
         self._stopped_seen = bool(st["es"]["stopped"])
+
+    def _set_dp_seed(self, seed: int) -> None:
+        self.dp_seed = int(seed)
+        self.engine.set_dp_seed(int(seed))   # a kernel argument: the native engine drops its graphs
+        self._graph_ready = False
 
     def state_dict(self) -> dict:
         self.stream.synchronize()

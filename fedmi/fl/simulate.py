@@ -75,7 +75,8 @@ class ClientGroup:
                 e = HipRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total,
                                    device=self.device, client_sizes=[len(i) for i in idx])
             elif backend == "torch":
-                e = TorchRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total)
+                e = TorchRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total,
+                                     client_sizes=[len(i) for i in idx])
             else:
                 raise ValueError(f"unknown backend {backend!r}")
             self.clients.append(e)

@@ -81,6 +81,10 @@ class FedTrialGroup:
                  n_total: Optional[int] = None, backend: str = "auto", seed: int = 0, group_graph_rounds: int = 16,
                  batched: bool = True):
         self.trials = list(trials)
+        if float(base.dp_clip) > 0.0 or float(base.dp_noise) > 0.0:
+            # the trials of a group share launches and one collective; a private sweep would also
+            # have to account for every trial's rounds (fedmi/privacy/accountant.py)
+            raise ValueError("fed_sweep does not run differentially private trials (dp_clip / dp_noise)")
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         rank = comm.rank if comm is not None else 0

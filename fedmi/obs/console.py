@@ -61,8 +61,10 @@ class JsonlWriter:
 
     def history(self, hist: dict, **extra) -> None:
         for r in range(hist["rounds_run"]):
+            # (DP engines: this client's pre-clip update norm of the round, 0 when not sampled)
+            norm = {"update_norm": float(hist["update_norm"][r])} if "update_norm" in hist else {}
             self.write(round=r + 1, **{k: float(hist["global"][r][i]) for i, k in enumerate(METRIC_NAMES)},
-                       per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **extra)
+                       per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **norm, **extra)
 
     def close(self) -> None:
         if self.f is not None:

@@ -301,6 +301,18 @@ __host__ __device__ inline char* fl_sel(const FLTrialDesc& t, FLSel s) {
     return s.base < 0 ? nullptr : t.base[s.base] + s.off;
 }
 
+// Differential privacy (fl_dp.hip): parameters of the per-round clip + noise kernel, passed to
+// that kernel alone (FLConfig / FLBuffers are by-value arguments of every round kernel).
+struct FLDp {
+    float clip;          // L2 bound S of a client's round update (> 0)
+    int noise;           // 1: Gaussian noise of std sigma[round] on every real parameter
+    int rank;            // third word of the noise counter
+    int max_rounds;      // entries of sigma / norm_hist
+    uint32_t key0, key1; // Philox key: the engine's 64-bit seed, low and high word
+    const float* sigma;  // [max_rounds] z * S * max_j w_j(r) / sqrt(K_r), host-built
+    float* norm_hist;    // [max_rounds] pre-clip ||local - input||_2 of this client (0: not sampled)
+};
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -331,6 +343,10 @@ hipError_t fl_launch_adam_ll(const MLPDesc& d, const FLConfig& c, const FLBuffer
                              int xchg, int afold, hipStream_t s);
 hipError_t fl_launch_eval(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,
                           const float* params, float* comm, const FLState* st, hipStream_t s);
+// (fl_dp.hip) clip + noise of the round whose last Adam kernel wrote state `st`: rewrites the
+// first Pimg floats of `comm` from `local` and the round's input image `pg`
+hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, const float* pg, float* comm,
+                        const FLState* st, const float* rtab, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

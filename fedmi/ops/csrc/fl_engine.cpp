@@ -266,11 +266,30 @@ class FLEngine {
         // post-step local model: one client (FedAvg of one is the identity, agg_scale 1).
         fused_ = cfg.contains("fused_eval") && cfg["fused_eval"].cast<bool>() && c_.world == 1 &&
                  c_.agg_scale == 1.0f;
+        // Differential privacy (fl_dp.hip): the round's output is the clipped, noised contribution,
+        // not the local model a fused / lagged round's next train kernel would score and stage, and
+        // a discarded late-fold round would have spent noise: classic rounds only.
+        std::memset(&dp_, 0, sizeof(dp_));
+        dp_.clip = cfg.contains("dp_clip") ? cfg["dp_clip"].cast<float>() : 0.f;
+        dp_on_ = dp_.clip > 0.f;
+        if (dp_on_) {
+            const unsigned long long seed = cfg["dp_seed"].cast<unsigned long long>();
+            dp_.noise = cfg["dp_noise"].cast<bool>() ? 1 : 0;
+            dp_.rank = c_.rank;
+            dp_.max_rounds = c_.max_rounds;
+            dp_.key0 = (uint32_t)seed;
+            dp_.key1 = (uint32_t)(seed >> 32);
+            dp_.sigma = as_ptr<const float>(bufs["dp_sigma"].cast<uintptr_t>());
+            dp_.norm_hist = as_ptr<float>(bufs["dp_norm"].cast<uintptr_t>());
+            if (dp_.sigma == nullptr || dp_.norm_hist == nullptr)
+                throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
+            fused_ = false;
+        }
         eval_fedavg_ = !cfg.contains("eval_fedavg") || cfg["eval_fedavg"].cast<bool>();
         // Lagged evaluation (fl_common.h FL_EVAL_LAGGED): several clients, early stopping off,
         // bf16 kernels, and room in LDS for the second parameter image.  The comm buffer then
         // carries the lag region A after the tails (the caller sized it: comm_len).
-        const bool lag_req = cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
+        const bool lag_req = !dp_on_ && cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
         if (lag_req) c_.lag_off = d_.Pimg + c_.tail_len;
         comm_len_ = d_.Pimg + c_.tail_len * (lag_req ? 2 : 1);
         const bool emulate = cfg.contains("emulate_clients") && cfg["emulate_clients"].cast<bool>();
@@ -541,6 +560,15 @@ class FLEngine {
         drop_graph();
     }
 
+    // Noise key of a DP engine (resume: the checkpoint's stream continues); a kernel argument, so
+    // captured graphs are dropped.
+    void set_dp_seed(unsigned long long seed) {
+        if (!dp_on_) throw std::runtime_error("set_dp_seed: differential privacy is off");
+        dp_.key0 = (uint32_t)seed;
+        dp_.key1 = (uint32_t)(seed >> 32);
+        drop_graph();
+    }
+
     // The host wrote the global weights (set_weights / resume): the next round repacks them.
     void invalidate() { need_pack_ = true; }
 
@@ -602,6 +630,7 @@ class FLEngine {
 
     // Launch one kernel of round r on its live state (0 = train, 1 = adam, 2 = eval).
     void launch_one(int r, int which, uintptr_t stream) {
+        no_relaunch_with_dp("launch_one");
         hipStream_t s = as_stream(stream);
         float* pg = pbuf_[r & 1];
         float* cb = comm_buf(r);
@@ -616,6 +645,7 @@ class FLEngine {
     // re-running the kernels of the last issued round `r` on its (live) state.  Training
     // launches use local_step=1 semantics so the round state is not advanced.
     py::dict time_kernels(int r, int iters, uintptr_t stream) {
+        no_relaunch_with_dp("time_kernels");
         hipStream_t s = as_stream(stream);
         float* pg = pbuf_[r & 1];
         float* cb = comm_buf(r);
@@ -671,7 +701,7 @@ class FLEngine {
         }
         tev_ = nullptr;
         HIP_CHECK(hipStreamSynchronize(s));
-        static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg"};
+        static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -736,11 +766,16 @@ class FLEngine {
         o["tail_len"] = c_.tail_len;
         o["comm_len"] = comm_len_;
         o["lagged_eval"] = lagged();
+        o["dp"] = dp_on_;                                // clipped (+ noised) contributions, classic rounds
         o["state_bytes"] = (int)sizeof(FLState);
         return o;
     }
 
   private:
+    // Re-running a round's Adam kernel alone republishes the un-noised w * local into the comm buffer.
+    void no_relaunch_with_dp(const char* what) const {
+        if (dp_on_) throw std::runtime_error(std::string(what) + ": not on a DP engine (use trace)");
+    }
     void launch_train(const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
                       int mode = FL_EVAL_CLASSIC, float* cm_out = nullptr, int fold_mask = FL_FOLD_B) {
         if (dtype_ == 0) {
@@ -758,7 +793,8 @@ class FLEngine {
             // output IS the local model (agg_scale = 1), which the Adam kernel already packed,
             // so the pack is needed only after host-side weight changes; later local steps
             // stage the Adam-packed local image too.
-            const bool solo = c_.world == 1 && c_.agg_scale == 1.0f && !need_pack_;
+            // (with DP the round's output is not the local model: always pack it from the fp32 image)
+            const bool solo = c_.world == 1 && c_.agg_scale == 1.0f && !need_pack_ && !dp_on_;
             // the peer all-reduce already wrote the packed image of its output
             const bool packed = solo || (peer_ != nullptr && !need_pack_);
             if (rec_ != nullptr) {
@@ -834,6 +870,13 @@ class FLEngine {
                 launch_adam(pg, pg, cb, si, ls, s, so, 1, score ? 1 : 0, mask);
             }
             else launch_adam(b_.local, pg, cb, so, ls, s);
+        }
+        if (dp_on_) {
+            // clip + noise of the contribution the last Adam kernel stored (fl_dp.hip); `so` holds
+            // the round's live flag and index
+            if (rec_ != nullptr) throw std::runtime_error("trial batch: no DP");
+            HIP_CHECK(fl_launch_dp(d_, dp_, b_.local, pg, cb, so, b_.rtab, s));
+            mark(TR_DP, s);
         }
         pending_cm_ = fused;
         cm_in_tail_ = false;
@@ -961,6 +1004,8 @@ class FLEngine {
     PeerPack pp_;                    // its bf16 pack epilogue (bf16 mode)
     bool eval_fedavg_ = true;  // world > 1 with peer: evaluation + all-reduce in one kernel
     bool fused_ = false;       // rounds evaluate the previous round inside the train kernel
+    bool dp_on_ = false;       // differential privacy: fl_dp_kernel after every round's last Adam kernel
+    FLDp dp_;
     bool pending_cm_ = false;  // the last issued round was fused: its metrics are not scored yet
     bool cm_in_tail_ = false;  // the last round's counts sit in the tail, not yet folded
     FLConfig c_;
@@ -974,7 +1019,7 @@ class FLEngine {
     long long graph_evals_ = 0;    // evaluation kernels inside the captured graph
     std::vector<FLLaunchRec>* rec_ = nullptr;  // TrialBatch: record launches instead of issuing them
     // trace(): an event after every launch, tagged with what was launched
-    enum { TR_PACK, TR_TRAIN, TR_ADAM, TR_EVAL, TR_ALLREDUCE, TR_EVAL_FEDAVG, TR_N };
+    enum { TR_PACK, TR_TRAIN, TR_ADAM, TR_EVAL, TR_ALLREDUCE, TR_EVAL_FEDAVG, TR_DP, TR_N };
     std::vector<std::pair<int, hipEvent_t>>* tev_ = nullptr;
     // trace markers without the system-scope release/acquire (device-side timing only needs the
     // marker's timestamp); FEDMI_TRACE_SYSFENCE=1 restores default events (A/B)
@@ -1258,6 +1303,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
              py::arg("close") = true, py::arg("gate_us") = 5000.0, py::arg("warm") = 0)
         .def("set_debug", &FLEngine::set_debug)
         .def("invalidate", &FLEngine::invalidate)
+        .def("set_dp_seed", &FLEngine::set_dp_seed)
         .def("set_early_stop", &FLEngine::set_early_stop)
         .def("reset_pending", &FLEngine::reset_pending)
         .def("attach_peer", &FLEngine::attach_peer, py::keep_alive<1, 2>())

@@ -31,6 +31,7 @@
 #include "fl_common.h"
 #include "fl_device.h"
 #include "peer_device.h"
+#include "fl_philox.h"
 #include <math.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -535,29 +536,6 @@ __global__ void fl_finalize_batch_kernel(MLPDesc d, const FLTrialDesc* __restric
 // ---------------------------------------------------------------------------------------
 // Synthetic income-shaped rows: Philox4x32-10 counter-based RNG, one row per thread.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
-                                             uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0;
-    const uint32_t h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-}
-
-__device__ __forceinline__ uint4 philox4x32(uint64_t ctr, uint32_t sub, uint64_t key) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = sub, c3 = 0x9E3779B9u;
-    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
 __global__ void fl_synth_kernel(float* __restrict__ X, int* __restrict__ y, long long n, int F,
                                 unsigned long long seed, unsigned long long row_offset,
                                 const float* __restrict__ w1, const float* __restrict__ w2, int H,
