@@ -147,16 +147,17 @@ adam_kernel(AdamArgs a) {
 
 // One optimizer step done for every active trial: bump its step counter.
 __global__ void step_count_kernel(long long* step, const int* active, int T) {
-    const int t = threadIdx.x;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < T && (active == nullptr || active[t])) step[t] += 1;
 }
 
 // ---------------------------------------------------------------------------------------
 // End of epoch, per trial (sklearn _fit_stochastic + _update_no_improvement_count):
 // loss_ = acc / n; curve append; count += (loss_ > best - tol) ? 1 : reset; best = min;
-// n_iter += 1; stop when count > n_iter_no_change or n_iter == max_iter.
+// n_iter += 1; stop when count > n_iter_no_change or n_iter == max_iter.  One thread per trial
+// over as many blocks as T needs; the epoch counter is bumped once, by thread 0 of block 0.
 __global__ void epoch_end_kernel(EpochArgs a) {
-    const int t = threadIdx.x;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0 && a.epoch_ctr != nullptr) *a.epoch_ctr += 1;
     if (t >= a.T || !a.active[t]) return;
     const double loss = a.loss_acc[t] / (double)a.n_samples;
@@ -229,12 +230,14 @@ hipError_t adam_launch(const AdamArgs& a, int T, hipStream_t s) {
 }
 
 hipError_t step_count_launch(long long* step, const int* active, int T, hipStream_t s) {
-    hipLaunchKernelGGL(step_count_kernel, dim3(1), dim3(64), 0, s, step, active, T);
+    if (T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(step_count_kernel, dim3((T + 63) / 64), dim3(64), 0, s, step, active, T);
     return hipGetLastError();
 }
 
 hipError_t epoch_end_launch(const EpochArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(epoch_end_kernel, dim3(1), dim3(64), 0, s, a);
+    if (a.T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(epoch_end_kernel, dim3((a.T + 63) / 64), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

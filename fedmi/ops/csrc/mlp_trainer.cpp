@@ -410,7 +410,9 @@ class MLPTrainerT {
 // Standalone layered GEMM entry (tests, wide-MLP path): dtype 0 f32 / 1 bf16.
 static void gemm_py(int M, int N, int K, uintptr_t A, int lda, int a_kc, uintptr_t B, int ldb, int b_kc, uintptr_t C,
                     int ldc, int epi, uintptr_t bias, uintptr_t mask, int ldmask, int mask_bf16, float alpha,
-                    float beta, int dtype, int splits, uintptr_t slab, uintptr_t Cbf16, uintptr_t stream) {
+                    float beta, int dtype, int splits, uintptr_t slab, uintptr_t Cbf16, uintptr_t stream,
+                    int batch, long long sA, long long sB, long long sC, long long sBias, long long sMask,
+                    uintptr_t active) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K;
@@ -419,22 +421,86 @@ static void gemm_py(int M, int N, int K, uintptr_t A, int lda, int a_kc, uintptr
     g.bias = reinterpret_cast<const float*>(bias);
     g.mask = reinterpret_cast<const void*>(mask); g.ldmask = ldmask; g.mask_bf16 = mask_bf16;
     g.alpha = alpha;
+    g.sA = sA; g.sB = sB; g.sC = sC; g.sBias = sBias; g.sMask = sMask;
+    g.active = reinterpret_cast<const int*>(active);
+    g.Cbf16 = reinterpret_cast<void*>(Cbf16);
     if (splits > 1) {
+        // the split form is one problem: slabs then a fixed-order reduce.  An epilogue or a bf16
+        // copy cannot be split (gemm_launch rejects them)
+        if (batch != 1) throw std::runtime_error("gemm: split-K is not batched");
         g.C = reinterpret_cast<float*>(slab); g.ldc = ldc; g.beta = 0.f;
         g.slab_stride = (size_t)M * ldc;
-        TR_CHECK(gemm_launch(g, dtype, a_kc, b_kc, GEMM_EPI_NONE, splits, 1, s));
+        TR_CHECK(gemm_launch(g, dtype, a_kc, b_kc, epi, splits, 1, s));
         TR_CHECK(splitk_reduce_launch(reinterpret_cast<float*>(slab), (size_t)M * ldc, splits,
                                       reinterpret_cast<float*>(C), (size_t)M * ldc, beta, s));
     } else {
         g.C = reinterpret_cast<float*>(C); g.ldc = ldc; g.beta = beta;
-        g.Cbf16 = reinterpret_cast<void*>(Cbf16);
-        TR_CHECK(gemm_launch(g, dtype, a_kc, b_kc, epi, 1, 1, s));
+        TR_CHECK(gemm_launch(g, dtype, a_kc, b_kc, epi, 1, batch, s));
     }
 }
 
-static void colsum_py(uintptr_t X, int M, int N, int ld, uintptr_t out, float beta, uintptr_t stream) {
-    TR_CHECK(colsum_launch(reinterpret_cast<const float*>(X), M, N, ld, reinterpret_cast<float*>(out), beta, 1, 0, 0,
-                           nullptr, reinterpret_cast<hipStream_t>(stream)));
+static void colsum_py(uintptr_t X, int M, int N, int ld, uintptr_t out, float beta, uintptr_t stream, int batch,
+                      long long sX, long long sOut, uintptr_t active) {
+    TR_CHECK(colsum_launch(reinterpret_cast<const float*>(X), M, N, ld, reinterpret_cast<float*>(out), beta, batch, sX,
+                           sOut, reinterpret_cast<const int*>(active), reinterpret_cast<hipStream_t>(stream)));
+}
+
+// The packed-trial forms of the layered kernels, as MLPTrainer launches them (op tests).
+static void xent_batched_py(uintptr_t z, int ldz, long long sZ, uintptr_t y, uintptr_t idx, int M, int C, int mode,
+                            float scale, uintptr_t dz, int lddz, long long sDz, uintptr_t loss_acc, uintptr_t pred,
+                            uintptr_t active, int T, uintptr_t stream) {
+    XentArgs a{};
+    a.z = reinterpret_cast<const float*>(z); a.ldz = ldz; a.sZ = sZ; a.y = reinterpret_cast<const int*>(y);
+    a.idx = reinterpret_cast<const int*>(idx); a.M = M; a.C = C; a.mode = mode; a.scale = scale;
+    a.dz = reinterpret_cast<float*>(dz); a.lddz = lddz; a.sDz = sDz;
+    a.loss_acc = reinterpret_cast<double*>(loss_acc); a.pred = reinterpret_cast<int*>(pred);
+    a.active = reinterpret_cast<const int*>(active);
+    TR_CHECK(xent_launch(a, T, reinterpret_cast<hipStream_t>(stream)));
+}
+
+static void adam_batched_py(uintptr_t p, uintptr_t m, uintptr_t v, uintptr_t g, uintptr_t anchor, uintptr_t wd_mask,
+                            size_t n, int style, uintptr_t lr, double b1, double b2, double eps, double wd, double mu,
+                            uintptr_t step, uintptr_t loss_acc, double l2_coef, uintptr_t active, uintptr_t p_bf16,
+                            int T, uintptr_t stream) {
+    AdamArgs a{};
+    a.p = reinterpret_cast<float*>(p); a.m = reinterpret_cast<float*>(m); a.v = reinterpret_cast<float*>(v);
+    a.g = reinterpret_cast<const float*>(g); a.anchor = reinterpret_cast<const float*>(anchor);
+    a.wd_mask = reinterpret_cast<const unsigned char*>(wd_mask); a.n = n; a.style = style;
+    a.lr = reinterpret_cast<const double*>(lr); a.beta1 = b1; a.beta2 = b2; a.eps = eps; a.wd = wd; a.mu = mu;
+    a.step = reinterpret_cast<const long long*>(step); a.loss_acc = reinterpret_cast<double*>(loss_acc);
+    a.l2_coef = l2_coef; a.active = reinterpret_cast<const int*>(active); a.p_bf16 = reinterpret_cast<void*>(p_bf16);
+    TR_CHECK(adam_launch(a, T, reinterpret_cast<hipStream_t>(stream)));
+}
+
+static void gather_rows_py(uintptr_t X, int ld, uintptr_t y, uintptr_t perms, uintptr_t epoch_ctr, long long n_perm,
+                           int off, int M, int F, uintptr_t out, int ldo, uintptr_t outb, uintptr_t yb,
+                           uintptr_t stream) {
+    GatherArgs a{reinterpret_cast<const float*>(X), ld, reinterpret_cast<const int*>(y),
+                 reinterpret_cast<const int*>(perms), reinterpret_cast<const int*>(epoch_ctr), n_perm, off, M, F,
+                 reinterpret_cast<float*>(out), ldo, reinterpret_cast<void*>(outb), reinterpret_cast<int*>(yb)};
+    TR_CHECK(gather_rows_launch(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+static void epoch_end_py(int T, uintptr_t epoch_ctr, uintptr_t loss_acc, uintptr_t best, uintptr_t count,
+                         uintptr_t n_iter, uintptr_t active, uintptr_t curve, long long n_samples, double tol,
+                         int n_iter_no_change, int max_iter, int tol_stop, uintptr_t stream) {
+    EpochArgs a{T, reinterpret_cast<int*>(epoch_ctr), reinterpret_cast<double*>(loss_acc),
+                reinterpret_cast<double*>(best), reinterpret_cast<int*>(count), reinterpret_cast<int*>(n_iter),
+                reinterpret_cast<int*>(active), reinterpret_cast<double*>(curve), n_samples, tol, n_iter_no_change,
+                max_iter, tol_stop};
+    TR_CHECK(epoch_end_launch(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+static void step_count_py(uintptr_t step, uintptr_t active, int T, uintptr_t stream) {
+    TR_CHECK(step_count_launch(reinterpret_cast<long long*>(step), reinterpret_cast<const int*>(active), T,
+                               reinterpret_cast<hipStream_t>(stream)));
+}
+
+static void confusion_py(uintptr_t pred, uintptr_t y, uintptr_t idx, int M, int C, int T, uintptr_t cm,
+                         uintptr_t stream) {
+    TR_CHECK(confusion_launch(reinterpret_cast<const int*>(pred), reinterpret_cast<const int*>(y),
+                              reinterpret_cast<const int*>(idx), M, C, T, reinterpret_cast<float*>(cm),
+                              reinterpret_cast<hipStream_t>(stream)));
 }
 
 static void to_bf16_py(uintptr_t x, uintptr_t y, size_t n, uintptr_t stream, float scale) {
@@ -587,7 +653,21 @@ void register_trainer(py::module_& m) {
         .def_property_readonly("split", &MLPTrainerT<double>::split)
         .def("stamps", &MLPTrainerT<double>::stamps)
         .def_property_readonly("P", &MLPTrainerT<double>::P);
-    m.def("gemm", &gemm_py);
-    m.def("colsum", &colsum_py);
+    // batched form (blockIdx.z / .y = problem, element strides, 0 = shared operand) by keyword
+    m.def("gemm", &gemm_py, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("A"), py::arg("lda"), py::arg("a_kc"),
+          py::arg("B"), py::arg("ldb"), py::arg("b_kc"), py::arg("C"), py::arg("ldc"), py::arg("epi"), py::arg("bias"),
+          py::arg("mask"), py::arg("ldmask"), py::arg("mask_bf16"), py::arg("alpha"), py::arg("beta"), py::arg("dtype"),
+          py::arg("splits"), py::arg("slab"), py::arg("Cbf16"), py::arg("stream"), py::arg("batch") = 1,
+          py::arg("sA") = 0, py::arg("sB") = 0, py::arg("sC") = 0, py::arg("sBias") = 0, py::arg("sMask") = 0,
+          py::arg("active") = 0);
+    m.def("colsum", &colsum_py, py::arg("X"), py::arg("M"), py::arg("N"), py::arg("ld"), py::arg("out"),
+          py::arg("beta"), py::arg("stream"), py::arg("batch") = 1, py::arg("sX") = 0, py::arg("sOut") = 0,
+          py::arg("active") = 0);
+    m.def("xent_batched", &xent_batched_py);
+    m.def("adam_batched", &adam_batched_py);
+    m.def("gather_rows", &gather_rows_py);
+    m.def("epoch_end", &epoch_end_py);
+    m.def("step_count", &step_count_py);
+    m.def("confusion", &confusion_py);
     m.def("to_bf16", &to_bf16_py, py::arg("x"), py::arg("y"), py::arg("n"), py::arg("stream"), py::arg("scale") = 1.f);
 }

@@ -133,6 +133,30 @@ def test_hip_packed_equals_single(data):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_hip_packed_more_than_64_estimators(data, dtype):
+    """65 packed estimators: the step counter and the end-of-epoch rule index trials across blocks
+    of 64 threads, so estimator 64 must train like every other (it used to keep step 0 -- fp32 Adam
+    then divides by 1 - beta1^0 -- and never saw an epoch end: n_iter_ 0, an empty loss curve)."""
+    X, y = data[0][:200], data[1][:200]
+    lrs = [0.001 + 0.0002 * i for i in range(65)]
+    kw = dict(hidden_layer_sizes=(4,), max_iter=3, random_state=42, backend="hip", dtype=dtype)
+    packed = [MLPClassifier(learning_rate_init=lr, **kw) for lr in lrs]
+    fit_packed(packed, X, y)
+    last = packed[64]
+    assert [e.n_iter_ for e in packed] == [3] * 65
+    assert len(last.loss_curve_) == 3 and np.isfinite(last.loss_curve_).all()
+    for w in last.coefs_ + last.intercepts_:
+        assert np.isfinite(w).all()
+    if dtype == "float64":
+        single = MLPClassifier(learning_rate_init=lrs[64], **kw).fit(X, y)
+        for u, v in zip(single.coefs_ + single.intercepts_, last.coefs_ + last.intercepts_):
+            np.testing.assert_allclose(u, v, rtol=1e-6, atol=1e-7)
+        np.testing.assert_allclose(last.loss_curve_, single.loss_curve_, rtol=1e-6)
+        assert last.n_iter_ == single.n_iter_
+
+
+@pytest.mark.gpu
 def test_hip_sweep_two_ranks_sharing_the_gpu():
     """The [H] entrypoint with two ranks on one GPU (``--device cuda:0``): its packed jobs run from
     several host threads per rank.  Jobs whose epoch graphs were captured inside those threads saw
