@@ -62,6 +62,13 @@ def parse_args(argv=None):
     ap.add_argument("--dp-delta", type=float, default=1e-5, help="delta of the reported (epsilon, delta)")
     ap.add_argument("--dp-seed", type=int, default=None,
                     help="noise seed for reproducible experiments (default: a private seed per client)")
+    ap.add_argument("--server-opt", choices=["none", "sgd", "adagrad", "adam", "yogi"], default="none",
+                    help="server optimizer on the aggregated update: sgd = FedAvgM, adagrad / adam / yogi = Reddi et "
+                         "al. 2021 (none = plain FedAvg, the reference)")
+    ap.add_argument("--server-lr", type=float, default=1.0, help="server learning rate")
+    ap.add_argument("--server-momentum", type=float, default=0.9, help="server momentum b1")
+    ap.add_argument("--server-beta2", type=float, default=0.99, help="server second-moment decay b2 (adam, yogi)")
+    ap.add_argument("--server-tau", type=float, default=1e-3, help="server adaptivity tau (adagrad, adam, yogi)")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -155,6 +162,11 @@ def _dp_fields(a) -> dict:
     return dict(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_seed=a.dp_seed)
 
 
+def _server_fields(a) -> dict:
+    return dict(server_opt=a.server_opt, server_lr=a.server_lr, server_momentum=a.server_momentum,
+                server_beta2=a.server_beta2, server_tau=a.server_tau)
+
+
 def _print_privacy(a, rounds: int) -> None:
     """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
     if a.dp_clip > 0.0:
@@ -176,7 +188,7 @@ def main_clients(a, comm):
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
-                       **_dp_fields(a))
+                       **_dp_fields(a), **_server_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -208,6 +220,13 @@ def main(argv=None):
         raise SystemExit("--dp-noise needs --dp-clip > 0")
     if a.wide and a.dp_clip > 0.0:
         raise SystemExit("--dp-clip is not supported with --wide")
+    if a.wide and a.server_opt != "none":
+        raise SystemExit("--server-opt is not supported with --wide")
+    try:
+        from fedmi.fl.engine import server_opt_id
+        server_opt_id(EngineConfig(**_server_fields(a)))
+    except ValueError as e:
+        raise SystemExit(f"--server-*: {e}")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -227,7 +246,7 @@ def main(argv=None):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, participation=a.participation, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
-                       debug=a.debug, dtype=a.dtype, **_dp_fields(a))
+                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

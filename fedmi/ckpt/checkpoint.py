@@ -133,11 +133,15 @@ def save_checkpoint(path: str, trainer) -> None:
     dp = {} if "dp_seed" not in st else {
         "dp_seed": np.asarray([int(st["dp_seed"]) & 0xFFFFFFFF, int(st["dp_seed"]) >> 32], np.int64),
         "update_norm": np.asarray(st["history"]["update_norm"], np.float32)}
+    # server optimizer: every rank holds the same replicated m / v; each client's file carries its copy
+    sv = {} if "server_m" not in st else {"server_m": np.asarray(st["server_m"], np.float32),
+                                          "server_v": np.asarray(st["server_v"], np.float32)}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
         {"local": np.asarray(st["local"], np.float32), "exp_avg": np.asarray(st["exp_avg"], np.float32),
          "exp_avg_sq": np.asarray(st["exp_avg_sq"], np.float32),
          # this client's own Adam step count (differs from rounds x local_steps when clients are sampled)
-         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp}, tmp, metadata={"round": str(R)}))
+         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv}, tmp,
+        metadata={"round": str(R)}))
     gflat = flat_to_dict(st["global"], eng.dims)
     if eng.rank == 0:
         _atomic(os.path.join(path, tagged("weights.safetensors", R)), lambda tmp: save_weights(tmp, gflat, R))
@@ -205,7 +209,9 @@ def resume(path: str, trainer) -> int:
         lo, hi = (int(x) for x in np.asarray(c["dp_seed"]).reshape(-1)[:2])
         st["dp_seed"] = lo | (hi << 32)
         st["history"]["update_norm"] = np.asarray(c["update_norm"], np.float32)
-    eng.load_portable_state(st)
+    if "server_m" in c:
+        st["server_m"], st["server_v"] = np.asarray(c["server_m"], np.float32), np.asarray(c["server_v"], np.float32)
+    eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer
     return st["rounds"]
 
 

@@ -112,6 +112,23 @@ class EngineConfig:
     dp_clip: float = 0.0
     dp_noise: float = 0.0
     dp_seed: Optional[int] = None
+    # Server optimizer (Hsu et al. 2019, FedAvgM; Reddi et al. 2021, FedAdagrad / FedAdam / FedYogi):
+    # with x the image a round trained from and a its aggregated image (after the all-reduce, so
+    # after DP clip + noise), d = a - x is a pseudo-gradient and the next global image is
+    #   "sgd":     m = b1 m + d;            x + lr m
+    #   "adagrad": m = b1 m + (1 - b1) d;   v = v + d^2;                          x + lr m / (sqrt(v) + tau)
+    #   "adam":    same m;                  v = b2 v + (1 - b2) d^2;              same step
+    #   "yogi":    same m;                  v = v - (1 - b2) d^2 sign(v - d^2);   same step
+    # with b1 = server_momentum, b2 = server_beta2, lr = server_lr, tau = server_tau; m starts at 0, v
+    # at tau^2, no bias correction.  Every rank computes the same step on the same all-reduced image
+    # (no extra communication), so every client must start from the same model (FederatedMLPLearning
+    # and ClientGroup seed it so).  "none": off (nothing of a round changes).  The local models, client
+    # Adam moments, local metrics and the early-stop rule are untouched; rounds are classic.
+    server_opt: str = "none"
+    server_lr: float = 1.0
+    server_momentum: float = 0.9
+    server_beta2: float = 0.99
+    server_tau: float = 1e-3
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -150,6 +167,53 @@ def dp_enabled(cfg: EngineConfig) -> bool:
     return S > 0.0
 
 
+SERVER_OPTS = ("none", "sgd", "adagrad", "adam", "yogi")
+
+
+def server_opt_id(cfg: EngineConfig) -> int:
+    """Validate the server-optimizer fields; the optimizer's index in ``SERVER_OPTS`` (0 = off)."""
+    if cfg.server_opt not in SERVER_OPTS:
+        raise ValueError(f"server_opt must be one of {SERVER_OPTS}, got {cfg.server_opt!r}")
+    lr, b1, b2, tau = (float(cfg.server_lr), float(cfg.server_momentum), float(cfg.server_beta2),
+                       float(cfg.server_tau))
+    if not (math.isfinite(lr) and lr > 0.0):
+        raise ValueError(f"server_lr must be a finite number > 0, got {cfg.server_lr!r}")
+    if not 0.0 <= b1 < 1.0:
+        raise ValueError(f"server_momentum must be in [0, 1), got {cfg.server_momentum!r}")
+    if not 0.0 <= b2 < 1.0:
+        raise ValueError(f"server_beta2 must be in [0, 1), got {cfg.server_beta2!r}")
+    kind = SERVER_OPTS.index(cfg.server_opt)
+    if kind >= 2 and not (math.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"server_tau must be a finite number > 0 for server_opt={cfg.server_opt!r}, "
+                         f"got {cfg.server_tau!r}")
+    return kind
+
+
+def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, m: torch.Tensor,
+                v: Optional[torch.Tensor]) -> torch.Tensor:
+    """One server-optimizer step in the tensors' dtype: updates ``m`` (and ``v``) in place and
+    returns the new global parameters.  The operation order is fl_server.hip's (which fuses
+    ``b1 m + .``, ``v + d^2``, ``b2 v + .`` and ``x + lr .`` into single roundings)."""
+    dt = x.dtype
+    sc = lambda s: torch.tensor(float(s), dtype=torch.float32).to(dt)   # the kernel's fp32 scalars
+    lr, b1, b2, tau = sc(cfg.server_lr), sc(cfg.server_momentum), sc(cfg.server_beta2), sc(cfg.server_tau)
+    omb1 = sc(1.0 - float(cfg.server_momentum))
+    omb2 = sc(1.0 - float(cfg.server_beta2))
+    d = a - x
+    if kind == 1:
+        m.mul_(b1).add_(d)
+        return x + lr * m
+    m.mul_(b1).add_(omb1 * d)
+    d2 = d * d
+    if kind == 2:
+        v.add_(d2)
+    elif kind == 3:
+        v.mul_(b2).add_(omb2 * d2)
+    else:
+        v.sub_(omb2 * d2 * torch.sign(v - d2))
+    return x + lr * (m / (v.sqrt() + tau))
+
+
 class _History:
     def __init__(self, max_rounds: int, world: int, dp: bool = False):
         # DP engines: this client's pre-clip update norm per round (0: not sampled)
@@ -186,6 +250,7 @@ class RoundEngineBase:
                  init_flat: np.ndarray, n_total: Optional[int] = None, client_sizes=None):
         self.cfg = cfg
         self.dp = dp_enabled(cfg)
+        self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
@@ -313,6 +378,22 @@ class RoundEngineBase:
     def _set_dp_seed(self, seed: int) -> None:
         self.dp_seed = int(seed)
 
+    def _server_state_in(self, st: dict):
+        """The dense (server_m, server_v) of a portable state for this engine, or None without a
+        server optimizer; a state and an engine that disagree on having one do not match."""
+        has = st.get("server_m") is not None
+        if has != bool(self.server):
+            raise ValueError("checkpoint and engine disagree on the server optimizer: the state "
+                             + ("carries" if has else "has no") + " server_m / server_v, the engine has server_opt="
+                             + repr(self.cfg.server_opt))
+        if not self.server:
+            return None
+        m = np.asarray(st["server_m"], np.float32).reshape(-1)
+        v = np.asarray(st["server_v"], np.float32).reshape(-1)
+        if m.shape != (self.P,) or v.shape != (self.P,):
+            raise ValueError(f"server optimizer state has {m.shape[0]} / {v.shape[0]} entries, the model {self.P}")
+        return m, v
+
 
 # ---------------------------------------------------------------------------------------
 # Torch (CPU / oracle) engine
@@ -335,6 +416,10 @@ class TorchRoundEngine(RoundEngineBase):
         self.stopper = EarlyStopper(cfg.patience, cfg.tolerance, cfg.rtol, enabled=cfg.early_stop)
         self.global_params = self.model.flat.detach().clone()
         self.rounds_issued = 0
+        if self.server:
+            # server optimizer state in dense named_parameters() order (v starts at tau^2)
+            self.server_m = torch.zeros(self.P, dtype=torch.float32)
+            self.server_v = torch.full((self.P,), float(np.float32(cfg.server_tau)) ** 2, dtype=torch.float32)
 
     def train_one_epoch(self) -> float:
         """``local_steps`` full-batch Adam steps + one StepLR step (reference C:63-73)."""
@@ -457,8 +542,13 @@ class TorchRoundEngine(RoundEngineBase):
         if sampling:
             buf[:self.P] /= buf[-1]
             buf = buf[:-1]
+        new = buf[:self.P]
+        if self.server:
+            # the aggregated image is a pseudo-gradient step from the image the round trained from
+            new = server_step(self.server, self.cfg, self.global_params.detach().cpu().to(torch.float32),
+                              new.to(torch.float32), self.server_m, self.server_v)
         with torch.no_grad():
-            self.model.flat.copy_(buf[:self.P].to(self.device))
+            self.model.flat.copy_(new.to(self.device))
         self.global_params = self.model.flat.detach().clone()
         self._finalize(r, buf[self.P:].numpy())
         self.rounds_issued += 1
@@ -549,11 +639,17 @@ class TorchRoundEngine(RoundEngineBase):
                    "stopped": bool(sp.stopped), "stop_round": int(self.hist.stop_round)},
             "history": self.hist.as_dict(),
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
+            **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
+               if self.server else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
         r = int(st["rounds"])
         cfg = self.cfg
+        sv = self._server_state_in(st)
+        if sv is not None:
+            self.server_m = torch.as_tensor(sv[0].copy())
+            self.server_v = torch.as_tensor(sv[1].copy())
         with torch.no_grad():
             self.model.flat.copy_(torch.as_tensor(np.asarray(st["global"], np.float32)))
         self.global_params = self.model.flat.detach().clone()
@@ -642,7 +738,7 @@ class HipRoundEngine(RoundEngineBase):
         # round run past a stop discarded bit-exactly: FLEngine.late_fold)
         # (differential privacy: classic rounds, see fl_engine.cpp)
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
-                     and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp)
+                     and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server)
         comm_len = self.Pimg + self.world * self.tail_stride * (2 if self._lag else 1)
         if comm_buffers is None:
             self.params = [torch.zeros(comm_len, **f32), torch.zeros(comm_len, **f32)]
@@ -709,6 +805,16 @@ class HipRoundEngine(RoundEngineBase):
             ecfg.update({"dp_clip": float(cfg.dp_clip), "dp_noise": float(cfg.dp_noise) > 0.0,
                          "dp_seed": int(self.dp_seed)})
             bufs.update({"dp_sigma": self.dp_sigma_dev.data_ptr(), "dp_norm": self.dp_norm.data_ptr()})
+        if self.server:
+            # server optimizer state: image-shaped fp32 (m = 0; v = tau^2 everywhere, padding included)
+            if comm_buffers is not None:
+                raise ValueError("trial packing (comm_buffers) does not run a server optimizer (server_opt)")
+            self.server_m = torch.zeros(self.Pimg, **f32)
+            self.server_v = torch.full((self.Pimg,), float(np.float32(cfg.server_tau)) ** 2, **f32)
+            ecfg.update({"server_opt": int(self.server), "server_lr": float(cfg.server_lr),
+                         "server_momentum": float(cfg.server_momentum), "server_beta2": float(cfg.server_beta2),
+                         "server_tau": float(cfg.server_tau)})
+            bufs.update({"server_m": self.server_m.data_ptr(), "server_v": self.server_v.data_ptr()})
         for i, R in enumerate(R_try):
             self.slab = torch.zeros(((self.n_local + R - 1) // R) * slab_stride, **f32)
             ecfg["R"] = R
@@ -847,12 +953,22 @@ class HipRoundEngine(RoundEngineBase):
 
     def _phase_allreduce(self, r: int) -> None:
         if self.world == 1:
+            if self.server:   # FedAvg of one client is the identity; the server step still runs
+                self.engine.phase(r, 2, self._stream(), None)
             return
         if self._engine_reduces():
             self.engine.phase(r, 2, self._stream(), self._native_comm)
         else:
             with torch.cuda.stream(self.stream):
                 self.comm.allreduce_(self.params[(r + 1) & 1])
+            self.server_step(r)
+
+    def server_step(self, r: int) -> None:
+        """Server-optimizer step of round ``r`` on the aggregated image a caller summed into
+        ``params[(r + 1) & 1]`` (host-plane all-reduce, :class:`~fedmi.fl.simulate.ClientGroup`);
+        nothing without a server optimizer."""
+        if self.server:
+            self.engine.phase(r, 3, self._stream(), None)
 
     def _issue_debug(self, n: int) -> None:
         """Debug mode: every phase launched eagerly and synchronised, so a
@@ -902,7 +1018,7 @@ class HipRoundEngine(RoundEngineBase):
         :meth:`profile`, which runs classic phases): the native engine issues them eagerly with
         a hipEvent after every launch behind a gate kernel (FLEngine::trace), so the kernels
         run back to back.  Returns mean us per round by kernel kind (``train``, ``adam``,
-        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``), ``round`` and launch counts.  Each
+        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``server``), ``round`` and launch counts.  Each
         interval carries the eager launch + event marker cost: measured on MI355X (bench N = 1,
         profiles/kernel_trace_r5.log) ~1.5 us per kernel over the rocprofv3 kernel durations
         (markers without the system-scope fence; ~3.2 us with it).
@@ -938,6 +1054,7 @@ class HipRoundEngine(RoundEngineBase):
                 for r in range(r0, r0 + n):
                     self.engine.run_local(r, s)
                     self.comm.allreduce_(self.params[(r + 1) & 1])
+                    self.server_step(r)
             self.rounds_issued += n
             return
         # lagged engines: graphs hold lagged rounds only, the last round of the call is eager and
@@ -1225,12 +1342,15 @@ class HipRoundEngine(RoundEngineBase):
                    "stop_round": int(st["stop_round"])},
             "history": self.hist.as_dict(),
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
+            **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
+                "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
         r = int(st["rounds"])
         if r > self.cfg.max_rounds:
             raise ValueError(f"checkpoint has {r} rounds > max_rounds {self.cfg.max_rounds}")
+        sv = self._server_state_in(st)
         self.stream.synchronize()
         dev = self.device
         img = lambda a: torch.as_tensor(dense_to_image(np.asarray(a, np.float32), self.dims), device=dev)
@@ -1239,6 +1359,12 @@ class HipRoundEngine(RoundEngineBase):
             self.local.copy_(img(st["local"]))
             self.mom.copy_(img(st["exp_avg"]))
             self.vel.copy_(img(st["exp_avg_sq"]))
+            if sv is not None:
+                self.server_m.copy_(img(sv[0]))
+                # padding of v keeps tau^2 (dense_to_image pads with zeros)
+                pad = torch.as_tensor(dense_to_image(np.ones(self.P, np.float32), self.dims), device=dev) == 0
+                self.server_v.copy_(torch.where(pad, torch.full_like(self.server_v, float(np.float32(self.cfg.server_tau)) ** 2),
+                                                img(sv[1])))
             es = st["es"]
             rec = np.zeros(1, dtype=_STATE_DTYPE)
             rec["next_round"] = r

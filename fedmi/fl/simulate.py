@@ -70,7 +70,8 @@ class ClientGroup:
                 c.graph_rounds = 0
             comm = SimRank(self.k, r, self.device)
             # FederatedMLPLearning's seeding: one init stream per (seed, rank)
-            flat0 = init_flat(dims, seed * 1000003 + r)
+            # (server optimizer: one common starting model, see FederatedMLPLearning)
+            flat0 = init_flat(dims, seed * 1000003 + (r if cfg.server_opt == "none" else 0))
             if backend == "hip":
                 e = HipRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total,
                                    device=self.device, client_sizes=[len(i) for i in idx])
@@ -103,6 +104,7 @@ class ClientGroup:
             for b in bufs:
                 b.copy_(tot)
         for e in self.clients:
+            e.server_step(r)              # server optimizer: every client steps its replica of the sum
             e.rounds_issued = r + 1
 
     def _round_torch(self) -> None:

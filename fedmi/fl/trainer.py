@@ -60,7 +60,9 @@ class FederatedMLPLearning:
         dims = [self.input_size, *self.hidden_sizes, self.output_size]
         # reference: unseeded torch init per rank -> seeded per rank (different models
         # until the first FedAvg, like the reference)
-        flat0 = init_flat(dims, seed * 1000003 + rank)
+        # (a server optimizer steps from the image a round trained from, which must be the same on
+        # every rank from round 0 on: all clients then start from rank 0's model)
+        flat0 = init_flat(dims, seed * 1000003 + (rank if cfg.server_opt == "none" else 0))
         self.engine = make_engine(self.X_local, self.y_local, self.output_size, cfg, comm, flat0,
                                   n_total=n_total, backend=backend)
         self.device = getattr(self.engine, "device", torch.device("cpu"))

@@ -85,6 +85,9 @@ class FedTrialGroup:
             # the trials of a group share launches and one collective; a private sweep would also
             # have to account for every trial's rounds (fedmi/privacy/accountant.py)
             raise ValueError("fed_sweep does not run differentially private trials (dp_clip / dp_noise)")
+        if base.server_opt != "none":
+            # the trials share launches and one collective; a server step per trial is not batched
+            raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         rank = comm.rank if comm is not None else 0

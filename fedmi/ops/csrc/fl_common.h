@@ -313,6 +313,32 @@ struct FLDp {
     float* norm_hist;    // [max_rounds] pre-clip ||local - input||_2 of this client (0: not sampled)
 };
 
+// Server optimizer (fl_server.hip): parameters of the per-round server step, passed to that
+// kernel alone, as FLDp is.  With x the image the round trained from, a the aggregated image and
+// d = a - x, the kernel keeps m (and, adaptive kinds, v) across rounds and replaces a by
+//   FL_SERVER_SGD     : m = b1 m + d;            x + lr m                      (FedAvgM)
+//   FL_SERVER_ADAGRAD : m = b1 m + (1 - b1) d;   v = v + d^2;                  x + lr m / (sqrt(v) + tau)
+//   FL_SERVER_ADAM    : same m;                  v = b2 v + (1 - b2) d^2;      same step
+//   FL_SERVER_YOGI    : same m;                  v = v - (1 - b2) d^2 sign(v - d^2); same step
+// (Reddi et al. 2021, Algorithm 2: no bias correction, v starts at tau^2).
+#define FL_SERVER_NONE 0
+#define FL_SERVER_SGD 1
+#define FL_SERVER_ADAGRAD 2
+#define FL_SERVER_ADAM 3
+#define FL_SERVER_YOGI 4
+struct FLServer {
+    int kind;            // FL_SERVER_*
+    int max_rounds;      // rounds past it are not stepped
+    float lr;            // server learning rate
+    float b1;            // momentum
+    float omb1;          // (float)(1 - b1)
+    float b2;            // second-moment decay (Adam, Yogi)
+    float omb2;          // (float)(1 - b2)
+    float tau;           // adaptivity (added to sqrt(v)); v starts at tau^2
+    float* m;            // [Pimg] fp32, caller-owned
+    float* v;            // [Pimg] fp32, caller-owned (adaptive kinds; unused by FL_SERVER_SGD)
+};
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -347,6 +373,12 @@ hipError_t fl_launch_eval(const MLPDesc& d, const FLConfig& c, const FLBuffers& 
 // first Pimg floats of `comm` from `local` and the round's input image `pg`
 hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, const float* pg, float* comm,
                         const FLState* st, const float* rtab, hipStream_t s);
+// (fl_server.hip) server-optimizer step of the round whose state is `st`: `x` = the image the round
+// trained from, `a` = its aggregated image, replaced in place (first Pimg floats only) by the new
+// global image.  `e` / `pk` (bf16 mode, else null): the same launch also writes the packed
+// split-bf16 image of the result into `pk`.
+hipError_t fl_launch_server(const MLPDesc& d, const FLServer& p, const float* x, float* a, const FLState* st,
+                            const MLPDescB* e, char* pk, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

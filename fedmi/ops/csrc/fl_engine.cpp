@@ -285,11 +285,35 @@ class FLEngine {
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
             fused_ = false;
         }
+        // Server optimizer (fl_server.hip): the round's output is x + (a server step), not the
+        // aggregated local models, so a fused round would score the wrong model through the global
+        // image and a lagged round's in-Adam exchange would publish an image the step then has to
+        // replace: classic rounds only, as with DP.
+        std::memset(&sv_, 0, sizeof(sv_));
+        sv_.kind = cfg.contains("server_opt") ? cfg["server_opt"].cast<int>() : FL_SERVER_NONE;
+        server_on_ = sv_.kind != FL_SERVER_NONE;
+        if (server_on_) {
+            if (sv_.kind < FL_SERVER_SGD || sv_.kind > FL_SERVER_YOGI)
+                throw std::runtime_error("FLEngine: unknown server optimizer");
+            const double b1 = cfg["server_momentum"].cast<double>(), b2 = cfg["server_beta2"].cast<double>();
+            sv_.max_rounds = c_.max_rounds;
+            sv_.lr = (float)cfg["server_lr"].cast<double>();
+            sv_.b1 = (float)b1;
+            sv_.omb1 = (float)(1.0 - b1);
+            sv_.b2 = (float)b2;
+            sv_.omb2 = (float)(1.0 - b2);
+            sv_.tau = (float)cfg["server_tau"].cast<double>();
+            sv_.m = as_ptr<float>(bufs["server_m"].cast<uintptr_t>());
+            sv_.v = sv_.kind == FL_SERVER_SGD ? nullptr : as_ptr<float>(bufs["server_v"].cast<uintptr_t>());
+            if (sv_.m == nullptr || (sv_.kind != FL_SERVER_SGD && sv_.v == nullptr))
+                throw std::runtime_error("FLEngine: the server optimizer needs its state buffers");
+            fused_ = false;
+        }
         eval_fedavg_ = !cfg.contains("eval_fedavg") || cfg["eval_fedavg"].cast<bool>();
         // Lagged evaluation (fl_common.h FL_EVAL_LAGGED): several clients, early stopping off,
         // bf16 kernels, and room in LDS for the second parameter image.  The comm buffer then
         // carries the lag region A after the tails (the caller sized it: comm_len).
-        const bool lag_req = !dp_on_ && cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
+        const bool lag_req = !dp_on_ && !server_on_ && cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
         if (lag_req) c_.lag_off = d_.Pimg + c_.tail_len;
         comm_len_ = d_.Pimg + c_.tail_len * (lag_req ? 2 : 1);
         const bool emulate = cfg.contains("emulate_clients") && cfg["emulate_clients"].cast<bool>();
@@ -385,11 +409,14 @@ class FLEngine {
         for (int r = r0; r < r0 + n; ++r) issue_round(r, s, comm, true, lagged() && !(close && r == r0 + n - 1));
     }
 
-    // Local part of round r (no all-reduce; the caller reduces a shared buffer).
-    void run_local(int r, uintptr_t stream) { issue_round(r, as_stream(stream), nullptr, false); }
+    // Local part of round r (no all-reduce; the caller reduces a shared buffer -- and, on a
+    // server-optimizer engine, issues phase 3 once the sum is in this engine's buffer).
+    void run_local(int r, uintptr_t stream) { issue_round(r, as_stream(stream), nullptr, false, false, false); }
 
     // One phase of round r: 0 = local training (all local steps), 1 = local evaluation,
-    // 2 = FedAvg all-reduce.  Used by the step-by-step reference API
+    // 2 = FedAvg all-reduce (+ the server-optimizer step when the engine aggregates itself),
+    // 3 = the server-optimizer step alone (the caller aggregated the round's buffer).  Used by the
+    // step-by-step reference API
     // (train_one_epoch / evaluate_local / federated_averaging); always classic rounds.
     void phase(int r, int which, uintptr_t stream, RcclComm* comm) {
         hipStream_t s = as_stream(stream);
@@ -402,8 +429,12 @@ class FLEngine {
             cm_in_tail_ = true;
         } else if (which == 2) {
             issue_allreduce(r, s, comm);
+            if (aggregates(comm)) issue_server(r, s);
+        } else if (which == 3) {
+            if (!server_on_) throw std::runtime_error("phase 3: no server optimizer");
+            issue_server(r, s);
         } else {
-            throw std::runtime_error("phase: 0, 1 or 2");
+            throw std::runtime_error("phase: 0, 1, 2 or 3");
         }
     }
 
@@ -569,6 +600,16 @@ class FLEngine {
         drop_graph();
     }
 
+    // bf16 engines: the packed split-bf16 image of the round's input weights as the train kernel
+    // stages it (param_bytes; tests compare the server step's pack with the stand-alone one)
+    py::bytes packed_global(uintptr_t stream) const {
+        if (dtype_ != 1) throw std::runtime_error("packed_global: bf16 engines only");
+        HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+        std::string out((size_t)e_.param_bytes, '\0');
+        HIP_CHECK(hipMemcpy(out.data(), b_.pk_global, out.size(), hipMemcpyDeviceToHost));
+        return py::bytes(out);
+    }
+
     // The host wrote the global weights (set_weights / resume): the next round repacks them.
     void invalidate() { need_pack_ = true; }
 
@@ -701,7 +742,8 @@ class FLEngine {
         }
         tev_ = nullptr;
         HIP_CHECK(hipStreamSynchronize(s));
-        static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp"};
+        static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
+                                          "server"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -767,14 +809,31 @@ class FLEngine {
         o["comm_len"] = comm_len_;
         o["lagged_eval"] = lagged();
         o["dp"] = dp_on_;                                // clipped (+ noised) contributions, classic rounds
+        static const char* server_names[] = {"none", "sgd", "adagrad", "adam", "yogi"};
+        o["server_opt"] = std::string(server_names[sv_.kind]);  // server step after every aggregation, classic rounds
         o["state_bytes"] = (int)sizeof(FLState);
         return o;
     }
 
   private:
     // Re-running a round's Adam kernel alone republishes the un-noised w * local into the comm buffer.
+    // ... and on a server-optimizer engine it overwrites the new global image with w * local.
     void no_relaunch_with_dp(const char* what) const {
         if (dp_on_) throw std::runtime_error(std::string(what) + ": not on a DP engine (use trace)");
+        if (server_on_)
+            throw std::runtime_error(std::string(what) + ": not on a server-optimizer engine (use trace)");
+    }
+    // The engine produces round outputs itself: one client, its peer all-reduce, or RCCL.
+    bool aggregates(const RcclComm* comm) const { return c_.world < 2 || peer_ != nullptr || comm != nullptr; }
+    // Server-optimizer step of round r (fl_server.hip) on the aggregated image in pbuf_[(r+1)&1];
+    // st_[(r+1)&1] holds the round's live flag and index.  bf16: also the packed image of the result.
+    void issue_server(int r, hipStream_t s) {
+        if (!server_on_) return;
+        if (rec_ != nullptr) throw std::runtime_error("trial batch: no server optimizer");
+        HIP_CHECK(fl_launch_server(d_, sv_, pbuf_[r & 1], pbuf_[(r + 1) & 1], st_[(r + 1) & 1],
+                                   dtype_ == 1 ? &e_ : nullptr, dtype_ == 1 ? b_.pk_global : nullptr, s));
+        mark(TR_SERVER, s);
+        srv_packed_ = dtype_ == 1;
     }
     void launch_train(const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
                       int mode = FL_EVAL_CLASSIC, float* cm_out = nullptr, int fold_mask = FL_FOLD_B) {
@@ -794,9 +853,12 @@ class FLEngine {
             // so the pack is needed only after host-side weight changes; later local steps
             // stage the Adam-packed local image too.
             // (with DP the round's output is not the local model: always pack it from the fp32 image)
-            const bool solo = c_.world == 1 && c_.agg_scale == 1.0f && !need_pack_ && !dp_on_;
+            // (nor with a server optimizer, whose step packs the new global image itself: then neither
+            // the peer all-reduce's pack epilogue nor the Adam-packed local image is the round's input)
+            const bool solo = c_.world == 1 && c_.agg_scale == 1.0f && !need_pack_ && !dp_on_ && !server_on_;
             // the peer all-reduce already wrote the packed image of its output
-            const bool packed = solo || (peer_ != nullptr && !need_pack_);
+            const bool packed = server_on_ ? (srv_packed_ && !need_pack_) : (solo || (peer_ != nullptr && !need_pack_));
+            if (ls == 0) srv_packed_ = false;  // a later step without a server launch in between repacks
             if (rec_ != nullptr) {
                 if (ls == 0 && !packed) rec_->push_back({FLLaunchRec::PACK, {0, 0, 0, 0}, {pg, b_.pk_global}});
                 rec_->push_back({FLLaunchRec::TRAIN, {ls, solo ? 1 : 0, mode, fold_mask}, {pg, si, so, cm_out}});
@@ -910,7 +972,9 @@ class FLEngine {
         mark(TR_ALLREDUCE, s);
     }
     // `lag`: a lagged round -- no evaluation; the next round's train kernel scores it.
-    void issue_round(int r, hipStream_t s, RcclComm* comm, bool allow_fused, bool lag = false) {
+    // `server`: the round ends with the server-optimizer step (not when the caller aggregates).
+    void issue_round(int r, hipStream_t s, RcclComm* comm, bool allow_fused, bool lag = false, bool server = true) {
+        server = server && server_on_ && aggregates(comm);
         const bool fused = fused_ && allow_fused;
         lag = lag && lagged() && !fused;
         if (!fused) flush_pending_eval(r, s);
@@ -925,6 +989,7 @@ class FLEngine {
             // evaluation and the one-shot all-reduce in one kernel (peer_device.h)
             issue_eval_fedavg(r, s);
             cm_in_tail_ = true;
+            if (server) issue_server(r, s);
             return;
         }
         if (!fused) {
@@ -932,6 +997,7 @@ class FLEngine {
             cm_in_tail_ = true;
         }
         issue_allreduce(r, s, comm);
+        if (server) issue_server(r, s);
     }
     // The fused evaluation + FedAvg grid (evaluation blocks + all-reduce blocks) must be
     // resident in one wave, which needs two evaluation workgroups per CU (measured: with one
@@ -1006,6 +1072,9 @@ class FLEngine {
     bool fused_ = false;       // rounds evaluate the previous round inside the train kernel
     bool dp_on_ = false;       // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLDp dp_;
+    bool server_on_ = false;   // server optimizer: fl_server_kernel after every round's aggregation
+    bool srv_packed_ = false;  // bf16: pk_global holds the last server step's output (nothing ran since)
+    FLServer sv_;
     bool pending_cm_ = false;  // the last issued round was fused: its metrics are not scored yet
     bool cm_in_tail_ = false;  // the last round's counts sit in the tail, not yet folded
     FLConfig c_;
@@ -1019,7 +1088,7 @@ class FLEngine {
     long long graph_evals_ = 0;    // evaluation kernels inside the captured graph
     std::vector<FLLaunchRec>* rec_ = nullptr;  // TrialBatch: record launches instead of issuing them
     // trace(): an event after every launch, tagged with what was launched
-    enum { TR_PACK, TR_TRAIN, TR_ADAM, TR_EVAL, TR_ALLREDUCE, TR_EVAL_FEDAVG, TR_DP, TR_N };
+    enum { TR_PACK, TR_TRAIN, TR_ADAM, TR_EVAL, TR_ALLREDUCE, TR_EVAL_FEDAVG, TR_DP, TR_SERVER, TR_N };
     std::vector<std::pair<int, hipEvent_t>>* tev_ = nullptr;
     // trace markers without the system-scope release/acquire (device-side timing only needs the
     // marker's timestamp); FEDMI_TRACE_SYSFENCE=1 restores default events (A/B)
@@ -1052,6 +1121,7 @@ class TrialBatch {
         for (int k = 0; k < K_; ++k) {
             const FLEngine& e = *engs_[k];
             if (e.peer_ != nullptr) throw std::runtime_error("TrialBatch: engines must not use the peer all-reduce");
+            if (e.server_on_) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
             if (e.dtype_ != a.dtype_ || std::memcmp(&e.d_, &a.d_, sizeof(MLPDesc)) != 0 ||
                 (a.dtype_ == 1 && (std::memcmp(&e.e_, &a.e_, sizeof(MLPDescB)) != 0 ||
                                    std::memcmp(&e.ev_, &a.ev_, sizeof(MLPDescB)) != 0)))
@@ -1304,6 +1374,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def("set_debug", &FLEngine::set_debug)
         .def("invalidate", &FLEngine::invalidate)
         .def("set_dp_seed", &FLEngine::set_dp_seed)
+        .def("packed_global", &FLEngine::packed_global)
         .def("set_early_stop", &FLEngine::set_early_stop)
         .def("reset_pending", &FLEngine::reset_pending)
         .def("attach_peer", &FLEngine::attach_peer, py::keep_alive<1, 2>())

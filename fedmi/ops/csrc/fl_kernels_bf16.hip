@@ -24,6 +24,7 @@
 #include "fl_common.h"
 #include "fl_device.h"
 #include "peer_device.h"
+#include "fl_bf16.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -31,17 +32,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
-
-// fp32 -> bf16 bits, round to nearest even (finite inputs)
-__device__ __forceinline__ uint32_t bf16_bits(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) { return bf16_bits(a) | (bf16_bits(b) << 16); }
-// lo parts of the split-bf16 representation: bf16(x - bf16(x))
-__device__ __forceinline__ uint32_t lo_bits(float x) { return bf16_bits(x - bf16_to_f32((uint16_t)bf16_bits(x))); }
-__device__ __forceinline__ uint32_t pack_lo_bf16x2(float a, float b) { return lo_bits(a) | (lo_bits(b) << 16); }
 
 // two fp32 -> packed bf16 pair (a low, b high), round to nearest even: v_cvt_pk_bf16_f32
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
