@@ -38,6 +38,9 @@ from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, met
 # measured on MI355X (profiles/round_emulate_r4_shards.log), R = 16 wins at 1000 and 2000 rows,
 # R = 32 at 4000 and 8000.
 SMALL_SHARD_ROWS = 2000
+# Local steps per round the native engine takes: a round's launches are planned into a fixed array
+# (fedmi/ops/csrc/fl_round_plan.h FL_PLAN_MAX_LOCAL_STEPS).  The torch engine has no limit.
+MAX_LOCAL_STEPS = 61
 
 
 @dataclass
@@ -49,7 +52,7 @@ class EngineConfig:
     weight_decay: float = 0.0
     step_size: int = 30
     gamma: float = 0.5
-    local_steps: int = 1
+    local_steps: int = 1            # full-batch Adam steps per round (HIP engine: at most MAX_LOCAL_STEPS = 61)
     prox_mu: float = 0.0
     early_stop: bool = True
     patience: int = 10
@@ -703,6 +706,8 @@ class HipRoundEngine(RoundEngineBase):
         ``client_sizes``: every client's shard size (client sampling weighs the sampled clients
         by n_i / their sum); gathered over ``comm`` when needed and not given."""
         from ..ops import native
+        if int(cfg.local_steps) > MAX_LOCAL_STEPS:
+            raise ValueError(f"HipRoundEngine: at most {MAX_LOCAL_STEPS} local steps per round (got {cfg.local_steps})")
         self.m = native()
         if device is None:
             device = comm.device if comm is not None else torch.device("cuda", torch.cuda.current_device())

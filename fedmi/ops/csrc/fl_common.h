@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fl_round_plan.h"  // host-only: launch vocabulary shared with the round planner
+
 #define FL_MAX_LAYERS 4
 #define FL_MAX_CLASSES 16
 #define FL_MAX_WORLD 64
@@ -246,33 +248,7 @@ struct FLBuffers {
                         // saturated (|x| = 65504, slab_store_h's clamp) or not finite
 };
 
-// Evaluation placement of a round (`mode` of the train kernels).
-//   FL_EVAL_CLASSIC : the train kernel folds the previous round's metrics into the state at
-//                     its start; a separate eval kernel scores the post-step model.
-//   FL_EVAL_FUSED   : one client (FedAvg is the identity, so the round's input weights ARE
-//                     the previous round's post-step local model): the train kernel's own
-//                     forward pass yields the previous round's confusion counts (argmax in
-//                     the loss epilogue) and the Adam kernel folds them and decides whether
-//                     this round is live.  No eval kernel.
-//   FL_EVAL_FUSED_SKIP : as FUSED, but the previous round's counts are already in the tail
-//                     (that round ran classic); the train kernel only trains.
-#define FL_EVAL_CLASSIC 0
-#define FL_EVAL_FUSED 1
-#define FL_EVAL_FUSED_SKIP 2
-//   FL_EVAL_LAGGED  : several clients: the train kernel of round r first scores round r-1's
-//                     post-step LOCAL model (a forward pass on the staged local image, before
-//                     the round's own weights replace it in LDS) into the local count buffer;
-//                     the Adam kernel publishes those counts (+ round r-1's loss) in region A
-//                     of round r's exchange, so no round needs a separate evaluation kernel.
-//                     With the Adam-fused exchange region A is exchanged and folded inside
-//                     round r's Adam kernel (in time for early stopping); riding an external
-//                     all-reduce (RCCL) it is folded one round later, by round r+1's Adam
-//                     kernel -- with early stopping round r runs before round r-1's stop is
-//                     known and is then discarded bit-exactly (FLState::late).
-#define FL_EVAL_LAGGED 3
-// Metric regions of an all-reduced comm buffer that a fold consumes (fl_device.h).
-#define FL_FOLD_A 1  // lag region: round next_round - 2
-#define FL_FOLD_B 2  // tail region: round next_round - 1
+// (evaluation placement FL_EVAL_*, fold regions FL_FOLD_*: fl_round_plan.h)
 // LDS confusion-counter region of the train kernels: C*C counters + a "score rows" flag,
 // padded to a multiple of 16 bytes.
 #define FL_CM_FLAG (FL_MAX_CLASSES * FL_MAX_CLASSES)
@@ -285,17 +261,11 @@ struct FLBuffers {
 // trial's configuration, buffers and the pointer bases its launches refer to sit in a device
 // table; a launch names each pointer argument as (base slot, byte offset), the same for every
 // trial of the batch (the recording engine checks that, fl_engine.cpp TrialBatch).
-#define FL_TB_BASES 8
-enum { FL_TB_PBUF0 = 0, FL_TB_PBUF1, FL_TB_ST0, FL_TB_ST1, FL_TB_LOCAL, FL_TB_LAG, FL_TB_PKG, FL_TB_PKL };
+// (slots FL_TB_* and the selector FLSel: fl_round_plan.h)
 struct FLTrialDesc {
     FLConfig c;
     FLBuffers b;
     char* base[FL_TB_BASES];
-};
-struct FLSel {
-    int base;        // FL_TB_* slot, -1 = nullptr
-    int pad;
-    long long off;   // bytes
 };
 __host__ __device__ inline char* fl_sel(const FLTrialDesc& t, FLSel s) {
     return s.base < 0 ? nullptr : t.base[s.base] + s.off;

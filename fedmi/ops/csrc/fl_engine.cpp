@@ -26,6 +26,7 @@
 
 #include "fl_common.h"
 #include "fl_layout.h"
+#include "fl_round_plan.h"
 #include "peer_allreduce.h"
 
 namespace py = pybind11;
@@ -186,16 +187,10 @@ class RcclComm {
 // ---------------------------------------------------------------------------------------
 // Engine
 // ---------------------------------------------------------------------------------------
+// Every launch of a round is planned on the host first (fl_round_plan.h: a pure function of the
+// engine's RoundTraits and its RoundCarry) and then executed from its record: by this engine
+// (execute), or batched over the engines of a trial batch (TrialBatch below).
 class TrialBatch;
-
-// One launch of a round, as recorded for a trial batch (TrialBatch below) instead of issued.
-struct FLLaunchRec {
-    enum Kind { PACK, TRAIN, ADAM, EVAL, FINALIZE };
-    int kind;
-    int i[4];           // TRAIN: ls, stage_local, mode, fold_mask | ADAM: ls, fold, tail_a, fold_mask |
-                        // FINALIZE: mask
-    const void* p[5];   // pointer arguments in launcher order
-};
 
 class FLEngine {
     friend class TrialBatch;
@@ -262,17 +257,32 @@ class FLEngine {
         c_.rtol = cfg["rtol"].cast<double>();
         c_.max_rounds = cfg["max_rounds"].cast<int>();
         c_.metric_mode = cfg["metric_mode"].cast<int>();
-        // Fused evaluation needs the round's input weights to BE the previous round's
-        // post-step local model: one client (FedAvg of one is the identity, agg_scale 1).
-        fused_ = cfg.contains("fused_eval") && cfg["fused_eval"].cast<bool>() && c_.world == 1 &&
-                 c_.agg_scale == 1.0f;
-        // Differential privacy (fl_dp.hip): the round's output is the clipped, noised contribution,
-        // not the local model a fused / lagged round's next train kernel would score and stage, and
-        // a discarded late-fold round would have spent noise: classic rounds only.
+        // ---- round kind (RoundTraits, fl_round_plan.h) ----
+        tr_.dtype = dtype_;
+        tr_.world = c_.world;
+        tr_.local_steps = c_.local_steps;
+        if (c_.local_steps > FL_PLAN_MAX_LOCAL_STEPS)
+            throw std::runtime_error("FLEngine: at most " + std::to_string(FL_PLAN_MAX_LOCAL_STEPS) + " local steps");
+        tr_.es_enabled = c_.es_enabled != 0;
+        tr_.identity = c_.world == 1 && c_.agg_scale == 1.0f;
+        tr_.cm_off = (long long)(c_.tail_off + c_.rank * c_.tail_stride) * (long long)sizeof(float);
         std::memset(&dp_, 0, sizeof(dp_));
         dp_.clip = cfg.contains("dp_clip") ? cfg["dp_clip"].cast<float>() : 0.f;
-        dp_on_ = dp_.clip > 0.f;
-        if (dp_on_) {
+        tr_.dp_on = dp_.clip > 0.f;
+        std::memset(&sv_, 0, sizeof(sv_));
+        sv_.kind = cfg.contains("server_opt") ? cfg["server_opt"].cast<int>() : FL_SERVER_NONE;
+        tr_.server_on = sv_.kind != FL_SERVER_NONE;
+        // The round's output is not the aggregated local model, so rounds are classic:
+        // differential privacy (fl_dp.hip) outputs the clipped, noised contribution, not the local
+        // model a fused / lagged round's next train kernel would score and stage, and a discarded
+        // late-fold round would have spent noise; a server optimizer (fl_server.hip) outputs x + (a
+        // server step), so a fused round would score the wrong model through the global image and a
+        // lagged round's in-Adam exchange would publish an image the step then has to replace.
+        const bool classic_only = tr_.foreign_output();
+        // Fused evaluation needs the round's input weights to BE the previous round's
+        // post-step local model: one client (FedAvg of one is the identity, agg_scale 1).
+        tr_.fused = !classic_only && cfg.contains("fused_eval") && cfg["fused_eval"].cast<bool>() && tr_.identity;
+        if (tr_.dp_on) {
             const unsigned long long seed = cfg["dp_seed"].cast<unsigned long long>();
             dp_.noise = cfg["dp_noise"].cast<bool>() ? 1 : 0;
             dp_.rank = c_.rank;
@@ -283,16 +293,8 @@ class FLEngine {
             dp_.norm_hist = as_ptr<float>(bufs["dp_norm"].cast<uintptr_t>());
             if (dp_.sigma == nullptr || dp_.norm_hist == nullptr)
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
-            fused_ = false;
         }
-        // Server optimizer (fl_server.hip): the round's output is x + (a server step), not the
-        // aggregated local models, so a fused round would score the wrong model through the global
-        // image and a lagged round's in-Adam exchange would publish an image the step then has to
-        // replace: classic rounds only, as with DP.
-        std::memset(&sv_, 0, sizeof(sv_));
-        sv_.kind = cfg.contains("server_opt") ? cfg["server_opt"].cast<int>() : FL_SERVER_NONE;
-        server_on_ = sv_.kind != FL_SERVER_NONE;
-        if (server_on_) {
+        if (tr_.server_on) {
             if (sv_.kind < FL_SERVER_SGD || sv_.kind > FL_SERVER_YOGI)
                 throw std::runtime_error("FLEngine: unknown server optimizer");
             const double b1 = cfg["server_momentum"].cast<double>(), b2 = cfg["server_beta2"].cast<double>();
@@ -307,21 +309,28 @@ class FLEngine {
             sv_.v = sv_.kind == FL_SERVER_SGD ? nullptr : as_ptr<float>(bufs["server_v"].cast<uintptr_t>());
             if (sv_.m == nullptr || (sv_.kind != FL_SERVER_SGD && sv_.v == nullptr))
                 throw std::runtime_error("FLEngine: the server optimizer needs its state buffers");
-            fused_ = false;
         }
-        eval_fedavg_ = !cfg.contains("eval_fedavg") || cfg["eval_fedavg"].cast<bool>();
+        {
+            // The fused evaluation + FedAvg grid (evaluation blocks + all-reduce blocks) must be
+            // resident in one wave, which needs two evaluation workgroups per CU (measured: with one
+            // per CU the extra blocks spill into a second wave and the fused kernel loses to the
+            // separate kernels, tools/round_emulate.py).
+            const size_t lds = dtype_ == 0 ? (size_t)d_.lds_floats * 4 : (size_t)ev_.lds_bytes;
+            tr_.eval_fedavg_fits = (!cfg.contains("eval_fedavg") || cfg["eval_fedavg"].cast<bool>()) &&
+                                   2 * lds <= (size_t)160 * 1024;
+        }
         // Lagged evaluation (fl_common.h FL_EVAL_LAGGED): several clients, early stopping off,
         // bf16 kernels, and room in LDS for the second parameter image.  The comm buffer then
         // carries the lag region A after the tails (the caller sized it: comm_len).
-        const bool lag_req = !dp_on_ && !server_on_ && cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
+        const bool lag_req = !classic_only && cfg.contains("lagged_eval") && cfg["lagged_eval"].cast<bool>();
         if (lag_req) c_.lag_off = d_.Pimg + c_.tail_len;
         comm_len_ = d_.Pimg + c_.tail_len * (lag_req ? 2 : 1);
         const bool emulate = cfg.contains("emulate_clients") && cfg["emulate_clients"].cast<bool>();
-        emulate_ = emulate;
+        tr_.emulate = emulate;
         // (with early stopping the rounds are lagged when the FedAvg runs inside the Adam kernel,
         // which folds the metrics in time, or rides RCCL, folded one round late: see lagged())
         // (the lagged train kernel scores the previous local model in the train layout itself)
-        lag_ok_ = lag_req && dtype_ == 1 && (c_.world > 1 || emulate) && !fused_;
+        tr_.lag_ok = lag_req && dtype_ == 1 && (c_.world > 1 || emulate) && !tr_.fused;
         // several clients + register scoring: the training forward pass is plain bf16 (no round
         // scores from it), in every round kind of the engine alike (lagged, classic, step API).
         // cfg["plain_fwd"] (EngineConfig.plain_fwd): -1 auto, 0 off, 1 on wherever valid;
@@ -329,7 +338,7 @@ class FLEngine {
         {
             const int req = cfg.contains("plain_fwd") ? cfg["plain_fwd"].cast<int>() : -1;
             const char* pf = std::getenv("FEDMI_PLAIN_FWD");
-            const bool valid = dtype_ == 1 && e_.lag_reg && !fused_;
+            const bool valid = dtype_ == 1 && e_.lag_reg && !tr_.fused;
             const bool want = req < 0 ? (c_.world > 1 || emulate) : req > 0;
             c_.plain_fwd = (valid && want && !(pf != nullptr && pf[0] == '0')) ? 1 : 0;
         }
@@ -343,7 +352,7 @@ class FLEngine {
                 cus = 0;
             const char* ss = std::getenv("FEDMI_SPLIT_SCORE");
             const bool force_on = ss != nullptr && ss[0] == '1', force_off = ss != nullptr && ss[0] == '0';
-            c_.split_score = (lag_ok_ && dtype_ == 1 && e_.lag_reg && !force_off &&
+            c_.split_score = (tr_.lag_ok && dtype_ == 1 && e_.lag_reg && !force_off &&
                               (force_on || 2 * c_.n_slabs <= cus)) ? 1 : 0;
         }
 
@@ -380,7 +389,7 @@ class FLEngine {
             b_.pk_global = pk_;
             b_.pk_local = pk_ + e_.param_bytes;
         }
-        if (lag_ok_ && c_.es_enabled) {
+        if (tr_.lag_ok && c_.es_enabled) {
             // pre-round [local | m | v | packed local image] for a round a late fold discards
             // (FLBuffers::undo); used only while late_fold() (refresh_undo)
             if ((e_.param_bytes & 3) != 0 || (d_.Pimg & 3) != 0)
@@ -391,6 +400,7 @@ class FLEngine {
             b_.undo_pk_bytes = dtype_ == 1 ? e_.param_bytes : 0;
         }
         refresh_undo();
+        fill_bases();
     }
 
     ~FLEngine() {
@@ -406,52 +416,26 @@ class FLEngine {
     // `close`, the last, which evaluates itself: after it every metric is in the buffers.
     void run(int r0, int n, uintptr_t stream, RcclComm* comm, bool close = true) {
         hipStream_t s = as_stream(stream);
-        for (int r = r0; r < r0 + n; ++r) issue_round(r, s, comm, true, lagged() && !(close && r == r0 + n - 1));
+        for (int r = r0; r < r0 + n; ++r) issue_round(r, s, comm, lagged() && !(close && r == r0 + n - 1));
     }
 
     // Local part of round r (no all-reduce; the caller reduces a shared buffer -- and, on a
     // server-optimizer engine, issues phase 3 once the sum is in this engine's buffer).
-    void run_local(int r, uintptr_t stream) { issue_round(r, as_stream(stream), nullptr, false, false, false); }
+    void run_local(int r, uintptr_t stream) {
+        issue([&](RoundPlan& p) { plan_round(tr_, carry_, p, r, false, false, false, false); }, as_stream(stream),
+              nullptr);
+    }
 
-    // One phase of round r: 0 = local training (all local steps), 1 = local evaluation,
-    // 2 = FedAvg all-reduce (+ the server-optimizer step when the engine aggregates itself),
-    // 3 = the server-optimizer step alone (the caller aggregated the round's buffer).  Used by the
-    // step-by-step reference API
-    // (train_one_epoch / evaluate_local / federated_averaging); always classic rounds.
+    // One phase of round r (plan_phase); used by the step-by-step reference API
+    // (train_one_epoch / evaluate_local / federated_averaging).
     void phase(int r, int which, uintptr_t stream, RcclComm* comm) {
-        hipStream_t s = as_stream(stream);
-        if (which == 0) {
-            flush_pending_eval(r, s);
-            issue_train(r, s, false);
-            prev_lagged_ = false;
-        } else if (which == 1) {
-            issue_eval(r, s);
-            cm_in_tail_ = true;
-        } else if (which == 2) {
-            issue_allreduce(r, s, comm);
-            if (aggregates(comm)) issue_server(r, s);
-        } else if (which == 3) {
-            if (!server_on_) throw std::runtime_error("phase 3: no server optimizer");
-            issue_server(r, s);
-        } else {
-            throw std::runtime_error("phase: 0, 1, 2 or 3");
-        }
+        issue([&](RoundPlan& p) { plan_phase(tr_, carry_, p, r, which, comm != nullptr); }, as_stream(stream), comm);
     }
 
     // Fold every pending metric into the state / history (host synchronisation point); `r`
     // = rounds issued.  A fused last round is evaluated first.
     void finalize(int r, uintptr_t stream) {
-        hipStream_t s = as_stream(stream);
-        flush_pending_eval(r, s);
-        if (prev_lagged_)
-            throw std::runtime_error("finalize: the last round is lagged (its metrics need one more round)");
-        const int mask = (prev_scored_ && !prev_afold_ ? FL_FOLD_A : 0) | FL_FOLD_B;
-        if (rec_ != nullptr)
-            rec_->push_back({FLLaunchRec::FINALIZE, {mask, 0, 0, 0}, {pbuf_[r & 1], st_[r & 1], st_[(r + 1) & 1]}});
-        else
-            HIP_CHECK(fl_launch_finalize(d_, c_, b_, pbuf_[r & 1], st_[r & 1], st_[(r + 1) & 1], s, mask,
-                                         late_fold() ? pbuf_[(r + 1) & 1] : nullptr));
-        cm_in_tail_ = false;
+        issue([&](RoundPlan& p) { plan_finalize(tr_, carry_, p, r); }, as_stream(stream), nullptr);
     }
 
     // Record `n` rounds (n even, starting at an even round) into one hipGraph.  Round
@@ -463,14 +447,14 @@ class FLEngine {
     // of lagged engines) select the instantiated graph again instead of re-capturing it (ADVICE
     // r4).  A graph is a pure function of the engine's configuration and buffers -- every change
     // of those drops the cache (drop_graph) -- except a pending repack of host-written weights
-    // (need_pack_), which is captured into the graph's first round: with one pending the graph is
-    // captured afresh.
+    // (RoundCarry::need_pack), which is captured into the graph's first round: with one pending the
+    // graph is captured afresh.
     void capture(int n, uintptr_t stream, RcclComm* comm) {
         if (n <= 0 || (n & 1)) throw std::runtime_error("capture: n must be a positive even number");
         if (needs_eager_round()) throw std::runtime_error("capture: issue one eager round first");
         for (size_t i = 0; i < graphs_.size(); ++i)
             if (graphs_[i].n == n) {
-                if (!need_pack_ && graphs_[i].comm == comm) {
+                if (!carry_.need_pack && graphs_[i].comm == comm) {
                     select_graph((int)i);
                     return;
                 }
@@ -485,21 +469,16 @@ class FLEngine {
         graph_ = nullptr;
         exec_ = nullptr;
         hipStream_t s = as_stream(stream);
-        const bool pend = pending_cm_, tail = cm_in_tail_, plag = prev_lagged_, pscore = prev_scored_,
-                   pafold = prev_afold_;
+        const RoundCarry carry0 = carry_;
         const long long ev0 = eval_launches_;
         HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         try {
-            for (int r = 0; r < n; ++r) issue_round(r, s, comm, true, lagged());
+            for (int r = 0; r < n; ++r) issue_round(r, s, comm, lagged());
         } catch (...) {
             hipGraph_t g;
             hipStreamEndCapture(s, &g);
             if (g) hipGraphDestroy(g);
-            pending_cm_ = pend;
-            cm_in_tail_ = tail;
-            prev_lagged_ = plag;
-            prev_scored_ = pscore;
-            prev_afold_ = pafold;
+            carry_ = carry0;  // nothing was captured: a pending repack stays pending
             eval_launches_ = ev0;
             throw;
         }
@@ -513,11 +492,9 @@ class FLEngine {
         ++captures_;
         select_graph((int)graphs_.size() - 1);
         eval_launches_ = ev0;
-        pending_cm_ = pend;  // nothing ran yet: replay() applies the rounds' effect
-        cm_in_tail_ = tail;
-        prev_lagged_ = plag;
-        prev_scored_ = pscore;
-        prev_afold_ = pafold;
+        // nothing ran yet: replay() applies the rounds' effect on the metrics; the pack state stays
+        // as the captured rounds left it (a pending repack went into the graph's first round)
+        carry_ = carry_.with_metrics_of(carry0);
     }
 
     void replay(uintptr_t stream) {
@@ -525,11 +502,7 @@ class FLEngine {
         if (needs_eager_round()) throw std::runtime_error("replay: issue one eager round first");
         HIP_CHECK(hipGraphLaunch(exec_, as_stream(stream)));
         eval_launches_ += graph_evals_;
-        pending_cm_ = fused_;
-        cm_in_tail_ = !fused_;
-        prev_lagged_ = lagged();
-        prev_scored_ = lagged();
-        prev_afold_ = lagged() && xchg_;
+        carry_ = carry_.steady(tr_);
     }
 
     int graph_rounds() const { return graph_rounds_; }
@@ -541,44 +514,17 @@ class FLEngine {
     // Host-side round bookkeeping (which metrics the last issued round left pending) as a bit
     // set.  A caller that captures rounds of this engine into its own graph (a trial group)
     // reads it after the capture and restores it after every replay of that graph.
-    int flags() const {
-        return (pending_cm_ ? 1 : 0) | (cm_in_tail_ ? 2 : 0) | (prev_lagged_ ? 4 : 0) | (prev_scored_ ? 8 : 0) |
-               (prev_afold_ ? 16 : 0) | (need_pack_ ? 32 : 0);
-    }
-    void set_flags(int f) {
-        pending_cm_ = f & 1;
-        cm_in_tail_ = f & 2;
-        prev_lagged_ = f & 4;
-        prev_scored_ = f & 8;
-        prev_afold_ = f & 16;
-        need_pack_ = f & 32;
-    }
+    int flags() const { return carry_.bits(); }
+    void set_flags(int f) { carry_ = RoundCarry::from_bits(f); }
 
-    // The captured rounds assume the steady state of their kind: a fused graph must not
-    // start behind a classic round (whose counts already sit in the tail), a classic graph
-    // not behind a fused one (whose counts were never computed).
-    // A lagged graph must start behind a lagged round that scored ITS predecessor: the first
-    // captured round's fold mask (region A of the round before) is fixed at capture, and every
-    // replay after the first starts behind such a round.  (Captured behind a lagged round that
-    // followed a self-evaluating one -- e.g. a warm-up that closed on an odd round count -- every
-    // replay's first round skipped the region-A fold: that round's metrics never reached the
-    // history or the early-stop rule.  The Adam-fused exchange folds in time and was unaffected.)
-    bool needs_eager_round() const {
-        if (lagged()) return !prev_lagged_ || !prev_scored_;
-        return fused_ ? cm_in_tail_ : pending_cm_;
-    }
-    // Lagged rounds: allowed by the layout, and either no early stopping (metrics may be
-    // folded one round late), the Adam-fused exchange (which folds them in time) or an
-    // external all-reduce (RCCL: folded one round late, a round run past a stop is discarded
-    // bit-exactly -- late_fold()).  A peer all-reduce kernel without the in-kernel exchange
-    // (several local steps) keeps classic rounds with early stopping: its send buffer is not the
-    // output buffer a late stop republishes from.
-    bool lagged() const { return lag_ok_ && (!c_.es_enabled || xchg_ || peer_ == nullptr); }
-    bool late_fold() const { return lagged() && c_.es_enabled && !xchg_; }
+    // A graph must start from the steady state of its round kind (fl_round_plan.h).
+    bool needs_eager_round() const { return ::needs_eager_round(tr_, carry_); }
+    bool lagged() const { return tr_.lagged(); }
+    bool late_fold() const { return tr_.late_fold(); }
     // The kernels keep / restore the pre-round state only where a round can be discarded.
     void refresh_undo() { b_.undo = (late_fold() && undo_ != nullptr) ? undo_ : nullptr; }
-    bool adam_exchange() const { return xchg_; }
-    bool fused() const { return fused_; }
+    bool adam_exchange() const { return tr_.xchg; }
+    bool fused() const { return tr_.fused; }
 
     // Early-stop parameters (train_and_evaluate(termination_patience, tolerance), C:122): the
     // kernels take FLConfig by value, so a captured graph is dropped; the caller rewrites the
@@ -594,7 +540,7 @@ class FLEngine {
     // Noise key of a DP engine (resume: the checkpoint's stream continues); a kernel argument, so
     // captured graphs are dropped.
     void set_dp_seed(unsigned long long seed) {
-        if (!dp_on_) throw std::runtime_error("set_dp_seed: differential privacy is off");
+        if (!tr_.dp_on) throw std::runtime_error("set_dp_seed: differential privacy is off");
         dp_.key0 = (uint32_t)seed;
         dp_.key1 = (uint32_t)(seed >> 32);
         drop_graph();
@@ -611,16 +557,10 @@ class FLEngine {
     }
 
     // The host wrote the global weights (set_weights / resume): the next round repacks them.
-    void invalidate() { need_pack_ = true; }
+    void invalidate() { carry_.need_pack = true; }
 
     // The host loaded a complete round state (resume): no metrics are pending.
-    void reset_pending() {
-        pending_cm_ = false;
-        cm_in_tail_ = false;
-        prev_lagged_ = false;
-        prev_scored_ = false;
-        prev_afold_ = false;
-    }
+    void reset_pending() { carry_ = carry_.cleared(); }
 
     // Aggregate with the one-shot xGMI all-reduce (peer_allreduce.hip) instead of RCCL: every
     // round publishes into the peer object's send buffers, and its kernel writes the reduced
@@ -628,17 +568,19 @@ class FLEngine {
     void attach_peer(PeerAllReduce& p) {
         // (world 1 is accepted: a one-rank "all-reduce" emulates the multi-client round on
         // one GPU for measurements, tools/round_emulate.py)
-        if (fused_ || p.world() != c_.world || p.rank() != c_.rank || !p.is_open())
+        if (tr_.fused || p.world() != c_.world || p.rank() != c_.rank || !p.is_open())
             throw std::runtime_error("attach_peer: communicator does not match this engine");
         if (p.n_floats() != comm_len_)
             throw std::runtime_error("attach_peer: buffer length != parameter image + tails");
         drop_graph();
         peer_ = &p;
+        tr_.has_peer = true;
+        fill_bases();
         p.prepare_eval((c_.n_rows + c_.R - 1) / c_.R);
         // lagged rounds reduce inside the Adam kernel when the communicator has a chunk-flag
         // table for every Adam block (+ the tail block); one local step per round
         // (chunks: every Adam block, the tail block and the early lag-region chunk)
-        xchg_ = lag_ok_ && c_.local_steps == 1 && p.n_chunks() >= (d_.P + 63) / 64 + 2;
+        tr_.xchg = tr_.lag_ok && c_.local_steps == 1 && p.n_chunks() >= (d_.P + 63) / 64 + 2;
         refresh_undo();
         std::memset(&pp_, 0, sizeof(pp_));
         if (dtype_ == 1) {
@@ -671,31 +613,21 @@ class FLEngine {
 
     // Launch one kernel of round r on its live state (0 = train, 1 = adam, 2 = eval).
     void launch_one(int r, int which, uintptr_t stream) {
-        no_relaunch_with_dp("launch_one");
-        hipStream_t s = as_stream(stream);
-        float* pg = pbuf_[r & 1];
-        float* cb = comm_buf(r);
-        FLState* so = st_[(r + 1) & 1];
-        if (which == 0) launch_train(pg, so, so, 1, s);
-        else if (which == 1) launch_adam(b_.local, pg, cb, so, 1, s);
-        else if (which == 3 && dtype_ == 1) launch_train(pg, so, so, 0, s, FL_EVAL_LAGGED, b_.cnt, 0);  // advances so
-        else launch_eval(b_.local, cb, so, s);
+        issue([&](RoundPlan& p) { plan_relaunch(p, "launch_one", r, which); }, as_stream(stream), nullptr);
     }
 
     // Per-kernel device time (us, averaged over `iters` back-to-back launches, hipEvents)
     // re-running the kernels of the last issued round `r` on its (live) state.  Training
     // launches use local_step=1 semantics so the round state is not advanced.
     py::dict time_kernels(int r, int iters, uintptr_t stream) {
-        no_relaunch_with_dp("time_kernels");
         hipStream_t s = as_stream(stream);
-        float* pg = pbuf_[r & 1];
-        float* cb = comm_buf(r);
-        FLState* so = st_[(r + 1) & 1];
         hipEvent_t e0, e1;
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
         py::dict out;
-        auto timeit = [&](const char* name, auto&& launch) {
+        auto timeit = [&](const char* name, int which) {
+            // (planned per launch: the first train launch consumes a pending repack)
+            auto launch = [&] { issue([&](RoundPlan& p) { plan_relaunch(p, "time_kernels", r, which); }, s, nullptr); };
             launch();
             HIP_CHECK(hipEventRecord(e0, s));
             for (int i = 0; i < iters; ++i) launch();
@@ -705,10 +637,9 @@ class FLEngine {
             HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
             out[name] = 1e3 * ms / iters;
         };
-        const int ls = 1;
-        timeit("train", [&] { launch_train(pg, so, so, ls, s); });
-        timeit("adam", [&] { launch_adam(b_.local, pg, cb, so, ls, s); });
-        timeit("eval", [&] { launch_eval(b_.local, cb, so, s); });
+        timeit("train", 0);
+        timeit("adam", 1);
+        timeit("eval", 2);
         HIP_CHECK(hipEventDestroy(e0));
         HIP_CHECK(hipEventDestroy(e1));
         return out;
@@ -724,7 +655,6 @@ class FLEngine {
     // `warm` untraced rounds run first behind the gate (they absorb the ranks' start skew: the
     // first in-kernel exchange waits for the last rank to arrive).
     py::dict trace(int r0, int n, uintptr_t stream, RcclComm* comm, bool close, double gate_us, int warm) {
-        if (rec_ != nullptr) throw std::runtime_error("trace: not inside a trial batch");
         if (n < 1 || warm < 0) throw std::runtime_error("trace: n >= 1, warm >= 0");
         hipStream_t s = as_stream(stream);
         std::vector<std::pair<int, hipEvent_t>> ev;
@@ -742,8 +672,9 @@ class FLEngine {
         }
         tev_ = nullptr;
         HIP_CHECK(hipStreamSynchronize(s));
+        constexpr int TR_N = FLLaunchRec::N_KINDS;  // events are tagged with the launch kind
         static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
-                                          "server"};
+                                          "server", "finalize"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -798,7 +729,7 @@ class FLEngine {
         o["lag_reg"] = dtype_ == 1 && e_.lag_reg != 0;  // lagged rounds score in registers (fl_layout.h)
         o["plain_fwd"] = c_.plain_fwd != 0;              // plain-bf16 training forward (several clients)
         o["split_score"] = c_.split_score != 0;          // lagged scoring on workgroups of its own
-        o["eval_fedavg"] = peer_ != nullptr && !fused_ && eval_fedavg_fits();
+        o["eval_fedavg"] = peer_ != nullptr && !tr_.fused && tr_.eval_fedavg_fits;
         o["dtype"] = dtype_;
         o["slab_stride"] = c_.slab_stride;
         o["n_slabs"] = c_.n_slabs;
@@ -808,7 +739,7 @@ class FLEngine {
         o["tail_len"] = c_.tail_len;
         o["comm_len"] = comm_len_;
         o["lagged_eval"] = lagged();
-        o["dp"] = dp_on_;                                // clipped (+ noised) contributions, classic rounds
+        o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
         static const char* server_names[] = {"none", "sgd", "adagrad", "adam", "yogi"};
         o["server_opt"] = std::string(server_names[sv_.kind]);  // server step after every aggregation, classic rounds
         o["state_bytes"] = (int)sizeof(FLState);
@@ -816,209 +747,103 @@ class FLEngine {
     }
 
   private:
-    // Re-running a round's Adam kernel alone republishes the un-noised w * local into the comm buffer.
-    // ... and on a server-optimizer engine it overwrites the new global image with w * local.
-    void no_relaunch_with_dp(const char* what) const {
-        if (dp_on_) throw std::runtime_error(std::string(what) + ": not on a DP engine (use trace)");
-        if (server_on_)
+    // Plan with `plan`, then execute the records in order.  A planning error leaves the carry as
+    // it was and nothing issued.
+    template <class F>
+    void issue(F&& plan, hipStream_t s, RcclComm* comm) {
+        RoundPlan p;
+        const RoundCarry carry0 = carry_;
+        try {
+            plan(p);
+        } catch (...) {
+            carry_ = carry0;
+            throw;
+        }
+        for (const FLLaunchRec& m : p) execute(m, s, comm);
+    }
+    void issue_round(int r, hipStream_t s, RcclComm* comm, bool lag) {
+        issue([&](RoundPlan& p) { plan_round(tr_, carry_, p, r, true, lag, true, comm != nullptr); }, s, comm);
+    }
+    // Records that re-run one kernel of round r on its live state (0 = train, 1 = Adam, both as a
+    // later local step; 2 = eval; 3 = bf16: the lagged first train step, which advances the state).
+    // Not where the round's output is not the aggregated local model: the Adam kernel alone would
+    // republish w * local over the noised contribution / the server step's image.
+    void plan_relaunch(RoundPlan& p, const char* what, int r, int which) {
+        if (tr_.dp_on) throw std::runtime_error(std::string(what) + ": not on a DP engine (use trace)");
+        if (tr_.server_on)
             throw std::runtime_error(std::string(what) + ": not on a server-optimizer engine (use trace)");
+        const int par = (r + 1) & 1;
+        const FLSel pg = fl_at(FL_TB_PBUF0 + (r & 1)), so = fl_at(FL_TB_ST0 + par);
+        if (which == 0) plan_train_launch(tr_, carry_, p, par, pg, so, so, 1);
+        else if (which == 1)
+            p.push(FLLaunchRec::ADAM, 1, 0, 0, FL_FOLD_B, par, fl_at(FL_TB_LOCAL), pg, plan_comm_buf(tr_, par), so);
+        else if (which == 3 && dtype_ == 1)
+            plan_train_launch(tr_, carry_, p, par, pg, so, so, 0, FL_EVAL_LAGGED, fl_at(FL_TB_LAG), 0);
+        else plan_eval(tr_, p, r);
     }
-    // The engine produces round outputs itself: one client, its peer all-reduce, or RCCL.
-    bool aggregates(const RcclComm* comm) const { return c_.world < 2 || peer_ != nullptr || comm != nullptr; }
-    // Server-optimizer step of round r (fl_server.hip) on the aggregated image in pbuf_[(r+1)&1];
-    // st_[(r+1)&1] holds the round's live flag and index.  bf16: also the packed image of the result.
-    void issue_server(int r, hipStream_t s) {
-        if (!server_on_) return;
-        if (rec_ != nullptr) throw std::runtime_error("trial batch: no server optimizer");
-        HIP_CHECK(fl_launch_server(d_, sv_, pbuf_[r & 1], pbuf_[(r + 1) & 1], st_[(r + 1) & 1],
-                                   dtype_ == 1 ? &e_ : nullptr, dtype_ == 1 ? b_.pk_global : nullptr, s));
-        mark(TR_SERVER, s);
-        srv_packed_ = dtype_ == 1;
+
+    // FL_TB_* slot -> pointer: the trial table's eight bases, then the peer's two send buffers
+    void fill_bases() {
+        char* const bases[FL_TB_COMM1 + 1] = {
+            (char*)pbuf_[0], (char*)pbuf_[1], (char*)st_[0], (char*)st_[1], (char*)b_.local, (char*)lagbuf_,
+            b_.pk_global, b_.pk_local, peer_ != nullptr ? (char*)peer_->send(0) : nullptr,
+            peer_ != nullptr ? (char*)peer_->send(1) : nullptr};
+        std::memcpy(base_, bases, sizeof(base_));
     }
-    void launch_train(const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
-                      int mode = FL_EVAL_CLASSIC, float* cm_out = nullptr, int fold_mask = FL_FOLD_B) {
-        if (dtype_ == 0) {
-            if (rec_ != nullptr)
-                rec_->push_back({FLLaunchRec::TRAIN, {ls, 0, mode, fold_mask}, {pg, si, so, cm_out}});
-            else
-                HIP_CHECK(fl_launch_train(d_, c_, b_, pg, si, so, ls, s, mode, cm_out, fold_mask));
-            mark(TR_TRAIN, s);
-            // (the fp32 kernels read the fp32 image directly: nothing to repack, but the flag
-            // also tells issue_train that the host replaced the weights -- consumed here, or
-            // every fused round would flush a separate evaluation)
-            need_pack_ = false;
-        } else {
-            // the round's input weights -> packed bf16 image.  With one client the FedAvg
-            // output IS the local model (agg_scale = 1), which the Adam kernel already packed,
-            // so the pack is needed only after host-side weight changes; later local steps
-            // stage the Adam-packed local image too.
-            // (with DP the round's output is not the local model: always pack it from the fp32 image)
-            // (nor with a server optimizer, whose step packs the new global image itself: then neither
-            // the peer all-reduce's pack epilogue nor the Adam-packed local image is the round's input)
-            const bool solo = c_.world == 1 && c_.agg_scale == 1.0f && !need_pack_ && !dp_on_ && !server_on_;
-            // the peer all-reduce already wrote the packed image of its output
-            const bool packed = server_on_ ? (srv_packed_ && !need_pack_) : (solo || (peer_ != nullptr && !need_pack_));
-            if (ls == 0) srv_packed_ = false;  // a later step without a server launch in between repacks
-            if (rec_ != nullptr) {
-                if (ls == 0 && !packed) rec_->push_back({FLLaunchRec::PACK, {0, 0, 0, 0}, {pg, b_.pk_global}});
-                rec_->push_back({FLLaunchRec::TRAIN, {ls, solo ? 1 : 0, mode, fold_mask}, {pg, si, so, cm_out}});
-                need_pack_ = false;
-                return;
+    // Issue one planned launch on `s` (`comm`: the RCCL communicator of an ALLREDUCE without a peer).
+    void execute(const FLLaunchRec& m, hipStream_t s, RcclComm* comm = nullptr) {
+        auto F = [&](int k) { return m.p[k].base < 0 ? nullptr : (float*)(base_[m.p[k].base] + m.p[k].off); };
+        auto S = [&](int k) { return (FLState*)F(k); };
+        const MLPDescB* eb = dtype_ == 1 ? &e_ : nullptr;
+        const int* i = m.i;
+        switch (m.kind) {
+            case FLLaunchRec::PACK:
+                HIP_CHECK(fl_launch_pack_bf16(d_, e_, F(0), (char*)F(1), s));
+                break;
+            case FLLaunchRec::TRAIN:
+                if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3]));
+                else
+                    HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
+                                                   i[3]));
+                break;
+            case FLLaunchRec::ADAM: {
+                PeerArgs pa;
+                if (m.peer) pa = peer_->args(m.par, pbuf_[m.par]);
+                HIP_CHECK(fl_launch_adam(d_, c_, b_, F(0), F(1), F(2), S(3), i[0], s, eb, S(4), i[1], i[2], i[3],
+                                         m.peer ? &pa : nullptr, (m.peer >> 1) & 1, (m.peer >> 2) & 1));
+                break;
             }
-            if (ls == 0 && !packed) {
-                HIP_CHECK(fl_launch_pack_bf16(d_, e_, pg, b_.pk_global, s));
-                mark(TR_PACK, s);
+            case FLLaunchRec::EVAL:
+                ++eval_launches_;
+                if (dtype_ == 0) HIP_CHECK(fl_launch_eval(d_, c_, b_, F(0), F(1), S(2), s));
+                else HIP_CHECK(fl_launch_eval_bf16(d_, ev_, c_, b_, F(0), F(1), S(2), s));
+                break;
+            case FLLaunchRec::ALLREDUCE:
+                if (peer_ != nullptr) HIP_CHECK(peer_->launch(m.par, pbuf_[m.par], dtype_ == 1 ? &pp_ : nullptr, s));
+                else comm->allreduce_f32((uintptr_t)pbuf_[m.par], (size_t)comm_len_, (uintptr_t)s);
+                break;
+            case FLLaunchRec::EVAL_FEDAVG: {
+                const PeerArgs a = peer_->args(m.par, pbuf_[m.par], d_.Pimg);
+                PeerPack pk;
+                std::memset(&pk, 0, sizeof(pk));
+                if (dtype_ == 1) pk = pp_;
+                if (dtype_ == 0) HIP_CHECK(fl_launch_eval_fedavg(d_, c_, b_, F(0), F(1), S(2), a, pk, s));
+                else HIP_CHECK(fl_launch_eval_fedavg_bf16(d_, ev_, c_, b_, F(0), F(1), S(2), a, pk, s));
+                break;
             }
-            need_pack_ = false;
-            HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, pg, si, so, ls, s, solo, mode, cm_out, fold_mask));
-            mark(TR_TRAIN, s);
+            case FLLaunchRec::DP:
+                HIP_CHECK(fl_launch_dp(d_, dp_, F(0), F(1), F(2), S(3), b_.rtab, s));
+                break;
+            case FLLaunchRec::SERVER:
+                HIP_CHECK(fl_launch_server(d_, sv_, F(0), F(1), S(2), eb, dtype_ == 1 ? b_.pk_global : nullptr, s));
+                break;
+            case FLLaunchRec::FINALIZE:
+                HIP_CHECK(fl_launch_finalize(d_, c_, b_, F(0), S(1), S(2), s, i[0],
+                                             late_fold() ? pbuf_[m.par] : nullptr));
+                break;
+            default: throw std::runtime_error("FLEngine: unknown launch");
         }
-    }
-    void launch_adam(const float* pin, const float* anchor, float* comm, const FLState* st, int ls,
-                     hipStream_t s, FLState* st_out = nullptr, int fold = 0, int tail_a = 0,
-                     int fold_mask = FL_FOLD_B, const PeerArgs* peer = nullptr, int wx = 0, int afold = 0) {
-        if (rec_ != nullptr) {
-            if (peer != nullptr || wx || afold) throw std::runtime_error("trial batch: no in-kernel exchange");
-            rec_->push_back({FLLaunchRec::ADAM, {ls, fold, tail_a, fold_mask}, {pin, anchor, comm, st, st_out}});
-            return;
-        }
-        HIP_CHECK(fl_launch_adam(d_, c_, b_, pin, anchor, comm, st, ls, s, dtype_ == 1 ? &e_ : nullptr, st_out,
-                                 fold, tail_a, fold_mask, peer, wx, afold));
-        mark(TR_ADAM, s);
-    }
-    void launch_eval(const float* params, float* comm, const FLState* st, hipStream_t s) {
-        ++eval_launches_;
-        if (rec_ != nullptr) {
-            rec_->push_back({FLLaunchRec::EVAL, {0, 0, 0, 0}, {params, comm, st}});
-            return;
-        }
-        if (dtype_ == 0) HIP_CHECK(fl_launch_eval(d_, c_, b_, params, comm, st, s));
-        else HIP_CHECK(fl_launch_eval_bf16(d_, ev_, c_, b_, params, comm, st, s));
-        mark(TR_EVAL, s);
-    }
-    // Train/Adam pairs of round r.  Fused rounds (fl_common.h FL_EVAL_FUSED): the first train
-    // kernel also scores the previous round's model from its own forward pass, and the first
-    // Adam kernel folds those counts and makes the round's live / stop decision.
-    // Lagged rounds (FL_EVAL_LAGGED): the train kernel scores the previous round's local model
-    // iff that round had no evaluation of its own; its fold consumes region A when the previous
-    // round scored ITS predecessor and region B when the previous round was evaluated.
-    // `xchg`: this round's FedAvg runs inside its Adam kernel (peer_device.h chunk exchange).
-    void issue_train(int r, hipStream_t s, bool fused, bool xchg = false) {
-        float* pg = pbuf_[r & 1];
-        float* cb = comm_buf(r);
-        FLState* si = st_[r & 1];
-        FLState* so = st_[(r + 1) & 1];
-        if (fused && need_pack_) flush_pending_eval(r, s);  // host replaced the weights: score the old model
-        // Every round's metric fold runs in its first Adam kernel (overlapped with the slab
-        // loads; measured: folding at the start of the train kernel cost ~3 us per round), the
-        // train kernel trains on the tentative live decision.
-        const bool score = !fused && prev_lagged_;
-        int mode = (fused && !cm_in_tail_) ? FL_EVAL_FUSED : FL_EVAL_FUSED_SKIP;
-        if (score) mode = FL_EVAL_LAGGED;
-        // metrics of the previous round: region B of its all-reduce (it evaluated itself), or
-        // region A one round later (lagged, FedAvg outside Adam); with the Adam-fused exchange
-        // a lagged predecessor is folded inside this Adam kernel from the exchanged region A
-        const bool afold = score && xchg_;  // fold the lagged predecessor in this Adam kernel
-        const int mask = fused ? FL_FOLD_B
-                               : ((prev_scored_ && !prev_afold_ ? FL_FOLD_A : 0) | (prev_lagged_ ? 0 : FL_FOLD_B));
-        float* cm_out = score ? b_.cnt : pg + c_.tail_off + c_.rank * c_.tail_stride;
-        for (int ls = 0; ls < c_.local_steps; ++ls) {
-            const bool first = ls == 0;
-            launch_train(pg, first ? si : so, so, ls, s, first ? mode : FL_EVAL_CLASSIC, cm_out, mask);
-            if (first && (xchg || afold)) {
-                const PeerArgs pa = peer_->args((r + 1) & 1, pbuf_[(r + 1) & 1]);
-                launch_adam(pg, pg, cb, si, ls, s, so, 1, score ? 1 : 0, mask, &pa, xchg ? 1 : 0, afold ? 1 : 0);
-            } else if (first) {
-                launch_adam(pg, pg, cb, si, ls, s, so, 1, score ? 1 : 0, mask);
-            }
-            else launch_adam(b_.local, pg, cb, so, ls, s);
-        }
-        if (dp_on_) {
-            // clip + noise of the contribution the last Adam kernel stored (fl_dp.hip); `so` holds
-            // the round's live flag and index
-            if (rec_ != nullptr) throw std::runtime_error("trial batch: no DP");
-            HIP_CHECK(fl_launch_dp(d_, dp_, b_.local, pg, cb, so, b_.rtab, s));
-            mark(TR_DP, s);
-        }
-        pending_cm_ = fused;
-        cm_in_tail_ = false;
-        prev_scored_ = score;
-        prev_afold_ = afold;
-    }
-    void issue_eval(int r, hipStream_t s) {
-        launch_eval(b_.local, comm_buf(r), st_[(r + 1) & 1], s);
-    }
-    // A fused round r-1 left its metrics pending (they are normally scored by round r's
-    // train kernel): score them with the eval kernel before anything that needs them.
-    void flush_pending_eval(int r, hipStream_t s) {
-        if (!pending_cm_) return;
-        issue_eval(r - 1, s);
-        pending_cm_ = false;
-        cm_in_tail_ = true;
-    }
-    // Buffer round r publishes into (FedAvg contribution + metric tails): the peer
-    // all-reduce's send buffer, or, for RCCL, the parameter buffer it reduces in place.
-    float* comm_buf(int r) const { return peer_ != nullptr ? peer_->send((r + 1) & 1) : pbuf_[(r + 1) & 1]; }
-    void issue_allreduce(int r, hipStream_t s, RcclComm* comm) {
-        // (one client: FedAvg is the identity; an emulating engine still issues the collective,
-        // e.g. a one-rank RCCL all-reduce, so the multi-client round shape runs on one GPU)
-        if (c_.world < 2 && peer_ == nullptr && !(emulate_ && comm != nullptr)) return;
-        if (peer_ != nullptr)
-            HIP_CHECK(peer_->launch((r + 1) & 1, pbuf_[(r + 1) & 1], dtype_ == 1 ? &pp_ : nullptr, s));
-        else if (comm != nullptr)
-            comm->allreduce_f32((uintptr_t)pbuf_[(r + 1) & 1], (size_t)comm_len_, (uintptr_t)s);
-        else
-            return;
-        mark(TR_ALLREDUCE, s);
-    }
-    // `lag`: a lagged round -- no evaluation; the next round's train kernel scores it.
-    // `server`: the round ends with the server-optimizer step (not when the caller aggregates).
-    void issue_round(int r, hipStream_t s, RcclComm* comm, bool allow_fused, bool lag = false, bool server = true) {
-        server = server && server_on_ && aggregates(comm);
-        const bool fused = fused_ && allow_fused;
-        lag = lag && lagged() && !fused;
-        if (!fused) flush_pending_eval(r, s);
-        const bool xchg = lag && xchg_;
-        issue_train(r, s, fused, xchg);
-        prev_lagged_ = lag;
-        if (lag) {
-            if (!xchg) issue_allreduce(r, s, comm);
-            return;
-        }
-        if (!fused && peer_ != nullptr && eval_fedavg_fits()) {
-            // evaluation and the one-shot all-reduce in one kernel (peer_device.h)
-            issue_eval_fedavg(r, s);
-            cm_in_tail_ = true;
-            if (server) issue_server(r, s);
-            return;
-        }
-        if (!fused) {
-            issue_eval(r, s);
-            cm_in_tail_ = true;
-        }
-        issue_allreduce(r, s, comm);
-        if (server) issue_server(r, s);
-    }
-    // The fused evaluation + FedAvg grid (evaluation blocks + all-reduce blocks) must be
-    // resident in one wave, which needs two evaluation workgroups per CU (measured: with one
-    // per CU the extra blocks spill into a second wave and the fused kernel loses to the
-    // separate kernels, tools/round_emulate.py).
-    bool eval_fedavg_fits() const {
-        const size_t lds = dtype_ == 0 ? (size_t)d_.lds_floats * 4 : (size_t)ev_.lds_bytes;
-        return eval_fedavg_ && 2 * lds <= (size_t)160 * 1024;
-    }
-    void issue_eval_fedavg(int r, hipStream_t s) {
-        if (rec_ != nullptr) throw std::runtime_error("trial batch: no peer all-reduce");
-        const int p = (r + 1) & 1;
-        const PeerArgs a = peer_->args(p, pbuf_[p], d_.Pimg);
-        PeerPack pk;
-        std::memset(&pk, 0, sizeof(pk));
-        if (dtype_ == 1) pk = pp_;
-        if (dtype_ == 0)
-            HIP_CHECK(fl_launch_eval_fedavg(d_, c_, b_, b_.local, comm_buf(r), st_[(r + 1) & 1], a, pk, s));
-        else
-            HIP_CHECK(fl_launch_eval_fedavg_bf16(d_, ev_, c_, b_, b_.local, comm_buf(r), st_[(r + 1) & 1], a, pk, s));
-        mark(TR_EVAL_FEDAVG, s);
+        mark(m.kind, s);
     }
 
     struct GraphRec {
@@ -1058,37 +883,24 @@ class FLEngine {
     char* pk_ = nullptr;
     float* lagbuf_ = nullptr;  // FL_EVAL_LAGGED count + loss carry-over
     long long comm_len_ = 0;   // floats of a comm buffer: image + tails (+ lag region)
-    bool lag_ok_ = false;      // lagged rounds possible (layout, clients, bf16): see lagged()
-    bool emulate_ = false;     // one process stands in for a multi-client round (measurements, tests)
-    bool xchg_ = false;        // lagged rounds: FedAvg inside the Adam kernel (no all-reduce kernel)
-    bool prev_lagged_ = false; // the last issued round had no evaluation of its own
-    bool prev_scored_ = false; // the last issued round's train kernel scored its predecessor
-    bool prev_afold_ = false;  // ... and its Adam kernel folded that predecessor (exchanged in-kernel)
-    bool need_pack_ = true;  // host changed the global weights: repack before the next round
+    RoundTraits tr_;           // round kind: fixed after construction / attach_peer
+    RoundCarry carry_;         // what the last issued round left pending
     PeerAllReduce* peer_ = nullptr;  // one-shot xGMI all-reduce (nullptr: RCCL)
     float* undo_ = nullptr;          // FLBuffers::undo storage (lagged engines with early stopping)
     PeerPack pp_;                    // its bf16 pack epilogue (bf16 mode)
-    bool eval_fedavg_ = true;  // world > 1 with peer: evaluation + all-reduce in one kernel
-    bool fused_ = false;       // rounds evaluate the previous round inside the train kernel
-    bool dp_on_ = false;       // differential privacy: fl_dp_kernel after every round's last Adam kernel
-    FLDp dp_;
-    bool server_on_ = false;   // server optimizer: fl_server_kernel after every round's aggregation
-    bool srv_packed_ = false;  // bf16: pk_global holds the last server step's output (nothing ran since)
-    FLServer sv_;
-    bool pending_cm_ = false;  // the last issued round was fused: its metrics are not scored yet
-    bool cm_in_tail_ = false;  // the last round's counts sit in the tail, not yet folded
+    FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
+    FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLConfig c_;
     FLBuffers b_;
     float* pbuf_[2];
     FLState* st_[2];
+    char* base_[FL_TB_COMM1 + 1];  // FL_TB_* slot -> pointer (fill_bases)
     hipGraph_t graph_ = nullptr;
     hipGraphExec_t exec_ = nullptr;
     int graph_rounds_ = 0;
     long long eval_launches_ = 0;  // see eval_launches()
     long long graph_evals_ = 0;    // evaluation kernels inside the captured graph
-    std::vector<FLLaunchRec>* rec_ = nullptr;  // TrialBatch: record launches instead of issuing them
-    // trace(): an event after every launch, tagged with what was launched
-    enum { TR_PACK, TR_TRAIN, TR_ADAM, TR_EVAL, TR_ALLREDUCE, TR_EVAL_FEDAVG, TR_DP, TR_SERVER, TR_N };
+    // trace(): an event after every launch, tagged with the launch kind
     std::vector<std::pair<int, hipEvent_t>>* tev_ = nullptr;
     // trace markers without the system-scope release/acquire (device-side timing only needs the
     // marker's timestamp); FEDMI_TRACE_SYSFENCE=1 restores default events (A/B)
@@ -1121,7 +933,7 @@ class TrialBatch {
         for (int k = 0; k < K_; ++k) {
             const FLEngine& e = *engs_[k];
             if (e.peer_ != nullptr) throw std::runtime_error("TrialBatch: engines must not use the peer all-reduce");
-            if (e.server_on_) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
+            if (e.tr_.server_on) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
             if (e.dtype_ != a.dtype_ || std::memcmp(&e.d_, &a.d_, sizeof(MLPDesc)) != 0 ||
                 (a.dtype_ == 1 && (std::memcmp(&e.e_, &a.e_, sizeof(MLPDescB)) != 0 ||
                                    std::memcmp(&e.ev_, &a.ev_, sizeof(MLPDescB)) != 0)))
@@ -1129,12 +941,14 @@ class TrialBatch {
             if (e.c_.R != a.c_.R || e.c_.n_rows != a.c_.n_rows || e.c_.world != a.c_.world ||
                 e.c_.plain_fwd != a.c_.plain_fwd ||
                 e.c_.rank != a.c_.rank || e.c_.slab_f16 != a.c_.slab_f16 || e.c_.lag_off != a.c_.lag_off ||
-                e.fused_ != a.fused_ || e.lagged() != a.lagged() || e.emulate_ != a.emulate_)
+                e.tr_.fused != a.tr_.fused || e.lagged() != a.lagged() || e.tr_.emulate != a.tr_.emulate)
                 throw std::runtime_error("TrialBatch: engines differ in rows, clients or round kind");
             if (k > 0 && e.c_.local_steps > engs_[k - 1]->c_.local_steps)
                 throw std::runtime_error("TrialBatch: order the engines by local steps, descending");
         }
         HIP_CHECK(hipMalloc(&dT_, sizeof(FLTrialDesc) * K_));
+        plans_.resize(K_);
+        carry0_.resize(K_);
         upload(nullptr);
     }
     ~TrialBatch() {
@@ -1146,15 +960,18 @@ class TrialBatch {
     void run(int r0, int n, uintptr_t stream, bool close) {
         for (int r = r0; r < r0 + n; ++r) {
             const bool last = close && r == r0 + n - 1;
-            issue([&](FLEngine* e) { e->run(r, 1, stream, nullptr, last); }, as_stream(stream));
+            issue([&](FLEngine& e, RoundPlan& p) {
+                plan_round(e.tr_, e.carry_, p, r, true, e.lagged() && !last, true, false);
+            }, as_stream(stream));
         }
     }
     // Local part of round r of every trial (the caller reduces the trials' shared buffer).
     void run_local(int r, uintptr_t stream) {
-        issue([&](FLEngine* e) { e->run_local(r, stream); }, as_stream(stream));
+        issue([&](FLEngine& e, RoundPlan& p) { plan_round(e.tr_, e.carry_, p, r, false, false, false, false); },
+              as_stream(stream));
     }
     void finalize(int r, uintptr_t stream) {
-        issue([&](FLEngine* e) { e->finalize(r, stream); }, as_stream(stream));
+        issue([&](FLEngine& e, RoundPlan& p) { plan_finalize(e.tr_, e.carry_, p, r); }, as_stream(stream));
     }
     bool needs_eager_round() const {
         for (auto* e : engs_)
@@ -1169,9 +986,7 @@ class TrialBatch {
             const FLEngine& e = *engs_[k];
             T[k].c = e.c_;
             T[k].b = e.b_;
-            char* const bases[FL_TB_BASES] = {(char*)e.pbuf_[0], (char*)e.pbuf_[1], (char*)e.st_[0], (char*)e.st_[1],
-                                              (char*)e.b_.local, (char*)e.lagbuf_, e.b_.pk_global, e.b_.pk_local};
-            std::memcpy(T[k].base, bases, sizeof(bases));
+            std::memcpy(T[k].base, e.base_, sizeof(T[k].base));
         }
     }
     // (re)upload the table when an engine's configuration changed (e.g. set_early_stop);
@@ -1190,90 +1005,52 @@ class TrialBatch {
         HIP_CHECK(hipMemcpy(dT_, T.data(), sizeof(FLTrialDesc) * K_, hipMemcpyHostToDevice));
         host_ = std::move(T);
     }
-    size_t base_bytes(const FLEngine& e, int i) const {
-        switch (i) {
-            case FL_TB_PBUF0: case FL_TB_PBUF1: return (size_t)e.comm_len_ * sizeof(float);
-            case FL_TB_ST0: case FL_TB_ST1: return sizeof(FLState);
-            case FL_TB_LOCAL: return (size_t)e.d_.Pimg * sizeof(float);
-            case FL_TB_LAG: return (FL_MAX_CLASSES * FL_MAX_CLASSES + 4) * sizeof(float);
-            default: return e.dtype_ == 1 ? (size_t)e.e_.param_bytes : 0;
-        }
-    }
-    FLSel resolve(int k, const void* p) const {
-        FLSel sel = {-1, 0, 0};
-        if (p == nullptr) return sel;
-        const char* q = static_cast<const char*>(p);
-        for (int i = 0; i < FL_TB_BASES; ++i) {
-            const char* b0 = host_[k].base[i];
-            if (b0 != nullptr && q >= b0 && q < b0 + base_bytes(*engs_[k], i)) {
-                sel.base = i;
-                sel.off = (long long)(q - b0);
-                return sel;
-            }
-        }
-        throw std::runtime_error("TrialBatch: launch argument outside the trial's buffers");
-    }
-    static bool same_launch(const FLLaunchRec& a, const FLLaunchRec& b) {
-        return a.kind == b.kind && std::memcmp(a.i, b.i, sizeof(a.i)) == 0;
+    // What a batched launch cannot do (the constructor already refuses peer and server engines).
+    static void check_batchable(const FLLaunchRec& m) {
+        if (m.kind == FLLaunchRec::DP) throw std::runtime_error("trial batch: no DP");
+        if (m.kind == FLLaunchRec::SERVER) throw std::runtime_error("trial batch: no server optimizer");
+        if (m.kind == FLLaunchRec::ALLREDUCE || m.kind == FLLaunchRec::EVAL_FEDAVG)
+            throw std::runtime_error("trial batch: no peer all-reduce");
+        if (m.kind == FLLaunchRec::ADAM && m.peer) throw std::runtime_error("trial batch: no in-kernel exchange");
     }
 
-    // Record every engine's launches, match them into batched launches (all checks done before
-    // anything is issued: on a mismatch the engines' round bookkeeping is rolled back and
-    // nothing ran), then issue them.
+    // Plan every engine's launches and match them into batched launches (all checks done before
+    // anything is issued: on a mismatch the engines' carries are rolled back and nothing ran),
+    // then issue them.  cnt_[j]: trials taking part in engine 0's j-th launch, a prefix of the table.
     template <class F>
-    void issue(F&& per_engine, hipStream_t s) {
+    void issue(F&& plan_one, hipStream_t s) {
         upload(s);
-        std::vector<int> flags0(K_);
-        for (int k = 0; k < K_; ++k) flags0[k] = engs_[k]->flags();
-        auto rollback = [&]() {
-            for (int k = 0; k < K_; ++k) {
-                engs_[k]->rec_ = nullptr;
-                engs_[k]->set_flags(flags0[k]);
-            }
-        };
-        struct Planned {
-            const FLLaunchRec* m;
-            FLSel sel[5];
-            int cnt;
-        };
-        std::vector<std::vector<FLLaunchRec>> recs(K_);
-        std::vector<Planned> plan;
+        for (int k = 0; k < K_; ++k) carry0_[k] = engs_[k]->carry_;
+        const RoundPlan& lead = plans_[0];
         try {
             for (int k = 0; k < K_; ++k) {
-                engs_[k]->rec_ = &recs[k];
-                per_engine(engs_[k]);
-                engs_[k]->rec_ = nullptr;
+                plans_[k].n = 0;
+                plan_one(*engs_[k], plans_[k]);
+                for (const FLLaunchRec& m : plans_[k]) {
+                    check_batchable(m);
+                    if (m.kind == FLLaunchRec::EVAL) ++engs_[k]->eval_launches_;
+                }
             }
-            std::vector<size_t> pos(K_, 0);
-            for (const FLLaunchRec& m : recs[0]) {
-                // trials whose next recorded launch is this one: a prefix of the table
-                Planned pl;
-                pl.m = &m;
-                pl.cnt = 0;
+            std::vector<int> pos(K_, 0);
+            for (int j = 0; j < lead.n; ++j) {
+                int cnt = 0;
                 for (int k = 0; k < K_; ++k) {
-                    const bool match = pos[k] < recs[k].size() && same_launch(recs[k][pos[k]], m);
-                    if (match && k != pl.cnt) throw std::runtime_error("TrialBatch: launch sequences do not align");
-                    if (match) ++pl.cnt;
+                    const bool match = pos[k] < plans_[k].n && same_launch(plans_[k].rec[pos[k]], lead.rec[j]);
+                    if (match && k != cnt) throw std::runtime_error("TrialBatch: launch sequences do not align");
+                    if (match && !same_buffers(plans_[k].rec[pos[k]], lead.rec[j]))
+                        throw std::runtime_error("TrialBatch: trials disagree on a launch argument");
+                    if (match) ++cnt;
                 }
-                for (int a = 0; a < 5; ++a) {
-                    pl.sel[a] = resolve(0, m.p[a]);
-                    for (int k = 1; k < pl.cnt; ++k) {
-                        const FLSel o = resolve(k, recs[k][pos[k]].p[a]);
-                        if (o.base != pl.sel[a].base || o.off != pl.sel[a].off)
-                            throw std::runtime_error("TrialBatch: trials disagree on a launch argument");
-                    }
-                }
-                for (int k = 0; k < pl.cnt; ++k) ++pos[k];
-                plan.push_back(pl);
+                for (int k = 0; k < cnt; ++k) ++pos[k];
+                cnt_[j] = cnt;
             }
             for (int k = 0; k < K_; ++k)
-                if (pos[k] != recs[k].size()) throw std::runtime_error("TrialBatch: launch sequences do not align");
+                if (pos[k] != plans_[k].n) throw std::runtime_error("TrialBatch: launch sequences do not align");
         } catch (...) {
-            rollback();
+            for (int k = 0; k < K_; ++k) engs_[k]->carry_ = carry0_[k];
             throw;
         }
-        const FLEngine& e0 = *engs_[0];
-        for (const Planned& pl : plan) launch(e0, *pl.m, pl.sel, pl.cnt, s);
+        for (int j = 0; j < lead.n; ++j) launch(*engs_[0], lead.rec[j], lead.rec[j].p, cnt_[j], s);
     }
     void launch(const FLEngine& e, const FLLaunchRec& m, const FLSel* sel, int cnt, hipStream_t s) {
         const FLConfig& c = e.c_;
@@ -1311,6 +1088,9 @@ class TrialBatch {
     int K_ = 0;
     FLTrialDesc* dT_ = nullptr;
     std::vector<FLTrialDesc> host_;
+    std::vector<RoundPlan> plans_;    // per engine, reused by every issue()
+    std::vector<RoundCarry> carry0_;  // the engines' carries before planning (rollback)
+    int cnt_[FL_PLAN_CAP];
 };
 
 // Thin wrappers used by tests and the synthetic-data path.
