@@ -69,6 +69,11 @@ def parse_args(argv=None):
     ap.add_argument("--server-momentum", type=float, default=0.9, help="server momentum b1")
     ap.add_argument("--server-beta2", type=float, default=0.99, help="server second-moment decay b2 (adam, yogi)")
     ap.add_argument("--server-tau", type=float, default=1e-3, help="server adaptivity tau (adagrad, adam, yogi)")
+    ap.add_argument("--aggregator", choices=["mean", "median", "trimmed_mean"], default="mean",
+                    help="aggregation rule: mean = sample-weighted FedAvg (the reference); median / trimmed_mean = "
+                         "coordinate-wise, unweighted, Byzantine-robust (Yin et al. 2018)")
+    ap.add_argument("--trim-ratio", type=float, default=0.1,
+                    help="--aggregator trimmed_mean: fraction beta cut at EACH end, in [0, 0.5)")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -167,6 +172,10 @@ def _server_fields(a) -> dict:
                 server_beta2=a.server_beta2, server_tau=a.server_tau)
 
 
+def _aggregator_fields(a) -> dict:
+    return dict(aggregator=a.aggregator, trim_ratio=a.trim_ratio)
+
+
 def _print_privacy(a, rounds: int) -> None:
     """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
     if a.dp_clip > 0.0:
@@ -188,7 +197,7 @@ def main_clients(a, comm):
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
-                       **_dp_fields(a), **_server_fields(a))
+                       **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -227,6 +236,13 @@ def main(argv=None):
         server_opt_id(EngineConfig(**_server_fields(a)))
     except ValueError as e:
         raise SystemExit(f"--server-*: {e}")
+    if a.wide and a.aggregator != "mean":
+        raise SystemExit("--aggregator is not supported with --wide")
+    try:
+        from fedmi.fl.engine import aggregator_id
+        aggregator_id(EngineConfig(**_dp_fields(a), **_aggregator_fields(a)))
+    except ValueError as e:
+        raise SystemExit(f"--aggregator / --trim-ratio: {e}")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -246,7 +262,7 @@ def main(argv=None):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, participation=a.participation, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
-                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a))
+                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

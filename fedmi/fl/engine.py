@@ -30,6 +30,7 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
+from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, robust_aggregate_torch
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
 
@@ -132,6 +133,16 @@ class EngineConfig:
     server_momentum: float = 0.9
     server_beta2: float = 0.99
     server_tau: float = 1e-3
+    # Aggregation rule (fedmi/fl/aggregate.py): "mean" = the sample-weighted FedAvg above (nothing of a
+    # round changes); "median" / "trimmed_mean" = the coordinate-wise median / beta-trimmed mean of the
+    # round's sampled clients' UNWEIGHTED local models (Yin et al. 2018), robust against clients that
+    # are alive and wrong (NaN, sign flips, scaling).  trim_ratio = beta, the fraction cut at EACH end
+    # (t = floor(beta K_r) of K_r sampled clients; "trimmed_mean" only).  Metric tails, history and
+    # the early-stop rule are unchanged; a server optimizer steps from the robust aggregate; rounds are
+    # classic.  Not with dp_clip > 0 (the noise calibration assumes a weighted sum), trial batches or
+    # WideClient; at most 64 clients.
+    aggregator: str = "mean"
+    trim_ratio: float = 0.1
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -189,6 +200,23 @@ def server_opt_id(cfg: EngineConfig) -> int:
     if kind >= 2 and not (math.isfinite(tau) and tau > 0.0):
         raise ValueError(f"server_tau must be a finite number > 0 for server_opt={cfg.server_opt!r}, "
                          f"got {cfg.server_tau!r}")
+    return kind
+
+
+def aggregator_id(cfg: EngineConfig) -> int:
+    """Validate the aggregation fields; the rule's index in ``AGGREGATORS`` (0 = the weighted mean)."""
+    if cfg.aggregator not in AGGREGATORS:
+        raise ValueError(f"aggregator must be one of {AGGREGATORS}, got {cfg.aggregator!r}")
+    try:
+        beta = float(cfg.trim_ratio)
+    except (TypeError, ValueError):
+        beta = math.nan
+    if not (math.isfinite(beta) and 0.0 <= beta < 0.5):
+        raise ValueError(f"trim_ratio must be a finite number in [0, 0.5), got {cfg.trim_ratio!r}")
+    kind = AGGREGATORS.index(cfg.aggregator)
+    if kind and float(cfg.dp_clip) > 0.0:
+        raise ValueError(f"aggregator={cfg.aggregator!r} does not combine with differential privacy (dp_clip > 0): "
+                         "the noise calibration assumes a weighted sum")
     return kind
 
 
@@ -257,6 +285,12 @@ class RoundEngineBase:
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
+        # index in AGGREGATORS, 0 = the weighted mean; the aggregate of one client is the identity
+        kind = aggregator_id(cfg)
+        self.robust = kind if self.world > 1 else 0
+        if self.robust and self.world > MAX_ROBUST_CLIENTS:
+            raise ValueError(f"aggregator={cfg.aggregator!r} takes at most {MAX_ROBUST_CLIENTS} clients "
+                             f"(the width of the sampled-client mask), got {self.world}")
         self.n_local = int(len(X))
         if self.n_local == 0:
             raise ValueError("client shard is empty (reference SURVEY Q12 would deadlock)")
@@ -266,7 +300,8 @@ class RoundEngineBase:
         if n_total is None:
             n_total = self._allreduce_scalar(float(self.n_local))
         self.n_total = int(n_total)
-        self.agg_scale = float(self.n_local) / float(self.n_total)
+        # robust aggregators are unweighted: the contribution image IS the local model (x 1.0f is exact)
+        self.agg_scale = 1.0 if self.robust else float(self.n_local) / float(self.n_total)
         self.tail_stride = self.n_classes * self.n_classes + 1
         self.hist = _History(cfg.max_rounds, self.world, dp=self.dp)
         assert init_flat.shape == (self.P,)
@@ -488,6 +523,8 @@ class TorchRoundEngine(RoundEngineBase):
     def fedavg_contribution(self) -> torch.Tensor:
         """This client's operand of the round's SUM all-reduce:
         [w * n_i/N | per-rank (confusion, loss) tails] (+ n_i when sampling clients)."""
+        if self.robust:
+            return self._robust_contribution()
         sampling = float(self.cfg.participation) < 1.0 and self.world > 1
         buf = torch.zeros(self.P + self.world * self.tail_stride + int(sampling), dtype=torch.float32)
         active = getattr(self, "_active", True)
@@ -531,17 +568,43 @@ class TorchRoundEngine(RoundEngineBase):
         xi = float(self.dp_sigma[r]) * dp_normals(self.P, r, self.rank, self.dp_seed)
         return local, torch.as_tensor(xi).to(local.dtype)
 
+    def _robust_contribution(self) -> torch.Tensor:
+        """Robust aggregators: this client's row of the round's gather, [unscaled local model (zeros
+        when not sampled) | per-rank (confusion, loss) tails | 1 when sampled, else 0]."""
+        buf = torch.zeros(self.P + self.world * self.tail_stride + 1, dtype=torch.float32)
+        if getattr(self, "_active", True):
+            buf[:self.P] = self.model.flat.detach().cpu()
+            buf[-1] = 1.0
+        t0 = self.P + self.rank * self.tail_stride
+        buf[t0:t0 + self.n_classes ** 2] = torch.as_tensor(self._cm.reshape(-1), dtype=torch.float32)
+        buf[t0 + self.n_classes ** 2] = self._loss
+        return buf
+
+    def robust_combine(self, bufs: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The clients' :meth:`fedavg_contribution` rows (rank order) -> [robust aggregate of the sampled
+        clients' images | tails summed in rank order], the buffer :meth:`fedavg_apply` adopts."""
+        stack = torch.stack([b[:self.P] for b in bufs])
+        out = bufs[0][:-1].clone()
+        for b in bufs[1:]:
+            out += b[:-1]
+        out[:self.P] = robust_aggregate_torch(stack, [float(b[-1]) != 0.0 for b in bufs], self.cfg.aggregator,
+                                              float(self.cfg.trim_ratio))
+        return out
+
     def step_aggregate(self) -> None:
         # one SUM all-reduce of [w * n_i/N | per-rank (confusion, loss) tails]
         buf = self.fedavg_contribution()
-        if self.comm is not None:
+        if self.robust:
+            # robust aggregators: every client's row is gathered, the rule applied on every rank alike
+            buf = self.robust_combine([torch.as_tensor(b) for b in self.comm.allgather(buf.numpy())])
+        elif self.comm is not None:
             self.comm.allreduce_(buf)
         self.fedavg_apply(buf)
 
     def fedavg_apply(self, buf: torch.Tensor) -> None:
         """Adopt the all-reduced buffer: new global weights, metrics, early-stop rule."""
         r = self.rounds_issued
-        sampling = float(self.cfg.participation) < 1.0 and self.world > 1
+        sampling = float(self.cfg.participation) < 1.0 and self.world > 1 and not self.robust
         if sampling:
             buf[:self.P] /= buf[-1]
             buf = buf[:-1]
@@ -708,6 +771,8 @@ class HipRoundEngine(RoundEngineBase):
         from ..ops import native
         if int(cfg.local_steps) > MAX_LOCAL_STEPS:
             raise ValueError(f"HipRoundEngine: at most {MAX_LOCAL_STEPS} local steps per round (got {cfg.local_steps})")
+        if cfg.aggregator != "mean" and comm_buffers is not None:
+            raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
         self.m = native()
         if device is None:
             device = comm.device if comm is not None else torch.device("cuda", torch.cuda.current_device())
@@ -742,8 +807,10 @@ class HipRoundEngine(RoundEngineBase):
         # which folds each round's metrics in time, or over RCCL, folded one round late with the
         # round run past a stop discarded bit-exactly: FLEngine.late_fold)
         # (differential privacy: classic rounds, see fl_engine.cpp)
+        # (robust aggregators: classic rounds aggregated from Python, see _aggregate)
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
-                     and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server)
+                     and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server
+                     and not self.robust)
         comm_len = self.Pimg + self.world * self.tail_stride * (2 if self._lag else 1)
         if comm_buffers is None:
             self.params = [torch.zeros(comm_len, **f32), torch.zeros(comm_len, **f32)]
@@ -832,6 +899,7 @@ class HipRoundEngine(RoundEngineBase):
                     raise
         self.R = R
         self.layout = self.engine.layout()
+        self.layout["aggregator"] = AGGREGATORS[self.robust]   # the rule that runs (one client: the identity)
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -844,7 +912,10 @@ class HipRoundEngine(RoundEngineBase):
         self._native_comm = None
         # one-shot xGMI all-reduce of [image | tails] (collective set-up; None -> RCCL)
         self._peer = None
-        if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False):
+        # (a robust aggregator gathers over the host plane: neither the peer plane nor RCCL is set
+        # up -- every rank shares the config, so that is collectively consistent)
+        self._robust_tab = None   # device pointer tables of the gather, built on first use
+        if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust:
             from ..parallel.peer import make_peer_allreduce
             torch.cuda.synchronize(dev)
             # lagged rounds reduce inside the Adam kernel: one chunk flag per Adam block + the
@@ -854,7 +925,7 @@ class HipRoundEngine(RoundEngineBase):
             if self._peer is not None:
                 self.engine.attach_peer(self._peer)
         if self.world > 1 and self._peer is None and comm_buffers is None and comm is not None \
-                and hasattr(comm, "rccl"):
+                and hasattr(comm, "rccl") and not self.robust:
             # RCCL only when the peer plane is off or fell back (every rank agreed on that above),
             # so this lazy, bounded bootstrap runs on every rank or on none; if it fails too, every
             # rank continues on the host plane (aggregation 'host') instead of raising
@@ -909,7 +980,9 @@ class HipRoundEngine(RoundEngineBase):
         for r in range(mr):
             part = self.participants(r)
             active = self.rank in part
-            if len(part) == self.world:
+            if self.robust:
+                w = 1.0   # unweighted: the contribution is the local model itself
+            elif len(part) == self.world:
                 w = float(self.n_local) / float(self.n_total)
             else:
                 w = float(self.n_local) / float(sum(int(client_sizes[k]) for k in part))
@@ -941,9 +1014,12 @@ class HipRoundEngine(RoundEngineBase):
 
     @property
     def aggregation(self) -> str:
-        """Data plane of the FedAvg all-reduce: 'none' (one client), 'xgmi-oneshot', 'rccl' or 'host'."""
+        """Data plane of the FedAvg all-reduce: 'none' (one client), 'xgmi-oneshot', 'rccl' or 'host';
+        'host-gather': a robust aggregator over every rank's gathered buffer."""
         if self.world == 1:
             return "none"
+        if self.robust:
+            return "host-gather"
         if self._peer is not None:
             return "xgmi-oneshot+adam" if self.engine.adam_exchange else "xgmi-oneshot"
         return "rccl" if self._native_comm is not None else "host"
@@ -965,8 +1041,29 @@ class HipRoundEngine(RoundEngineBase):
             self.engine.phase(r, 2, self._stream(), self._native_comm)
         else:
             with torch.cuda.stream(self.stream):
-                self.comm.allreduce_(self.params[(r + 1) & 1])
+                self._aggregate(r)
             self.server_step(r)
+
+    def _aggregate(self, r: int) -> None:
+        """Aggregation of round ``r`` from Python, on the current stream, in place in the round's
+        output buffer: the communicator's SUM all-reduce, or (robust aggregators) a gather of every
+        rank's buffer over the host plane and one fl_robust launch over the gathered stack."""
+        buf = self.params[(r + 1) & 1]
+        if not self.robust:
+            self.comm.allreduce_(buf)
+            return
+        if self._robust_tab is None:
+            stack = torch.empty((self.world, buf.numel()), dtype=torch.float32, device=self.device)
+            src = torch.tensor([stack[k].data_ptr() for k in range(self.world)], dtype=torch.int64, device=self.device)
+            dst = [torch.tensor([p.data_ptr()], dtype=torch.int64, device=self.device) for p in self.params]
+            self._robust_tab = (stack, src, dst)
+        stack, src, dst = self._robust_tab
+        self.comm.allgather_device(buf, out=stack)
+        par = (r + 1) & 1
+        self.m.robust_aggregate(self.dims, self.robust, float(self.cfg.trim_ratio), src.data_ptr(), self.world,
+                                dst[par].data_ptr(), 1, self.state[par].data_ptr(), self.rtab.data_ptr(),
+                                self.world * self.tail_stride, int(self.cfg.max_rounds),
+                                torch.cuda.current_stream(self.device).cuda_stream)
 
     def server_step(self, r: int) -> None:
         """Server-optimizer step of round ``r`` on the aggregated image a caller summed into
@@ -1058,7 +1155,7 @@ class HipRoundEngine(RoundEngineBase):
             with torch.cuda.stream(self.stream):
                 for r in range(r0, r0 + n):
                     self.engine.run_local(r, s)
-                    self.comm.allreduce_(self.params[(r + 1) & 1])
+                    self._aggregate(r)
                     self.server_step(r)
             self.rounds_issued += n
             return

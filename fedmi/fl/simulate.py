@@ -16,11 +16,15 @@ client's tail (C:165-192).
 * ``backend='hip'``: k :class:`~fedmi.fl.engine.HipRoundEngine` on one device stream, classic
   rounds (train + Adam + eval kernels per client), the k FedAvg buffers summed on the device.
 * ``backend='torch'``: k :class:`~fedmi.fl.engine.TorchRoundEngine` (CPU oracle).
+
+With a robust aggregator (``EngineConfig.aggregator``) the in-process sum is replaced by the
+coordinate-wise median / trimmed mean of the sampled clients' buffers: one ``fl_robust`` launch,
+in place over the k buffers, on the device; ``robust_aggregate_torch`` on the CPU.
 """
 from __future__ import annotations
 
 import copy
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import numpy as np
 import torch
@@ -48,7 +52,13 @@ class ClientGroup:
     """k clients of one federation in this process."""
 
     def __init__(self, X, y, k: int, cfg: EngineConfig, backend: str = "hip", shard_mode: str = "compat",
-                 seed: int = 0, alpha: float = 0.5, device=None, n_classes: Optional[int] = None):
+                 seed: int = 0, alpha: float = 0.5, device=None, n_classes: Optional[int] = None,
+                 tamper: Optional[Callable[[int, List[torch.Tensor]], None]] = None):
+        """``tamper(r, bufs)``: optional hook for Byzantine-client studies, called every round after the
+        local steps and before the aggregation with the round index and the k clients' contribution
+        buffers in client order (hip: the device FedAvg buffers, on the group's stream, the padded
+        parameter image first; torch: the ``fedavg_contribution`` rows, the dense parameters first);
+        what it writes is what gets aggregated.  ``None`` changes nothing."""
         X = np.asarray(X)
         y = np.asarray(y)
         self.k = int(k)
@@ -81,6 +91,8 @@ class ClientGroup:
             else:
                 raise ValueError(f"unknown backend {backend!r}")
             self.clients.append(e)
+        self.tamper = tamper
+        self._robust_tab = None   # hip, robust aggregators: device pointer tables of the k buffers, per parity
         if backend == "hip":
             self.stream = torch.cuda.Stream(device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -93,8 +105,30 @@ class ClientGroup:
         s = self.stream.cuda_stream
         for e in self.clients:
             e.engine.run_local(r, s)      # train + Adam + eval into its own FedAvg buffer
+        lead = self.clients[0]
+        par = (r + 1) & 1
+        bufs = [e.params[par] for e in self.clients]
+        if self.tamper is not None:
+            with torch.cuda.stream(self.stream):
+                self.tamper(r, bufs)
+        if lead.robust:
+            # one launch, in place: every client's buffer is a source and a destination; the round's
+            # live flag, index and sampled mask are the lead client's (identical on all)
+            if self._robust_tab is None:
+                self._robust_tab = [torch.tensor([e.params[q].data_ptr() for e in self.clients], dtype=torch.int64,
+                                                 device=self.device) for q in (0, 1)]
+            tab = self._robust_tab[par].data_ptr()
+            lead.m.robust_aggregate(lead.dims, lead.robust, float(lead.cfg.trim_ratio), tab, self.k, tab, self.k,
+                                    lead.state[par].data_ptr(), lead.rtab.data_ptr(), self.k * lead.tail_stride,
+                                    int(lead.cfg.max_rounds), s)
+        else:
+            self._sum_hip(bufs)
+        for e in self.clients:
+            e.server_step(r)              # server optimizer: every client steps its replica of the sum
+            e.rounds_issued = r + 1
+
+    def _sum_hip(self, bufs) -> None:
         with torch.cuda.stream(self.stream):
-            bufs = [e.params[(r + 1) & 1] for e in self.clients]
             tot = getattr(self, "_tot", None)
             if tot is None or tot.shape != bufs[0].shape:
                 tot = self._tot = torch.empty_like(bufs[0])   # one accumulation buffer for all rounds
@@ -103,18 +137,20 @@ class ClientGroup:
                 tot += b                  # rank order
             for b in bufs:
                 b.copy_(tot)
-        for e in self.clients:
-            e.server_step(r)              # server optimizer: every client steps its replica of the sum
-            e.rounds_issued = r + 1
 
     def _round_torch(self) -> None:
         for e in self.clients:
             e.step_train()
             e.step_eval()
         bufs = [e.fedavg_contribution() for e in self.clients]
-        tot = bufs[0].clone()
-        for b in bufs[1:]:
-            tot += b
+        if self.tamper is not None:
+            self.tamper(self.rounds, bufs)
+        if self.clients[0].robust:
+            tot = self.clients[0].robust_combine(bufs)
+        else:
+            tot = bufs[0].clone()
+            for b in bufs[1:]:
+                tot += b
         for e in self.clients:
             e.fedavg_apply(tot.clone())
 

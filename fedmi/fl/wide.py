@@ -42,7 +42,11 @@ class WideClient:
                  micro_batch: int = 131072, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  step_size: int = 30, gamma: float = 0.5, seed: int = 0, dtype: str = "bf16",
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
-                 fused_eval: Optional[bool] = None, server_opt: str = "none"):
+                 fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean"):
+        if aggregator != "mean":
+            # the wide path all-reduces its buckets; nothing gathers the clients' models
+            raise ValueError(f"WideClient does not run a robust aggregator (aggregator={aggregator!r}); "
+                             "use the round engines (EngineConfig.aggregator)")
         if server_opt != "none":
             # the wide path aggregates with its own all-reduce and keeps no server state
             raise ValueError(f"WideClient does not run a server optimizer (server_opt={server_opt!r}); "

@@ -88,6 +88,9 @@ class FedTrialGroup:
         if base.server_opt != "none":
             # the trials share launches and one collective; a server step per trial is not batched
             raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")
+        if base.aggregator != "mean":
+            # the trials share one SUM all-reduce; a gather and a selection per trial is not batched
+            raise ValueError("fed_sweep does not run robust-aggregator trials (aggregator)")
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         rank = comm.rank if comm is not None else 0

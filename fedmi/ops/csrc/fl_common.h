@@ -70,6 +70,25 @@ struct MLPDesc {
     int lds_floats;                   // LDS floats needed per block
 };
 
+// Real parameters of the image's float4 that starts at float `idx` (a multiple of 4): its elements
+// j < fl_image_lim are parameters, the rest image padding (rows >= N, columns >= K, the 4 pad floats
+// of a row, bias slots >= N); <= 0: all padding.  The layer by compile-time-indexed selects; a
+// float4 lies in one row and one 4-float swizzle chunk (fl_ldw and the chunk swizzle are multiples
+// of 4).
+__host__ __device__ inline int fl_image_lim(const MLPDesc& d, int idx) {
+    int K = d.dim[0], N = d.dim[1], iwo = d.iw_off[0], ibo = d.ib_off[0];
+#pragma unroll
+    for (int t = 1; t < FL_MAX_LAYERS; ++t)
+        if (t < d.L && idx >= d.iw_off[t]) {
+            K = d.dim[t]; N = d.dim[t + 1]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
+        }
+    if (idx >= ibo) return N - (idx - ibo);
+    const int ldw = fl_ldw(K);
+    const int q = idx - iwo;
+    const int n = q / ldw, c = q - n * ldw;
+    return n < N ? K - (c ^ fl_swz(n)) : 0;
+}
+
 // bf16 LDS layout of the fused kernels (fl_kernels_bf16.hip).  All offsets are BYTES into
 // the dynamic LDS window.  Every fan-in dimension is padded to kp = roundup32(dim) (one
 // v_mfma_f32_16x16x32_bf16 k-step per 32).  W_l has kp[l+1] rows (the dgrad contraction
@@ -309,6 +328,29 @@ struct FLServer {
     float* v;            // [Pimg] fp32, caller-owned (adaptive kinds; unused by FL_SERVER_SGD)
 };
 
+// Robust aggregation (fl_robust.hip; Yin et al. 2018): parameters of the per-round coordinate-wise
+// median / trimmed mean over K clients' buffers, passed to that kernel alone.  Of the round's K_r
+// sampled clients (rtab mask) the fl_robust_trim lowest and highest values of every coordinate are
+// dropped, the rest averaged.
+#define FL_ROBUST_MEDIAN 1
+#define FL_ROBUST_TRIMMED 2
+#define FL_ROBUST_MAX_K 64           // width of the rtab mask
+struct FLRobust {
+    int kind;            // FL_ROBUST_*
+    int K;               // sources, 1 .. FL_ROBUST_MAX_K
+    int max_rounds;      // rounds of rtab; rounds past it are not live
+    double beta;         // trimmed mean: fraction cut at each end, in [0, 0.5)
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+};
+// values cut at each end of K_r >= 1 sampled clients: median (K_r - 1) / 2, trimmed mean
+// floor(beta K_r) in double, never more than the median's (fedmi/fl/aggregate.py trim_count)
+__host__ __device__ inline int fl_robust_trim(int kind, double beta, int kr) {
+    const int med = (kr - 1) / 2;
+    if (kind == FL_ROBUST_MEDIAN) return med;
+    const int t = (int)(beta * (double)kr);
+    return t < med ? t : med;
+}
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -349,6 +391,13 @@ hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, con
 // split-bf16 image of the result into `pk`.
 hipError_t fl_launch_server(const MLPDesc& d, const FLServer& p, const float* x, float* a, const FLState* st,
                             const MLPDescB* e, char* pk, hipStream_t s);
+// (fl_robust.hip) robust aggregate of the round whose state is `st`, over the K buffers of Pimg +
+// `tails_len` floats named by the device pointer table `src`, written to the `n_dst` buffers named by
+// the device pointer table `dst` (destinations may be sources).  Image: median / trimmed mean of the
+// round's sampled clients, padding exact 0; tails, and the whole buffer of a round that is not live:
+// the left fold in source order.  No per-round host argument: the launch is replayable.
+hipError_t fl_launch_robust(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
+                            const FLState* st, int tails_len, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

@@ -1100,6 +1100,36 @@ static void synth(uintptr_t X, uintptr_t y, long long n, int F, unsigned long lo
                               as_ptr<const float>(w2), H, as_stream(stream), label_noise));
 }
 
+// Robust aggregate (fl_robust.hip) over K buffers of the image of `dims` + `tails_len` floats.  `src` /
+// `dst`: device tables of K / n_dst buffer addresses (int64); `state` / `rtab`: a client's round
+// state and per-round table.  Works across engines' buffers, so it is not an FLEngine phase.
+static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintptr_t src, int K, uintptr_t dst,
+                             int n_dst, uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds,
+                             uintptr_t stream) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("robust_aggregate: 1..4 Linear layers supported");
+    if (K < 1 || K > FL_ROBUST_MAX_K)
+        throw std::runtime_error("robust_aggregate: 1.." + std::to_string(FL_ROBUST_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (kind != FL_ROBUST_MEDIAN && kind != FL_ROBUST_TRIMMED)
+        throw std::runtime_error("robust_aggregate: kind must be 1 (median) or 2 (trimmed mean)");
+    if (!(beta >= 0.0 && beta < 0.5)) throw std::runtime_error("robust_aggregate: beta must be in [0, 0.5)");
+    if (n_dst < 1 || n_dst > FL_ROBUST_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !dst || !state || !rtab)
+        throw std::runtime_error("robust_aggregate: bad arguments");
+    MLPDesc d;
+    std::memset(&d, 0, sizeof(d));
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    FLRobust p;
+    std::memset(&p, 0, sizeof(p));
+    p.kind = kind;
+    p.K = K;
+    p.max_rounds = max_rounds;
+    p.beta = beta;
+    p.rtab = as_ptr<const float>(rtab);
+    HIP_CHECK(fl_launch_robust(d, p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
+                               as_ptr<const FLState>(state), tails_len, as_stream(stream)));
+}
+
 #ifndef FEDMI_SRC_DIGEST
 #define FEDMI_SRC_DIGEST "unknown"
 #endif
@@ -1176,6 +1206,10 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def_property_readonly("size", &TrialBatch::size);
     m.def("synth", &synth, py::arg("X"), py::arg("y"), py::arg("n"), py::arg("F"), py::arg("seed"), py::arg("off"),
           py::arg("w1"), py::arg("w2"), py::arg("H"), py::arg("stream"), py::arg("label_noise") = 0.f);
+    m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
+          py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
+          py::arg("max_rounds"), py::arg("stream"));
+    m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);
     m.attr("SRC_DIGEST") = std::string(kSrcDigestMarker + sizeof("FEDMI_SRC_DIGEST:") - 1);

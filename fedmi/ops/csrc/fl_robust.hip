@@ -1,0 +1,175 @@
+// Byzantine-robust aggregation of a FedAvg round (Yin et al. 2018, "Byzantine-Robust Distributed
+// Learning: Towards Optimal Statistical Rates"): one launch per round, after the K clients published
+// their contributions (the unscaled post-step local models: the engine's FedAvg scale is 1 for a
+// sampled client in robust mode), replaces the weighted sum by the coordinate-wise median or
+// beta-trimmed mean.  With S_r the round's sampled clients (rtab mask of the round in `st`),
+// K_r = |S_r| and t = fl_robust_trim (median (K_r - 1) / 2, trimmed mean floor(beta K_r)), per
+// coordinate of the parameter image:
+//
+//   order the K_r values: any NaN above +inf, otherwise by value; ties (-0 and +0 tie) by client index
+//   drop the t lowest and the t highest
+//   acc = 0; acc = add(acc, v_k) over the kept clients in client order; result = div(acc, float(K_r - 2 t))
+//
+// Every operation is an explicit round-to-nearest fp32 intrinsic, so the result is bit-identical on
+// every rank and across replays whatever the compile flags (as in fl_server.hip);
+// fedmi/fl/aggregate.py robust_aggregate_torch is the host model of it.  The aggregate is
+// unweighted: sample sizes are self-reported, and a weighted median is not what the paper analyses.
+//
+// Selection is rank by counting on the sortable-integer image of the float (NaN canonicalised to
+// one key above +inf's, an unsampled slot to the key above that, so it ranks behind every sampled
+// one): rank_i = #{j : key_j < key_i, or key_j == key_i and j < i}, each pair compared once.  That is
+// K (K - 1) / 2 compares per coordinate, branch-free, no LDS, no atomics, no grid barrier.  The
+// kernel is instantiated for K buckets 4 / 8 / 16 / 32 / 64 with every loop unrolled, so values,
+// keys and ranks stay in registers (3 K per coordinate; a runtime-indexed array would live in
+// scratch).  Buckets up to 8 take one float4 of the image per thread, the wider ones one float
+// (float4 at 64 would need 768 registers).  Slots past K re-read source K - 1 and are masked out.
+//
+// One thread owns a coordinate: it reads it from all K sources -- every load issued before the
+// first use, one L2 latency per thread -- and writes the result to all n_dst destinations, which may
+// be sources (in place: nobody else reads or writes that coordinate).  Image padding of every
+// destination is written as exact 0 whatever the sources hold: a tampered peer cannot break the
+// zero-padding invariant the unpredicated MFMA operand reads rely on (fl_common.h).
+//
+// The metric tails behind the image (tails_len floats; every client fills its own slot) are the
+// left fold over all K sources in source order, as the one-shot all-reduce sums them.  A round
+// that is not live (past an early stop or past max_rounds; client 0 republished the global image,
+// the others zeros) folds the whole buffer that way, padding included: it stays the exact no-op
+// it is under the weighted sum.
+//
+// Launch- and latency-bound like fl_server: 64-thread workgroups, so the waves land on CUs of
+// their own; the tails run in workgroups of their own (no wave mixes the two paths).  Plain vector
+// stores only.
+#include "fl_common.h"
+
+#define FL_ROBUST_THREADS 64
+
+// Sortable image of a float: unsigned order of the keys = the total order above.
+__device__ __forceinline__ uint32_t robust_key(float x) {
+    const uint32_t u = __float_as_uint(x);
+    const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return (u & 0x7fffffffu) > 0x7f800000u ? 0xfffffffeu : (u == 0x80000000u ? 0x80000000u : k);
+}
+
+// Clients' values of a float / float4 at float `idx`: all loads issued, nothing used.
+template <int KB, int VEC>
+__device__ __forceinline__ void robust_load(const float* const* __restrict__ src, int K, int idx, float (&v)[KB][VEC]) {
+#pragma unroll
+    for (int i = 0; i < KB; ++i) {
+        const float* s = src[i < K ? i : K - 1];
+        if constexpr (VEC == 4) {
+            const float4 x = *reinterpret_cast<const float4*>(s + idx);
+            v[i][0] = x.x; v[i][1] = x.y; v[i][2] = x.z; v[i][3] = x.w;
+        } else {
+            v[i][0] = s[idx];
+        }
+    }
+}
+
+// Left fold in source order (tails; rounds that are not live).
+template <int KB, int VEC>
+__device__ __forceinline__ float robust_fold(const float (&v)[KB][VEC], int K, int e) {
+    float acc = v[0][e];
+#pragma unroll
+    for (int i = 1; i < KB; ++i) acc = i < K ? __fadd_rn(acc, v[i][e]) : acc;
+    return acc;
+}
+
+// Median / trimmed mean of column e: ranks in [lo, hi) are kept, n = float(hi - lo).
+template <int KB, int VEC>
+__device__ __forceinline__ float robust_select(const float (&v)[KB][VEC], int e, uint64_t mask, int lo, int hi,
+                                               float n) {
+    uint32_t key[KB];
+    int rank[KB];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) {
+        key[i] = ((mask >> i) & 1) ? robust_key(v[i][e]) : 0xffffffffu;
+        rank[i] = 0;
+    }
+#pragma unroll
+    for (int i = 1; i < KB; ++i)
+#pragma unroll
+        for (int j = 0; j < i; ++j) {
+            const int before = key[j] <= key[i] ? 1 : 0;  // j < i: j sorts before i on a tie
+            rank[i] += before;
+            rank[j] += 1 - before;
+        }
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < KB; ++i) acc = (rank[i] >= lo && rank[i] < hi) ? __fadd_rn(acc, v[i][e]) : acc;
+    return __fdiv_rn(acc, n);
+}
+
+template <int KB, int VEC>
+__global__ void __launch_bounds__(FL_ROBUST_THREADS)
+fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, float* const* __restrict__ dst, int n_dst,
+                 const FLState* __restrict__ st, int tails_len, int img_blocks) {
+    if ((int)blockIdx.x >= img_blocks) {
+        // metric tails: one float per thread
+        const int j = ((int)blockIdx.x - img_blocks) * FL_ROBUST_THREADS + threadIdx.x;
+        if (j >= tails_len) return;
+        float v[KB][1];
+        robust_load<KB, 1>(src, p.K, d.Pimg + j, v);
+        const float out = robust_fold<KB, 1>(v, p.K, 0);
+        for (int q = 0; q < n_dst; ++q) dst[q][d.Pimg + j] = out;
+        return;
+    }
+    const int u = blockIdx.x * FL_ROBUST_THREADS + threadIdx.x;
+    const int idx = VEC * u;
+    if (idx >= d.Pimg) return;
+    float v[KB][VEC];
+    robust_load<KB, VEC>(src, p.K, idx, v);
+    // the round's sampled clients
+    uint64_t mask = 0;
+    if (st->live) {
+        const int r = st->cur_round;
+        if (r >= 0 && r < p.max_rounds) {
+            const uint32_t* rt = reinterpret_cast<const uint32_t*>(p.rtab) + 4 * (size_t)r;
+            mask = ((uint64_t)rt[3] << 32) | rt[2];
+            if (p.K < 64) mask &= (1ull << p.K) - 1ull;
+        }
+    }
+    const int kr = __popcll(mask);
+    float out[VEC];
+    if (kr == 0) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) out[e] = robust_fold<KB, VEC>(v, p.K, e);
+    } else {
+        const int t = fl_robust_trim(p.kind, p.beta, kr);
+        const float n = (float)(kr - 2 * t);
+        const int lim = fl_image_lim(d, idx & ~3) - (idx & 3);  // elements e < lim are real parameters
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float a = robust_select<KB, VEC>(v, e, mask, t, kr - t, n);
+            out[e] = e < lim ? a : 0.f;
+        }
+    }
+    for (int q = 0; q < n_dst; ++q) {
+        float* o = dst[q] + idx;
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(out[0], out[1], out[2], out[3]);
+        else *o = out[0];
+    }
+}
+
+template <int KB, int VEC>
+static void robust_launch(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
+                          const FLState* st, int tails_len, hipStream_t s) {
+    const int units = d.Pimg / VEC;
+    const int img_blocks = (units + FL_ROBUST_THREADS - 1) / FL_ROBUST_THREADS;
+    const int tail_blocks = (tails_len + FL_ROBUST_THREADS - 1) / FL_ROBUST_THREADS;
+    hipLaunchKernelGGL((fl_robust_kernel<KB, VEC>), dim3(img_blocks + tail_blocks), dim3(FL_ROBUST_THREADS), 0, s, d, p,
+                       src, dst, n_dst, st, tails_len, img_blocks);
+}
+
+hipError_t fl_launch_robust(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
+                            const FLState* st, int tails_len, hipStream_t s) {
+    if ((d.Pimg & 3) != 0 || d.Pimg < 4 || src == nullptr || dst == nullptr || st == nullptr || p.rtab == nullptr ||
+        p.K < 1 || p.K > FL_ROBUST_MAX_K || n_dst < 1 || tails_len < 0 || p.max_rounds < 1 ||
+        (p.kind != FL_ROBUST_MEDIAN && p.kind != FL_ROBUST_TRIMMED) || !(p.beta >= 0.0 && p.beta < 0.5))
+        return hipErrorInvalidValue;
+    if (p.K <= 4) robust_launch<4, 4>(d, p, src, dst, n_dst, st, tails_len, s);
+    else if (p.K <= 8) robust_launch<8, 4>(d, p, src, dst, n_dst, st, tails_len, s);
+    else if (p.K <= 16) robust_launch<16, 1>(d, p, src, dst, n_dst, st, tails_len, s);
+    else if (p.K <= 32) robust_launch<32, 1>(d, p, src, dst, n_dst, st, tails_len, s);
+    else robust_launch<64, 1>(d, p, src, dst, n_dst, st, tails_len, s);
+    return hipGetLastError();
+}

@@ -96,22 +96,7 @@ fl_server_kernel(MLPDesc d, FLServer p, const float* __restrict__ xg, float* __r
     float4 m = reinterpret_cast<const float4*>(p.m)[i];
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (KIND != FL_SERVER_SGD) v = reinterpret_cast<const float4*>(p.v)[i];
-    const int idx = 4 * i;
-    int K = d.dim[0], N = d.dim[1], iwo = d.iw_off[0], ibo = d.ib_off[0];
-#pragma unroll
-    for (int t = 1; t < FL_MAX_LAYERS; ++t)
-        if (t < d.L && idx >= d.iw_off[t]) {
-            K = d.dim[t]; N = d.dim[t + 1]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-        }
-    int lim;  // elements j < lim of the float4 are real parameters
-    if (idx >= ibo) {
-        lim = N - (idx - ibo);
-    } else {
-        const int ldw = fl_ldw(K);
-        const int q = idx - iwo;
-        const int n = q / ldw, c = q - n * ldw;
-        lim = n < N ? K - (c ^ fl_swz(n)) : 0;
-    }
+    const int lim = fl_image_lim(d, 4 * i);  // elements j < lim of the float4 are real parameters
     server_quad<KIND>(p, 0 < lim, 1 < lim, 2 < lim, 3 < lim, x, a, m, v);
     reinterpret_cast<float4*>(ag)[i] = a;
     reinterpret_cast<float4*>(p.m)[i] = m;

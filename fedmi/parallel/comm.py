@@ -364,6 +364,21 @@ class Comm:
             acc += p
         return acc
 
+    def allgather_device(self, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every rank's ``t`` (same length on all ranks) as rows of a ``[size, n]`` tensor on ``t``'s
+        device, in rank order, gathered over gloo exactly as :meth:`_host_sum_rank_order` gathers;
+        written into ``out`` when given.  On the current stream."""
+        h = t.detach().reshape(-1).cpu()
+        if self.size == 1:
+            parts = [h]
+        else:
+            parts = [torch.empty_like(h) for _ in range(self.size)]
+            dist.all_gather(parts, h)
+        stack = torch.stack(parts)
+        if out is None:
+            return stack.to(t.device)
+        return out.copy_(stack)
+
     def rccl_or_host(self):
         """COLLECTIVE.  The RCCL communicator (:meth:`rccl`), or ``None`` when RCCL is not
         allowed or its bootstrap failed -- then RCCL is disabled for the rest of the job and
