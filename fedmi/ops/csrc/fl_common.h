@@ -41,17 +41,17 @@
 #define FL_LAG_PARTS (FL_LAG_SPR == 2 ? 4 : 2)
 #define FL_LAG_MAX_C 4
 // logits part range of scoring wave j of a group (parts [fl_lag_w(G, j), fl_lag_w(G, j + 1)))
-__host__ __device__ inline int fl_lag_w(int G, int j) { return G - ((FL_LAG_SPR - j) * G) / FL_LAG_SPR; }
+__host__ __device__ constexpr int fl_lag_w(int G, int j) { return G - ((FL_LAG_SPR - j) * G) / FL_LAG_SPR; }
 
 // ldw = roundup16(K) + 4 (4 mod 8 floats): 16-byte aligned rows; with the chunk swizzle
 // (fl_swz below) the rows of every gfx950 ds_read_b128 lane group land on distinct 16-byte
 // bank slots.
-__host__ __device__ inline int fl_ldw(int K) { return ((K + 15) & ~15) + 4; }
-__host__ __device__ inline int fl_wrows(int N) { return (N + 15) & ~15; }
+__host__ __device__ constexpr int fl_ldw(int K) { return ((K + 15) & ~15) + 4; }
+__host__ __device__ constexpr int fl_wrows(int N) { return (N + 15) & ~15; }
 // fp32 LDS / image chunk swizzle: row r keeps logical column k < roundup16(width) at column
 // k ^ fl_swz(r) -- the 4-float chunks of rows 4..11 (mod 16) trade places in pairs
 // (fl_kernels.hip; models/mlp.py mirrors it).
-__host__ __device__ inline int fl_swz(int r) { return ((r + 4) & 8) >> 1; }
+__host__ __device__ constexpr int fl_swz(int r) { return ((r + 4) & 8) >> 1; }
 
 struct MLPDesc {
     int L;                            // number of Linear layers
@@ -150,8 +150,8 @@ struct MLPDescB {
 // Packed bf16 W images (see the bank notes above): byte offset of row n (fl_wrow(kp rows) =
 // image bytes), the chunk swizzle of row n, the byte position of element (n, k), and the W
 // row / output column that lane lr of a forward tile computes.
-__host__ __device__ inline int fl_wrow(int n, int ldw, int wgap) { return n * ldw * 2 + (n >> 3) * wgap; }
-__host__ __device__ inline int fl_wswz(int n, int wxor) { return ((n >> 3) & 1) * wxor; }
+__host__ __device__ constexpr int fl_wrow(int n, int ldw, int wgap) { return n * ldw * 2 + (n >> 3) * wgap; }
+__host__ __device__ constexpr int fl_wswz(int n, int wxor) { return ((n >> 3) & 1) * wxor; }
 __host__ __device__ inline int fl_wbyte(const MLPDescB& e, int l, int n, int k) {
     return fl_wrow(n, e.ldw[l], e.wgap) + ((((k >> 3) ^ fl_wswz(n, e.wxor)) << 4) | ((k & 7) << 1));
 }
@@ -359,7 +359,14 @@ struct PeerPack;
 hipError_t fl_launch_train(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,
                            const float* pg, const FLState* st_in, FLState* st_out,
                            int local_step, hipStream_t s, int mode = FL_EVAL_CLASSIC,
-                           float* cm_out = nullptr, int fold_mask = FL_FOLD_B);
+                           float* cm_out = nullptr, int fold_mask = FL_FOLD_B, bool shape_spec = false);
+// (fl_train_spec.hip: the fp32 train kernel specialised for the reference shape; `shape_spec` above
+// lets fl_launch_train pick it where fl_train_spec_ok holds)
+bool fl_train_spec_ok(const MLPDesc& d, const FLConfig& c, int mode);
+hipError_t fl_launch_train_spec(const FLConfig& c, const FLBuffers& b, const float* pg, const FLState* st_in,
+                                FLState* st_out, int local_step, hipStream_t s, int mode, float* cm_out,
+                                int fold_mask);
+hipError_t fl_set_lds_limit_spec(size_t bytes);
 // `st` = state the step runs under; with `fold` (FL_EVAL_FUSED rounds, first local step) it
 // is the previous round's state: every block folds pg's tail into it, block 0 writes the
 // round's state to `st_out`.
@@ -408,7 +415,15 @@ hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffe
 hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                 const float* pg, const FLState* st_in, FLState* st_out, int local_step,
                                 hipStream_t s, bool stage_local = false, int mode = FL_EVAL_CLASSIC,
-                                float* cm_out = nullptr, int fold_mask = FL_FOLD_B);
+                                float* cm_out = nullptr, int fold_mask = FL_FOLD_B, bool shape_spec = false);
+// (fl_train_bf16_spec.hip: the train kernel specialised for the reference shape, fl_layout.h FlRefShape.
+// `shape_spec` above lets fl_launch_train_bf16 pick it where fl_train_bf16_spec_ok holds: descriptors
+// byte-equal to the compile-time ones, and a round kind that is instantiated)
+bool fl_train_bf16_spec_ok(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, int mode);
+hipError_t fl_launch_train_bf16_spec(const FLConfig& c, const FLBuffers& b, const float* pg, const FLState* st_in,
+                                     FLState* st_out, int local_step, hipStream_t s, bool stage_local, int mode,
+                                     float* cm_out, int fold_mask);
+hipError_t fl_set_lds_limit_bf16_spec(size_t bytes);
 hipError_t fl_launch_eval_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                const float* params, float* comm, const FLState* st, hipStream_t s);
 hipError_t fl_set_lds_limit_bf16(size_t bytes);

@@ -356,6 +356,14 @@ class FLEngine {
                               (force_on || 2 * c_.n_slabs <= cus)) ? 1 : 0;
         }
 
+        // shape-specialised train kernels (fl_train_bf16_spec.hip, fl_train_spec.hip): on by default, FEDMI_SHAPE_SPEC=0
+        // forces the generic kernels (A/B, tests).  The launch function decides per launch; reported
+        // as layout()["shape_spec"]: the one-client round's train kernel is the specialised one
+        {
+            const char* sp = std::getenv("FEDMI_SHAPE_SPEC");
+            shape_spec_on_ = !(sp != nullptr && sp[0] == '0');
+        }
+
         b_.X = as_ptr<const float>(bufs["X"].cast<uintptr_t>());
         b_.y = as_ptr<const int>(bufs["y"].cast<uintptr_t>());
         b_.slab = as_ptr<float>(bufs["slab"].cast<uintptr_t>());
@@ -729,6 +737,9 @@ class FLEngine {
         o["lag_reg"] = dtype_ == 1 && e_.lag_reg != 0;  // lagged rounds score in registers (fl_layout.h)
         o["plain_fwd"] = c_.plain_fwd != 0;              // plain-bf16 training forward (several clients)
         o["split_score"] = c_.split_score != 0;          // lagged scoring on workgroups of its own
+        // the train kernel of classic / fused rounds is the reference shape's specialised one
+        o["shape_spec"] = shape_spec_on_ && (dtype_ == 1 ? fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED)
+                                                         : fl_train_spec_ok(d_, c_, FL_EVAL_FUSED));
         o["eval_fedavg"] = peer_ != nullptr && !tr_.fused && tr_.eval_fedavg_fits;
         o["dtype"] = dtype_;
         o["slab_stride"] = c_.slab_stride;
@@ -801,10 +812,11 @@ class FLEngine {
                 HIP_CHECK(fl_launch_pack_bf16(d_, e_, F(0), (char*)F(1), s));
                 break;
             case FLLaunchRec::TRAIN:
-                if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3]));
+                if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3],
+                                                              shape_spec_on_));
                 else
                     HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
-                                                   i[3]));
+                                                   i[3], shape_spec_on_));
                 break;
             case FLLaunchRec::ADAM: {
                 PeerArgs pa;
@@ -880,6 +892,7 @@ class FLEngine {
     MLPDescB e_;
     MLPDescB ev_;  // evaluation-only layout of e_ (no delta buffers)
     int dtype_ = 0;  // 0 = fp32 MFMA, 1 = bf16 MFMA (fp32 accumulate / master weights)
+    bool shape_spec_on_ = true;  // FEDMI_SHAPE_SPEC != 0: launchers may pick shape-specialised kernels
     char* pk_ = nullptr;
     float* lagbuf_ = nullptr;  // FL_EVAL_LAGGED count + loss carry-over
     long long comm_len_ = 0;   // floats of a comm buffer: image + tails (+ lag region)

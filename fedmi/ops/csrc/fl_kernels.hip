@@ -32,6 +32,7 @@
 #include "fl_device.h"
 #include "peer_device.h"
 #include "fl_philox.h"
+#include "fl_layout.h"
 #include <math.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -69,7 +70,9 @@ __device__ __forceinline__ float f4(const float4& v, int j) {
 
 // out[r][n] = act(sum_k in[r][k] W[n][k] + bias[n]) for all R rows; columns
 // [N, roundup16(N)) come out 0 (zero image rows + zero bias padding).
-template <int RT>
+// ST (all GEMM phases below): called under the static shape policy (fl_layout.h FlShapeRef) with
+// constant shapes -- the chunk loops are fully unrolled; false: the run-time loops as they are.
+template <int RT, bool ST = false>
 __device__ void fwd_layer_mfma(const float* w, int ldw, const float* bias, int K, int N, const float* in,
                                int ld_in, float* out, int ld_out, bool relu) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -91,6 +94,7 @@ __device__ void fwd_layer_mfma(const float* w, int ldw, const float* bias, int K
         // group g takes k = 16q + 4g + j): skipped -- they would add exact zeros (a (50, 200) layer
         // runs 14 of 16 steps)
         const int klast = K - 16 * (kchunks - 1);
+#pragma unroll ST ? 16 : 1
         for (int q = 0; q < kchunks; ++q) {
             const int qn = (q + 1 < kchunks) ? q + 1 : q;  // prefetch (last: harmless reload)
             const float4 bn = lds4(wr + 16 * qn);
@@ -181,7 +185,7 @@ __device__ __forceinline__ int wgrad_waves_fp32(int K, int N, int l) {
 // same phase can run the layer's wgrad, which reads act).  Item = 16-column tile of dH (all
 // R rows); B fragment W[o][i] reused across the RT rows.  Items are handed out from the
 // LAST wave down, so they pair with the wgrad tiles handed out from wave 0 up.
-template <int RT>
+template <int RT, bool ST = false>
 __device__ void dgrad_layer(const float* w, int ldw, int K, int N, const float* dz, int ld_z, const float* act,
                             int ld_a, float* out) {
     const int wave = (FL_WAVES - 1) - (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -207,6 +211,7 @@ __device__ void dgrad_layer(const float* w, int ldw, int K, int N, const float* 
         for (int j = 0; j < 4; ++j) bc[j] = wc[j * ldw];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) ac[rt] = lds4(ar + rt * 16 * ld_z);
+#pragma unroll ST ? 16 : 1
         for (int q = 0; q < ochunks; ++q) {
             const int qn = (q + 1 < ochunks) ? q + 1 : q;
             float bn[4];
@@ -319,15 +324,20 @@ __device__ void stage_rows(const float* __restrict__ X, int n_rows, int F, int r
 
 // The global parameter image is bit-identical to the LDS image (weight rows already swizzled,
 // fl_common.h): one float4 copy.
-__device__ __forceinline__ void stage_image(const MLPDesc& d, const float* __restrict__ params, float* li) {
+template <class SP = FlShapeDyn>
+__device__ __forceinline__ void stage_image(const MLPDesc& d_, const float* __restrict__ params, float* li) {
+    FL_SHAPE_D(SP, d, d_);
     const float4* src = reinterpret_cast<const float4*>(params);
     float4* dst = reinterpret_cast<float4*>(li);
     const int n4 = d.Pimg >> 2;
     for (int e = threadIdx.x; e < n4; e += FL_THREADS) dst[e] = src[e];
 }
 
-template <int RT>
-__device__ void forward_block(const MLPDesc& d, float* acts, const float* li, unsigned long long* dbg = nullptr) {
+template <int RT, class SP = FlShapeDyn>
+__device__ void forward_block(const MLPDesc& d_, float* acts, const float* li, unsigned long long* dbg = nullptr) {
+    FL_SHAPE_D(SP, d, d_);
+    // static shape policy: one copy per layer, every shape and offset a constant of its copy
+#pragma unroll SP::kStatic ? FL_MAX_LAYERS : 1
     for (int l = 0; l < d.L; ++l) {
         if (dbg != nullptr && threadIdx.x == 0) dbg[blockIdx.x * 16 + 10 + l] = __builtin_amdgcn_s_memrealtime();
         const int K = d.dim[l], N = d.dim[l + 1];
@@ -337,7 +347,7 @@ __device__ void forward_block(const MLPDesc& d, float* acts, const float* li, un
             fwd_head_valu<RT>(w, fl_ldw(K), bias, K, N, acts + d.act_off[l], d.ld[l], acts + d.act_off[l + 1],
                               d.ld[l + 1]);
         else
-            fwd_layer_mfma<RT>(w, fl_ldw(K), bias, K, N, acts + d.act_off[l], d.ld[l], acts + d.act_off[l + 1],
+            fwd_layer_mfma<RT, SP::kStatic>(w, fl_ldw(K), bias, K, N, acts + d.act_off[l], d.ld[l], acts + d.act_off[l + 1],
                                d.ld[l + 1], l + 1 < d.L);
         lds_barrier();
     }
@@ -346,12 +356,16 @@ __device__ void forward_block(const MLPDesc& d, float* acts, const float* li, un
 // ---------------------------------------------------------------------------------------
 // Kernels
 // ---------------------------------------------------------------------------------------
+// FL_FP32_DEVICE_ONLY: fl_train_spec.hip includes this file for the device functions above and
+// defines the shape-specialised train kernel in a translation unit of its own.
+#ifndef FL_FP32_DEVICE_ONLY
 // Kernel body shared by the single-engine and trial-batch entry points (fl_train_body.inc).
 template <int RT>
 __global__ void __launch_bounds__(FL_THREADS)
 fl_train_kernel(MLPDesc d, FLConfig c, FLBuffers b, const float* __restrict__ pg,
                 const FLState* __restrict__ st_in, FLState* __restrict__ st_out, int local_step, int mode,
                 float* __restrict__ cm_out, int fold_mask) {
+    using SP = FlShapeDyn;
 #include "fl_train_body.inc"
 }
 
@@ -366,6 +380,7 @@ fl_train_batch_kernel(MLPDesc d, const FLTrialDesc* __restrict__ T, FLSel pg_sel
     const FLState* __restrict__ st_in = reinterpret_cast<const FLState*>(fl_sel(t, si_sel));
     FLState* __restrict__ st_out = reinterpret_cast<FLState*>(fl_sel(t, so_sel));
     float* __restrict__ cm_out = reinterpret_cast<float*>(fl_sel(t, cm_sel));
+    using SP = FlShapeDyn;
 #include "fl_train_body.inc"
 }
 
@@ -590,9 +605,11 @@ static hipError_t launch_train_rt(const MLPDesc& d, const FLConfig& c, const FLB
 
 hipError_t fl_launch_train(const MLPDesc& d, const FLConfig& c, const FLBuffers& b, const float* pg,
                            const FLState* si, FLState* so, int ls, hipStream_t s, int mode, float* cm_out,
-                           int fold_mask) {
+                           int fold_mask, bool shape_spec) {
     if (mode == FL_EVAL_FUSED && cm_out == nullptr) return hipErrorInvalidValue;
     if (mode == FL_EVAL_LAGGED) return hipErrorInvalidValue;  // bf16 kernels only
+    if (shape_spec && fl_train_spec_ok(d, c, mode))
+        return fl_launch_train_spec(c, b, pg, si, so, ls, s, mode, cm_out, fold_mask);
     switch (c.R) {
         case 16: return launch_train_rt<1>(d, c, b, pg, si, so, ls, s, mode, cm_out, fold_mask);
         case 32: return launch_train_rt<2>(d, c, b, pg, si, so, ls, s, mode, cm_out, fold_mask);
@@ -779,5 +796,7 @@ hipError_t fl_set_lds_limit(size_t bytes) {
     FL_SET(fl_eval_batch_kernel<1>); FL_SET(fl_eval_batch_kernel<2>);
     FL_SET(fl_eval_fedavg_kernel<1>); FL_SET(fl_eval_fedavg_kernel<2>);
 #undef FL_SET
+    if (e == hipSuccess) e = fl_set_lds_limit_spec(bytes);
     return e;
 }
+#endif  // FL_FP32_DEVICE_ONLY

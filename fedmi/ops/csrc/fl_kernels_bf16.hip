@@ -25,6 +25,7 @@
 #include "fl_device.h"
 #include "peer_device.h"
 #include "fl_bf16.h"
+#include "fl_layout.h"
 #include <math.h>
 #include <stdint.h>
 
@@ -103,6 +104,7 @@ __device__ __forceinline__ void fl_pack_bf16_body(const MLPDesc& d, const MLPDes
     }
 }
 
+#ifndef FL_BF16_DEVICE_ONLY  // (the kernels and launchers of this file: not for a unit that includes it, see below)
 __global__ void fl_pack_bf16_kernel(MLPDesc d, MLPDescB e, const float* __restrict__ params, char* __restrict__ out) {
     fl_pack_bf16_body(d, e, params, out);
 }
@@ -112,6 +114,7 @@ __global__ void fl_pack_bf16_batch_kernel(MLPDesc d, MLPDescB e, const FLTrialDe
     const FLTrialDesc& t = T[blockIdx.y];
     fl_pack_bf16_body(d, e, reinterpret_cast<const float*>(fl_sel(t, params)), fl_sel(t, out));
 }
+#endif
 
 // Stage the packed parameter region AND this block's input rows with every global load in
 // flight before the first LDS store: the two ~1 us L2 latencies overlap instead of adding.
@@ -123,10 +126,11 @@ __global__ void fl_pack_bf16_batch_kernel(MLPDesc d, MLPDescB e, const FLTrialDe
 // waves out, fwd_sync).
 // PLAIN (plain-bf16 training forward, FLConfig::plain_fwd): only the hi images and the biases
 // (the region's first w_off[0] + wlo_delta bytes) are staged -- half the bytes.
-template <int RT, int NT = FL_THREADS, bool PLAIN = false>
-__device__ __forceinline__ void stage_params_rows_bf16(const MLPDescB& e, const char* __restrict__ packed,
+template <int RT, int NT = FL_THREADS, bool PLAIN = false, class SP = FlShapeDyn>
+__device__ __forceinline__ void stage_params_rows_bf16(const MLPDescB& e_, const char* __restrict__ packed,
                                                        const float* __restrict__ X, int n_rows, int F, int row0,
                                                        char* lds) {
+    FL_SHAPE_E(SP, e, e_);
     const uint4* src = reinterpret_cast<const uint4*>(packed);
     uint4* dst = reinterpret_cast<uint4*>(lds + e.param_off);
     const int n16 = (PLAIN ? e.w_off[0] - e.param_off + e.wlo_delta : e.param_bytes) >> 4;
@@ -251,8 +255,10 @@ __device__ __forceinline__ void params_store(const MLPDescB& e, const char* __re
 // FL_WAVES - FL_LAG_SPR RT, fwd_sync).
 // PLAIN: a_hi.W_hi only (the training forward of several clients, FLConfig::plain_fwd): no lo
 // operands, no lo parts of the outputs.
-template <int RT, int NWV = FL_WAVES, bool PLAIN = false>
-__device__ __forceinline__ void fwd_layer_bf16(const MLPDesc& d, const MLPDescB& e, int l, char* lds) {
+template <int RT, int NWV = FL_WAVES, bool PLAIN = false, class SP = FlShapeDyn>
+__device__ __forceinline__ void fwd_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, char* lds) {
+    FL_SHAPE_D(SP, d, d_);
+    FL_SHAPE_E(SP, e, e_);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4;
     const bool last = (l + 1 == d.L);
@@ -275,6 +281,7 @@ __device__ __forceinline__ void fwd_layer_bf16(const MLPDesc& d, const MLPDescB&
             acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
             acl[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
+#pragma unroll SP::kStatic ? 8 : 1
         for (int ks = 0; ks < ksteps; ++ks) {
             const bf16x8 bv = ld128(wrow + ks * 64);
             if constexpr (PLAIN) {
@@ -363,9 +370,11 @@ __device__ __forceinline__ void slab_put(float* slab, int idx, float v) {
 // Tiles go to waves [0, nw).  nw < FL_WAVES (waves nw.. run a long dgrad, wgrad_waves_bf16):
 // handed out from wave nw-1 down, so the low waves, which also sum the biases (threads 0..),
 // get the fewest.  nw = FL_WAVES: from wave 0 up (the dgrad items pair with them from the top).
-template <int RT, bool F16>
-__device__ void wgrad_layer_bf16(const MLPDesc& d, const MLPDescB& e, int l, const char* lds, float* __restrict__ slab,
+template <int RT, bool F16, class SP = FlShapeDyn>
+__device__ void wgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, const char* lds, float* __restrict__ slab,
                                  int nw) {
+    FL_SHAPE_D(SP, d, d_);
+    FL_SHAPE_E(SP, e, e_);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4, lq = lr >> 2, lp = lr & 3;
     const int K = d.dim[l], N = d.dim[l + 1];
@@ -421,7 +430,9 @@ __device__ void wgrad_layer_bf16(const MLPDesc& d, const MLPDescB& e, int l, con
 // (tools/probes/stamps_fine.py, profiles/ab_backward_waves_r2.log).  Short chains (the head's 1 step)
 // share the waves with the tiles as before.  Only the work-to-wave map changes: every tile
 // and item computes the same values.
-__device__ __forceinline__ int wgrad_waves_bf16(const MLPDescB& e, int l) {
+template <class SP = FlShapeDyn>
+__device__ __forceinline__ int wgrad_waves_bf16(const MLPDescB& e_, int l) {
+    FL_SHAPE_E(SP, e, e_);
     const int items = l > 0 ? (e.kp[l] >> 4) : 0;
     const int steps = e.kp[l + 1] >> 5;
     return (items > 0 && steps >= 4 && 2 * items <= FL_WAVES) ? FL_WAVES - items : FL_WAVES;
@@ -430,8 +441,10 @@ __device__ __forceinline__ int wgrad_waves_bf16(const MLPDescB& e, int l) {
 // D_l[r][i] = (sum_o D_{l+1}[r][o] W_l[o][i]) * (act_l[r][i] > 0), all kp[l] columns.
 // B = W_l^T through transposed reads of the row-major W image.  Items from the last wave
 // down (pairs with wgrad's tiles handed out from wave 0 up).
-template <int RT, bool HWCVT = false>
-__device__ void dgrad_layer_bf16(const MLPDesc& d, const MLPDescB& e, int l, char* lds) {
+template <int RT, bool HWCVT = false, class SP = FlShapeDyn>
+__device__ void dgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, char* lds) {
+    FL_SHAPE_D(SP, d, d_);
+    FL_SHAPE_E(SP, e, e_);
     const int wave = (FL_WAVES - 1) - (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4, lq = lr >> 2, lp = lr & 3;
     const int itiles = e.kp[l] >> 4;
@@ -449,6 +462,7 @@ __device__ void dgrad_layer_bf16(const MLPDesc& d, const MLPDescB& e, int l, cha
         const char* pw = W + fl_wrow(8 * lg + lq, ldw, e.wgap) + 32 * it + 16 * ((lp >> 1) ^ fl_wswz(8 * lg, e.wxor)) +
                          8 * (lp & 1);
         const char* pa = Dn + (lr * ldd + 8 * lg) * 2;
+#pragma unroll SP::kStatic ? 8 : 1
         for (int os = 0; os < osteps; ++os) {
             const char* pwk = pw + os * (64 * ldw + 4 * e.wgap);  // fl_wrow(32 os + r) - fl_wrow(r)
             const bf16x8 bv = cat8(ld_tr(pwk), ld_tr(pwk + 4 * ldw * 2));
@@ -502,9 +516,11 @@ __device__ __forceinline__ void fwd_sync(int* cnt, int& tgt) {
     }
 }
 
-template <int RT, bool PART = false, bool PLAIN = false>
-__device__ __forceinline__ void fwd_head_split_bf16(const MLPDesc& d, const MLPDescB& e, char* lds, int* cnt,
+template <int RT, bool PART = false, bool PLAIN = false, class SP = FlShapeDyn>
+__device__ __forceinline__ void fwd_head_split_bf16(const MLPDesc& d_, const MLPDescB& e_, char* lds, int* cnt,
                                                     int& tgt) {
+    FL_SHAPE_D(SP, d, d_);
+    FL_SHAPE_E(SP, e, e_);
     const int l = d.L - 1, C = d.dim[d.L], G = e.head_split;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4;
@@ -558,21 +574,27 @@ __device__ __forceinline__ void fwd_head_split_bf16(const MLPDesc& d, const MLPD
     for (int i = threadIdx.x; i < RT * 16 * C; i += FL_THREADS) {
         const int row = i / C, c = i - row * C;
         float s = part[row * C + c];
+#pragma unroll SP::kStatic ? 16 : 1
         for (int w = 1; w < G; ++w) s += part[(w * RT * 16 + row) * C + c];
         z[row * FL_LOGIT_LD + c] = s + bias[c];
     }
 }
 
-template <int RT, bool PART = false, bool PLAIN = false>
-__device__ __forceinline__ void forward_block_bf16(const MLPDesc& d, const MLPDescB& e, char* lds, unsigned long long* dbg,
-                                                   int* cnt = nullptr) {
+template <int RT, bool PART = false, bool PLAIN = false, class SP = FlShapeDyn>
+__device__ __forceinline__ void forward_block_bf16(const MLPDesc& d_, const MLPDescB& e_, char* lds,
+                                                   unsigned long long* dbg, int* cnt = nullptr) {
+    FL_SHAPE_D(SP, d, d_);
+    FL_SHAPE_E(SP, e, e_);
     int tgt = 0;
+    // static shape policy: the layer loop is unrolled, so every layer's strides, offsets and trip
+    // counts are constants of its copy (unroll(1): the run-time loop, as without the pragma)
+#pragma unroll SP::kStatic ? FL_MAX_LAYERS : 1
     for (int l = 0; l < d.L; ++l) {
 #ifndef FL_LAG_STAMPS
         if (dbg != nullptr && threadIdx.x == 0) dbg[blockIdx.x * 16 + 10 + l] = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (l + 1 == d.L && e.head_split > 1) fwd_head_split_bf16<RT, PART, PLAIN>(d, e, lds, cnt, tgt);
-        else fwd_layer_bf16<RT, PART ? FL_WAVES - FL_LAG_SPR * RT : FL_WAVES, PLAIN>(d, e, l, lds);
+        if (l + 1 == d.L && e.head_split > 1) fwd_head_split_bf16<RT, PART, PLAIN, SP>(d, e, lds, cnt, tgt);
+        else fwd_layer_bf16<RT, PART ? FL_WAVES - FL_LAG_SPR * RT : FL_WAVES, PLAIN, SP>(d, e, l, lds);
         fwd_sync<RT, PART>(cnt, tgt);
     }
 }
@@ -915,6 +937,9 @@ __device__ void score_block_bf16(const MLPDesc& d, const MLPDescB& e, const FLCo
 // ---------------------------------------------------------------------------------------
 // Kernels
 // ---------------------------------------------------------------------------------------
+// FL_BF16_DEVICE_ONLY: fl_train_bf16_spec.hip includes this file for the device functions above and
+// defines the shape-specialised train kernels in a translation unit of its own.
+#ifndef FL_BF16_DEVICE_ONLY
 // Kernel body shared by the single-engine and trial-batch entry points (fl_train_bf16_body.inc).
 // LAG: the lagged scoring pass (FL_EVAL_LAGGED, several clients) is compiled in -- 1: before
 // the training pass (its register copy of the round's weights: R = 32 126 VGPRs), 2: in
@@ -925,6 +950,7 @@ __global__ void __launch_bounds__(FL_THREADS)
 fl_train_bf16_kernel(MLPDesc d, MLPDescB e, FLConfig c, FLBuffers b, const float* __restrict__ pg,
                      const FLState* __restrict__ st_in, FLState* __restrict__ st_out, int local_step,
                      int stage_local, int mode, float* __restrict__ cm_out, int fold_mask) {
+    using SP = FlShapeDyn;
 #include "fl_train_bf16_body.inc"
 }
 
@@ -933,6 +959,7 @@ __global__ void __launch_bounds__(FL_THREADS)
 fl_train_bf16_batch_kernel(MLPDesc d, MLPDescB e, const FLTrialDesc* __restrict__ T, FLSel pg_sel, FLSel si_sel,
                            FLSel so_sel, int local_step, int stage_local, int mode, FLSel cm_sel, int fold_mask) {
     constexpr int LAG = 0;  // trial batches never run lagged rounds
+    using SP = FlShapeDyn;
     const FLTrialDesc& t = T[blockIdx.y];
     const FLConfig c = t.c;
     const FLBuffers b = t.b;
@@ -1029,8 +1056,10 @@ fl_eval_fedavg_bf16_kernel(MLPDesc d, MLPDescB e, FLConfig c, FLBuffers b, const
 // ---------------------------------------------------------------------------------------
 hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                 const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
-                                bool stage_local, int mode, float* cm_out, int fold_mask) {
+                                bool stage_local, int mode, float* cm_out, int fold_mask, bool shape_spec) {
     if ((mode == FL_EVAL_FUSED || mode == FL_EVAL_LAGGED) && cm_out == nullptr) return hipErrorInvalidValue;
+    if (shape_spec && fl_train_bf16_spec_ok(d, e, c, mode))
+        return fl_launch_train_bf16_spec(c, b, pg, si, so, ls, s, stage_local, mode, cm_out, fold_mask);
     const size_t lds = (size_t)e.lds_bytes;
     const bool lag = mode == FL_EVAL_LAGGED;
     // split scoring (FLConfig::split_score): the lagged round's first local step scores on
@@ -1200,5 +1229,7 @@ hipError_t fl_set_lds_limit_bf16(size_t bytes) {
     FLB_SET(fl_eval_bf16_batch_kernel<1>); FLB_SET(fl_eval_bf16_batch_kernel<2>); FLB_SET(fl_eval_bf16_batch_kernel<4>);
     FLB_SET(fl_eval_fedavg_bf16_kernel<1>); FLB_SET(fl_eval_fedavg_bf16_kernel<2>);
 #undef FLB_SET
+    if (r == hipSuccess) r = fl_set_lds_limit_bf16_spec(bytes);
     return r;
 }
+#endif  // FL_BF16_DEVICE_ONLY

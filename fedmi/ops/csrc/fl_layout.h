@@ -12,12 +12,12 @@
 // Activation row stride: roundup16(dim) + 4 floats (16-byte aligned rows, 4 mod 8: with the
 // chunk swizzle of fl_kernels.hip (fl_swz) the b128 / b32 MFMA operand patterns are
 // bank-conflict free).
-inline int fl_pick_ld(int dim) { return ((dim + 15) & ~15) + 4; }
+constexpr int fl_pick_ld(int dim) { return ((dim + 15) & ~15) + 4; }
 
 // dims[0..L]: features, hidden sizes, classes.  Fills the dense / image offsets and the fp32
 // kernels' LDS layout (floats) for R rows per workgroup.
-inline void fl_build_fp32_layout(const int* dims, int L, int R, MLPDesc* d) {
-    std::memset(d, 0, sizeof(*d));
+constexpr void fl_build_fp32_layout(const int* dims, int L, int R, MLPDesc* d) {
+    *d = MLPDesc{};
     d->L = L;
     int off = 0;
     for (int l = 0; l <= L; ++l) d->dim[l] = dims[l];
@@ -65,8 +65,8 @@ inline void fl_build_fp32_layout(const int* dims, int L, int R, MLPDesc* d) {
 // FL_LAG_SPR R/16 waves -- FL_LAG_SPR per 16 rows -- score while the others train; and the LDS holds the
 // partials beside the layout.  Otherwise the scoring pass runs before the training pass on the
 // whole workgroup.
-inline int fl_lag_reg_static_bytes(int R) { return (R / 16) * ((FL_LAG_SPR - 1) * FL_LAG_PARTS * 16 * 16 + 16); }
-inline bool fl_lag_reg_ok(const MLPDesc& d, const MLPDescB& e, int R) {
+constexpr int fl_lag_reg_static_bytes(int R) { return (R / 16) * ((FL_LAG_SPR - 1) * FL_LAG_PARTS * 16 * 16 + 16); }
+constexpr bool fl_lag_reg_ok(const MLPDesc& d, const MLPDescB& e, int R) {
     const int L = d.L, C = d.dim[L];
     const int nw = FL_WAVES - FL_LAG_SPR * (R / 16);
     if ((R != 16 && R != 32) || nw < 1 || (L != 2 && L != 3) || C > FL_LAG_MAX_C) return false;
@@ -83,9 +83,8 @@ inline bool fl_lag_reg_ok(const MLPDesc& d, const MLPDescB& e, int R) {
 
 // bf16 LDS layouts (fl_common.h MLPDescB), byte offsets, 16-byte aligned pieces: `e` for the
 // train kernel, `ev` for the evaluation kernels (forward pass only), at bank layout `level`.
-inline void fl_build_bf16_layout_level(const MLPDesc& d, int R, int level, MLPDescB* e_out, MLPDescB* ev_out) {
-    MLPDescB e, ev;
-    std::memset(&e, 0, sizeof(e));
+constexpr void fl_build_bf16_layout_level(const MLPDesc& d, int R, int level, MLPDescB* e_out, MLPDescB* ev_out) {
+    MLPDescB e{}, ev{};
     const int L = d.L;
     e.level = level;
     e.wgap = level == 2 ? 128 : 0;
@@ -155,9 +154,65 @@ inline void fl_build_bf16_layout_level(const MLPDesc& d, int R, int level, MLPDe
 
 // The most conflict-free level whose train and evaluation layouts fit the CU's LDS (level 0
 // when none fits: the engine then refuses this R).
-inline void fl_build_bf16_layout(const MLPDesc& d, int R, MLPDescB* e_out, MLPDescB* ev_out) {
+constexpr void fl_build_bf16_layout(const MLPDesc& d, int R, MLPDescB* e_out, MLPDescB* ev_out) {
     for (int level = 2; level >= 0; --level) {
         fl_build_bf16_layout_level(d, R, level, e_out, ev_out);
         if (std::max(e_out->lds_bytes, ev_out->lds_bytes) <= (int)FL_LDS_DYNAMIC_MAX) return;
     }
 }
+
+// The reference shape -- BASELINE's 14-50-200-2 income MLP -- with its layouts at R rows per
+// workgroup as constants, from the functions above: what the engine computes at run time for this
+// shape, evaluated by the compiler.  The shape-specialised train kernels take their strides, offsets
+// and trip counts from here and no descriptor arguments; a launcher may pick them only for run-time
+// descriptors that are byte-equal to these (fl_ref_shape_match; both structs are all int, no padding).
+struct FlRefLayouts {
+    MLPDesc d;
+    MLPDescB e, ev;
+};
+constexpr FlRefLayouts fl_ref_layouts(int R) {
+    constexpr int dims[4] = {14, 50, 200, 2};
+    FlRefLayouts s{};
+    fl_build_fp32_layout(dims, 3, R, &s.d);
+    fl_build_bf16_layout(s.d, R, &s.e, &s.ev);
+    return s;
+}
+template <int R>
+struct FlRefShape {
+    static constexpr FlRefLayouts all = fl_ref_layouts(R);
+    static constexpr MLPDesc d = all.d;
+    static constexpr MLPDescB e = all.e, ev = all.ev;
+};
+template <int R>
+inline bool fl_ref_shape_match(const MLPDesc& d, const MLPDescB& e) {
+    const MLPDesc rd = FlRefShape<R>::d;  // copies: the comparison needs no definition of the members
+    const MLPDescB re = FlRefShape<R>::e;
+    return std::memcmp(&d, &rd, sizeof(d)) == 0 && std::memcmp(&e, &re, sizeof(e)) == 0;
+}
+
+// Shape policies of the train kernels' device functions (template parameter SP): where a function
+// takes its descriptors from.  FlShapeDyn: the by-value kernel arguments, as passed.  FlShapeRef<R>:
+// the reference shape's constants -- the arguments are ignored, every stride, offset and trip count
+// folds at compile time (kStatic: the functions then also unroll their layer, K and tile loops).
+// A function binds its descriptors with FL_SHAPE_D / FL_SHAPE_E (name, argument): a reference bound
+// by a constant-condition select -- under FlShapeDyn to the argument itself, exactly as without a
+// policy; under FlShapeRef to a function-local constexpr copy of the constants, which the compiler
+// folds (a load from the class-scope object is not folded in device code: such objects are
+// constant-memory symbols the host may overwrite).
+struct FlShapeDyn {
+    static constexpr bool kStatic = false;
+    static constexpr const MLPDesc* pd = nullptr;
+    static constexpr const MLPDescB* pe = nullptr;
+};
+template <int R>
+struct FlShapeRef {
+    static constexpr bool kStatic = true;
+    static constexpr const MLPDesc* pd = &FlRefShape<R>::d;
+    static constexpr const MLPDescB* pe = &FlRefShape<R>::e;
+};
+#define FL_SHAPE_D(SP, name, arg)                                          \
+    constexpr MLPDesc name##_const = SP::kStatic ? *SP::pd : MLPDesc{};    \
+    const MLPDesc& name = SP::kStatic ? name##_const : (arg)
+#define FL_SHAPE_E(SP, name, arg)                                          \
+    constexpr MLPDescB name##_const = SP::kStatic ? *SP::pe : MLPDescB{};  \
+    const MLPDescB& name = SP::kStatic ? name##_const : (arg)

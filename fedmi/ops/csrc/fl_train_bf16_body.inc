@@ -1,8 +1,10 @@
 // Body of the bf16 train kernel (fl_kernels_bf16.hip), included verbatim by its two entry
 // points -- fl_train_bf16_kernel (arguments = kernel arguments) and fl_train_bf16_batch_kernel
 // (the same names bound from the FLTrialDesc table row of blockIdx.y) -- so the single-engine
-// kernel compiles to exactly the code it had before trial batches existed.  In scope: RT, LAG
-// (the FL_EVAL_LAGGED scoring pass compiled in), d, e, c, b, pg, st_in, st_out, local_step,
+// kernel compiles to exactly the code it had before trial batches existed -- and by
+// fl_train_bf16_spec_kernel (fl_train_bf16_spec.hip), where d and e are compile-time constants.  In
+// scope: RT, LAG (the FL_EVAL_LAGGED scoring pass compiled in), SP (the shape policy, fl_layout.h:
+// FlShapeDyn = d and e are the kernel arguments), d, e, c, b, pg, st_in, st_out, local_step,
 // stage_local, mode, cm_out, fold_mask.  LAG: 0 no lagged scoring, 1 scoring pass before the
 // training pass, 2 scoring in registers on the last FL_LAG_SPR RT waves beside it (score_out),
 // 3 the same scoring on workgroups of its own (score_block_bf16): blocks [n_slabs, 2 n_slabs) of
@@ -80,10 +82,10 @@
     static_assert(!(LAGT == 1 && PLAIN), "the serial scoring pass stages the split image");
     ScorePre spre;
     if (LAGT == 2 && lagged) {
-        if (!scorer) stage_params_rows_bf16<RT, NT, PLAIN>(e, img, b.X, c.n_rows, d.dim[0], row0, lds);
+        if (!scorer) stage_params_rows_bf16<RT, NT, PLAIN, SP>(e, img, b.X, c.n_rows, d.dim[0], row0, lds);
         else score_prefetch<RT>(d, e, b, spre);
     } else {
-        stage_params_rows_bf16<RT, FL_THREADS, PLAIN>(e, (LAGT == 1 && lagged) ? b.pk_local : img, b.X, c.n_rows,
+        stage_params_rows_bf16<RT, FL_THREADS, PLAIN, SP>(e, (LAGT == 1 && lagged) ? b.pk_local : img, b.X, c.n_rows,
                                                       d.dim[0], row0, lds);
     }
     FL_STAMP(8);
@@ -106,14 +108,14 @@
     // the forward pass (inlined, so the prefetched weights stay in registers across it)
     if constexpr (LAGT == 2) {
         const int wave = threadIdx.x >> 6;
-        if (!lagged) forward_block_bf16<RT, false, PLAIN>(d, e, lds, b.dbg);
+        if (!lagged) forward_block_bf16<RT, false, PLAIN, SP>(d, e, lds, b.dbg);
         else if (scorer) {
             const int sw = wave - (FL_WAVES - FL_LAG_SPR * RT);
             score_in_lds<RT>(d, e, b, lds, sw, spre, sin);
             score_out<RT>(d, e, c, b, cm_s, sw, row0, ysc, sin,
                           lag_parts + (sw / FL_LAG_SPR) * (FL_LAG_SPR - 1) * FL_LAG_PARTS * 16, lag_ready + sw / FL_LAG_SPR);
         }
-        else forward_block_bf16<RT, true, PLAIN>(d, e, lds, b.dbg, &fwd_done);
+        else forward_block_bf16<RT, true, PLAIN, SP>(d, e, lds, b.dbg, &fwd_done);
     } else {
     ParamRegs pr;
     if (lagged) params_load(e, img, pr);
@@ -135,7 +137,7 @@
             params_store(e, img, pr, lds);
             lds_barrier();
         }
-        forward_block_bf16<RT, false, PLAIN>(d, e, lds, b.dbg);
+        forward_block_bf16<RT, false, PLAIN, SP>(d, e, lds, b.dbg);
     }
     }
     FL_STAMP(2);
@@ -217,17 +219,18 @@
     // phase writes only D_{l-1} and the slab (separate buffers), so the wgrad tiles of layer l
     // overlap the next layer's work instead of holding it at a barrier.
     int dgrad_target = 0;
+#pragma unroll SP::kStatic ? FL_MAX_LAYERS : 1  // static shape: one copy per layer, constants throughout
     for (int l = L - 1; l >= 0; --l) {
-        const int nw = wgrad_waves_bf16(e, l);
-        if (c.slab_f16) wgrad_layer_bf16<RT, true>(d, e, l, lds, slab, nw);
-        else wgrad_layer_bf16<RT, false>(d, e, l, lds, slab, nw);
+        const int nw = wgrad_waves_bf16<SP>(e, l);
+        if (c.slab_f16) wgrad_layer_bf16<RT, true, SP>(d, e, l, lds, slab, nw);
+        else wgrad_layer_bf16<RT, false, SP>(d, e, l, lds, slab, nw);
 #ifdef FL_STAMP_FINE  // profiling builds only (tools/probes/stamps_fine.py): wgrad / dgrad split
         if (l == L - 2) FL_STAMP(7);
         if (l == L - 1) FL_STAMP(14);
         if (l == L - 2 && b.dbg != nullptr && threadIdx.x == 64 * (FL_WAVES - 1))  // last wave: dgrad start
             b.dbg[blockIdx.x * 16 + 11] = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (l > 0) dgrad_layer_bf16<RT, LAGT == 2>(d, e, l, lds);
+        if (l > 0) dgrad_layer_bf16<RT, LAGT == 2, SP>(d, e, l, lds);
 #ifdef FL_STAMP_FINE
         if (l == L - 2) FL_STAMP(13);
         if (l == L - 2 && b.dbg != nullptr && threadIdx.x == 64 * (FL_WAVES - 1))  // last wave: dgrad end

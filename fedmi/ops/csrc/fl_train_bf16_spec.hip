@@ -1,0 +1,44 @@
+// Shape-specialised bf16 train kernel for the reference 14-50-200-2 MLP, in a translation unit of
+// its own so the generic kernels' code generation is untouched (as fl_adam_local.hip).  The body and
+// the device functions are the generic kernel's (fl_train_bf16_body.inc, fl_kernels_bf16.hip) under
+// the static shape policy FlShapeRef<R> (fl_layout.h): the model shape and the LDS layout are the
+// compiler-evaluated constants of FlRefShape<R> instead of the MLPDesc / MLPDescB kernel arguments
+// (384 bytes less per launch, no descriptor loads between the phases), and the layer, K and tile
+// loops are unrolled with constant trip counts and immediate LDS offsets.  Same MFMAs in the same
+// order into the same accumulators, same epilogues and slab stores: results are bitwise the generic
+// kernel's (tests/test_shape_spec.py).  fl_launch_train_bf16 picks it only for run-time
+// descriptors that are byte-equal to the constants.
+#define FL_BF16_DEVICE_ONLY
+#include "fl_kernels_bf16.hip"
+
+template <int RT, int LAG, bool PLAIN>
+__global__ void __launch_bounds__(FL_THREADS)
+fl_train_bf16_spec_kernel(FLConfig c, FLBuffers b, const float* __restrict__ pg, const FLState* __restrict__ st_in,
+                          FLState* __restrict__ st_out, int local_step, int stage_local, int mode,
+                          float* __restrict__ cm_out, int fold_mask) {
+    using SP = FlShapeRef<RT * 16>;
+    constexpr MLPDesc d = FlRefShape<RT * 16>::d;  // (local copies: folded, fl_layout.h FL_SHAPE_D)
+    constexpr MLPDescB e = FlRefShape<RT * 16>::e;
+#include "fl_train_bf16_body.inc"
+}
+
+// One client, R = 32, split-bf16 forward, no lagged scoring: the round bench.py's headline times.
+bool fl_train_bf16_spec_ok(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, int mode) {
+    return c.R == 32 && mode != FL_EVAL_LAGGED && !c.plain_fwd && fl_ref_shape_match<32>(d, e);
+}
+
+hipError_t fl_launch_train_bf16_spec(const FLConfig& c, const FLBuffers& b, const float* pg, const FLState* si,
+                                     FLState* so, int ls, hipStream_t s, bool stage_local, int mode, float* cm_out,
+                                     int fold_mask) {
+    if (c.R != 32 || mode == FL_EVAL_LAGGED || c.plain_fwd) return hipErrorInvalidValue;
+    if (mode == FL_EVAL_FUSED && cm_out == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((fl_train_bf16_spec_kernel<2, 0, false>), dim3(c.n_slabs), dim3(FL_THREADS),
+                       (size_t)FlRefShape<32>::e.lds_bytes, s, c, b, pg, si, so, ls, stage_local ? 1 : 0, mode, cm_out,
+                       fold_mask);
+    return hipGetLastError();
+}
+
+hipError_t fl_set_lds_limit_bf16_spec(size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(fl_train_bf16_spec_kernel<2, 0, false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}

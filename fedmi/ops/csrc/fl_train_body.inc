@@ -1,6 +1,7 @@
 // Body of the fp32 train kernel (fl_kernels.hip), included verbatim by fl_train_kernel and
-// fl_train_batch_kernel (see fl_train_bf16_body.inc).  In scope: RT, d, c, b, pg, st_in, st_out,
-// local_step, mode, cm_out, fold_mask.
+// fl_train_batch_kernel (see fl_train_bf16_body.inc) and by fl_train_spec_kernel (fl_train_spec.hip:
+// d is a compile-time constant).  In scope: RT, SP (the shape policy, fl_layout.h), d, c, b, pg,
+// st_in, st_out, local_step, mode, cm_out, fold_mask.
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ FLState S_sh;
     __shared__ int dgrad_done;  // backward: long-chain dgrad waves finished so far (wgrad_waves_fp32)
@@ -40,13 +41,13 @@
     // staging does not depend on the state: it overlaps the finalize above
     // labels are needed only after the forward pass: issue the load now
     const int ylab = (threadIdx.x < R) ? b.y[min(row0 + (int)threadIdx.x, c.n_rows - 1)] : 0;
-    stage_image(d, params, li);
+    stage_image<SP>(d, params, li);
     stage_rows<RT>(b.X, c.n_rows, d.dim[0], row0, acts + d.act_off[0], d.ld[0]);
     lds_barrier();
     FL_STAMP(1);
     if (!S_sh.live) return;
     float* slab = b.slab + (size_t)blockIdx.x * c.slab_stride;
-    forward_block<RT>(d, acts, li, b.dbg);
+    forward_block<RT, SP>(d, acts, li, b.dbg);
     FL_STAMP(2);
     if (b.dbg != nullptr && threadIdx.x == 0) b.dbg[blockIdx.x * 16 + 14] = __builtin_amdgcn_s_memtime();
 
@@ -114,6 +115,7 @@
     // tiles go to the dgrad waves first (from the top), which are free earliest.
     int dgrad_target = 0;
     bool from_top = false;
+#pragma unroll SP::kStatic ? FL_MAX_LAYERS : 1  // static shape: one copy per layer, constants throughout
     for (int l = L - 1; l >= 0; --l) {
         const float* dz = (l == L - 1) ? acts + d.act_off[L] : acts + d.dlt_off[l + 1];
         const float* act = acts + d.act_off[l];
@@ -128,7 +130,7 @@
             b.dbg[blockIdx.x * 16 + 11] = __builtin_amdgcn_s_memrealtime();
 #endif
         if (l > 0)
-            dgrad_layer<RT>(li + d.iw_off[l], fl_ldw(d.dim[l]), d.dim[l], d.dim[l + 1], dz, d.ld[l + 1], act,
+            dgrad_layer<RT, SP::kStatic>(li + d.iw_off[l], fl_ldw(d.dim[l]), d.dim[l], d.dim[l + 1], dz, d.ld[l + 1], act,
                             d.ld[l], acts + d.dlt_off[l]);
 #ifdef FL_STAMP_FINE
         if (l == L - 2 && b.dbg != nullptr && threadIdx.x == 64 * (FL_WAVES - 1))  // last wave: dgrad end
