@@ -1,9 +1,11 @@
 // Adam-kernel helpers shared by the translation units that instantiate the Adam body
 // (fl_adam_body.inc): fl_kernels.hip (general kernel with the in-kernel xGMI exchange, trial
-// batches) and fl_adam_local.hip (rounds without an in-kernel exchange).
+// batches), fl_adam_local.hip (rounds without an in-kernel exchange) and fl_adam_spec.hip (those
+// rounds for the reference shape, one client).
 #pragma once
 #include "fl_common.h"
 #include "fl_device.h"
+#include "fl_adam_map.h"
 
 // Slab reduction + Adam + StepLR + FedAvg pre-scale.  Block = 16 waves x 64 DENSE
 // parameters: wave w sums slab rows w, w+16, ... of its 64 columns with 16 rows in flight
@@ -67,11 +69,13 @@ __device__ __forceinline__ void pack_store(char* img, int pk, bool is_bias, int 
 // Adam step of one parameter (wave 0 lane of fl_adam_kernel) from the block's partial sums.
 // `p`, `m`, `v`, `anc`: the parameter, its Adam moments and its anchor value, loaded by the
 // caller at the start of the kernel (their latency hides behind the slab loads).  Returns the
-// FedAvg contribution p * scale (also stored into `comm` on the last local step).
+// FedAvg contribution p * scale (also stored into `comm` on the last local step).  `sched_pre` (may
+// be null): the step's two sched entries, fetched by the caller ahead of the call.
 __device__ __forceinline__ float adam_update(const FLConfig& c, const FLBuffers& b, float* __restrict__ comm,
                                             const FLState& S, int local_step, int last_local_step, int pack, int j,
                                             int pk, bool is_bias, int wlo_delta, float (*part)[64], int lane, float p,
-                                            float m, float v, float anc, float scale) {
+                                            float m, float v, float anc, float scale,
+                                            const float* sched_pre = nullptr) {
     if (b.undo != nullptr && local_step == 0) {
         // a late fold may discard this round: keep the parameter's pre-round state (FLBuffers::undo)
         b.undo[j] = p;
@@ -86,14 +90,16 @@ __device__ __forceinline__ float adam_update(const FLConfig& c, const FLBuffers&
 #pragma unroll
         for (int w = 0; w < ADAM_CANON; ++w) g += part[w][lane];
         if (c.slab_f16) g *= c.inv_n;  // fp16 slab: partial sums of the unscaled gradient
-        if (c.weight_decay != 0.f) g += c.weight_decay * p;
-        if (c.prox_mu != 0.f) g += c.prox_mu * (p - anc);
+        // (explicit fused multiply-adds: left to the compiler's contraction, g * inv_n + wd * p comes
+        // out as fma(wd, p, g * inv_n) in one kernel and as a sum of two rounded products in another)
+        if (c.weight_decay != 0.f) g = __builtin_fmaf(c.weight_decay, p, g);
+        if (c.prox_mu != 0.f) g = __builtin_fmaf(c.prox_mu, p - anc, g);
         // torch.optim.Adam single-tensor path: scalars in double, rounded to fp32 once;
         // exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
         // p.addcdiv_(m, sqrt(v)/sqrt(bc2) + eps, -lr/bc1).  StepLR steps once per round.
         const int t = S.cur_round * c.local_steps + local_step + 1;
-        const float step_size = b.sched[2 * (t - 1)];
-        const float bc2_sqrt = b.sched[2 * (t - 1) + 1];
+        const float step_size = sched_pre != nullptr ? sched_pre[0] : b.sched[2 * (t - 1)];
+        const float bc2_sqrt = sched_pre != nullptr ? sched_pre[1] : b.sched[2 * (t - 1) + 1];
         m = m + c.omb1 * (g - m);
         v = v * c.beta2f + c.omb2 * g * g;
         const float denom = sqrtf(v) / bc2_sqrt + c.eps;

@@ -3,9 +3,22 @@
 // local_step, e, pack, st_out, fold, tail_a, fold_mask, pa, xchg, afold; macro ADAM_PA_LL: the
 // exchange uses LL chunks (pa.ll != nullptr; a constant in the specialised kernels).  ADAM_BLK: the
 // block's index in the Adam grid (blockIdx.x, or a virtual block of fl_adam_ll_grid_kernel).
+// ADAM_STATIC / ADAM_FINALIZE / ADAM_EARLY: set by the shape-specialised kernel (fl_adam_spec.hip).
 #ifndef ADAM_BLK
 #define ADAM_BLK blockIdx.x
 #define ADAM_BLK_DEFAULTED
+#endif
+#ifndef ADAM_STATIC  // the descriptors d / e are compile-time constants (fl_adam_spec.hip)
+#define ADAM_STATIC false
+#define ADAM_STATIC_DEFAULTED
+#endif
+#ifndef ADAM_FINALIZE  // the metric fold of round_state (fl_adam_spec.hip: out of line)
+#define ADAM_FINALIZE(S0, hist) finalize_state(d, c, b, anchor, S0, hist, fold_mask)
+#define ADAM_FINALIZE_DEFAULTED
+#endif
+#ifndef ADAM_EARLY  // 1: wave 0 loads the state on entry and its Adam scalars with the FedAvg weight (fl_adam_spec.hip)
+#define ADAM_EARLY 0
+#define ADAM_EARLY_DEFAULTED
 #endif
 #ifndef ADAM_PA_RSAG  // weight chunks by reduce-scatter + all-gather on the LL ring (peer_device.h peer_rsag)
 #define ADAM_PA_RSAG false
@@ -18,6 +31,22 @@
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float sc0 = 0.f;  // parameter blocks: this step's schedule entry (rtab), read by round_state
     FL_STAMP(0);
+#if ADAM_EARLY
+    // The chain state -> round -> schedule entries is two dependent trips to memory on wave 0, the
+    // wave that applies the update: the state load goes out first of all, and the step's Adam
+    // scalars (sched) are fetched with the FedAvg weight (rtab) as soon as the round is known,
+    // not after the block's barrier.
+    // Wave 0 only, like its one reader round_state.  No initialiser, and the address through a
+    // per-lane zero the compiler cannot see through: it moves a uniform value it has to merge or
+    // knows to be uniform into scalar registers where it is loaded, and waits for the load there.
+    FLState S_early;
+    if (wave == 0) {
+        int lane_zero;
+        asm("v_mov_b32 %0, 0" : "=v"(lane_zero));
+        S_early = *reinterpret_cast<const FLState*>(reinterpret_cast<const char*>(st) + lane_zero);
+    }
+    float sched_pre[2] = {0.f, 0.f};
+#endif
     const unsigned target = st->calls + 1;  // call index of this kernel's exchanges
     // lag region A through LL slots (peer_device.h) when it fits one chunk's 64 positions:
     // every rank pushes its whole region (zeros outside its own segment), receivers sum in rank
@@ -34,13 +63,24 @@
     // exchanged right here (chunk ADAM_CHUNK_LAG), so the live decision is taken in time.
     auto round_state = [&]() {
         if (wave != 0) return;
+#if ADAM_EARLY
+        FLState S0 = S_early;
+#else
         FLState S0 = *st;
+#endif
         if (ADAM_BLK != 0) {
             // the round this step belongs to whenever it is live: the folded state's next round,
             // or the running one (loaded here, after the slab loads were issued, not in front of
             // them: it depends on the state load)
             const int rg = fold ? S0.next_round : S0.cur_round;
             sc0 = b.rtab[4 * (size_t)min(max(rg, 0), c.max_rounds - 1)];
+#if ADAM_EARLY
+            // a live step's slot is t - 1 = cur_round * local_steps + local_step with cur_round = rg
+            // (adam_update; the fold leaves next_round as it is); the clamp keeps a dead one in range
+            const size_t slot = (size_t)min(max(rg, 0), c.max_rounds - 1) * c.local_steps + local_step;
+            sched_pre[0] = b.sched[2 * slot];
+            sched_pre[1] = b.sched[2 * slot + 1];
+#endif
         }
         if (fold) {
             const bool need = ADAM_BLK == 0 || fold_may_stop(c, S0);
@@ -57,7 +97,7 @@
                     S0 = fold_round(d, c, b, lag_s, S0.next_round - 1, S0, ADAM_BLK == 0);
                 }
             } else if (need) {
-                S0 = finalize_state(d, c, b, anchor, S0, ADAM_BLK == 0, fold_mask);
+                S0 = ADAM_FINALIZE(S0, ADAM_BLK == 0);
             }
             if (lane == 0) {
                 // a stop triggered before the round that ran last (fold of region A one round
@@ -190,30 +230,14 @@
     const int di = pblk * 64 + lane;  // dense index
     const bool valid = di < d.P;
     // dense index -> image index (and, in bf16 mode, -> packed bf16 LDS-layout position), on
-    // wave 0 (the update runs there) from the layer's offsets gathered by compile-time-indexed
-    // selects: a per-lane index into the descriptors reads them from memory, a dependent round
-    // trip in front of the wave's slab loads
+    // wave 0 (the update runs there): fl_adam_map.h, shared with the host
     int j = 0, pk = 0;
     bool is_bias = false;
     if (wave == 0 && valid) {
-        int K = d.dim[0], wo = d.w_off[0], bo = d.b_off[0], iwo = d.iw_off[0], ibo = d.ib_off[0];
-        int ewo = e.w_off[0], ebo = e.bias_off[0], eldw = e.ldw[0];
-#pragma unroll
-        for (int t = 1; t < FL_MAX_LAYERS; ++t)
-            if (t < d.L && di >= d.w_off[t]) {
-                K = d.dim[t]; wo = d.w_off[t]; bo = d.b_off[t]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-                ewo = e.w_off[t]; ebo = e.bias_off[t]; eldw = e.ldw[t];
-            }
-        if (di < bo) {
-            const int q = di - wo;
-            const int n = q / K, k = q - n * K;
-            j = iwo + n * fl_ldw(K) + (k ^ fl_swz(n));  // (swizzled image, fl_common.h)
-            pk = ewo - e.param_off + fl_wrow(n, eldw, e.wgap) + ((((k >> 3) ^ fl_wswz(n, e.wxor)) << 4) | ((k & 7) << 1));
-        } else {
-            j = ibo + (di - bo);
-            pk = ebo - e.param_off + (di - bo) * 4;
-            is_bias = true;
-        }
+        const FlAdamPos ps = fl_adam_pos<ADAM_STATIC>(d, e, di);
+        j = ps.j;
+        pk = ps.pk;
+        is_bias = ps.is_bias;
     }
     // past the stop: rank 0 contributes the (identical) global weights, others 0, so the
     // all-reduce returns them bit-exactly.  Classic rounds know the state on entry and skip
@@ -328,8 +352,13 @@
             if (last_local_step && !(c.rank == 0 && S.late)) comm[j] = contrib;
             if (S.late && b.undo != nullptr) undo_restore(c, b, pack, j, pk, is_bias, e.wlo_delta);
         } else {
+#if ADAM_EARLY
+            contrib = adam_update(c, b, comm, S, local_step, last_local_step, pack, j, pk, is_bias, e.wlo_delta, part,
+                                  lane, p0, m0, v0, a0, sc0, sched_pre);
+#else
             contrib = adam_update(c, b, comm, S, local_step, last_local_step, pack, j, pk, is_bias, e.wlo_delta, part,
                                   lane, p0, m0, v0, a0, sc0);
+#endif
         }
     }
     FL_STAMP(5);
@@ -368,4 +397,16 @@
 #ifdef ADAM_PA_RSAG_DEFAULTED
 #undef ADAM_PA_RSAG
 #undef ADAM_PA_RSAG_DEFAULTED
+#endif
+#ifdef ADAM_EARLY_DEFAULTED
+#undef ADAM_EARLY
+#undef ADAM_EARLY_DEFAULTED
+#endif
+#ifdef ADAM_STATIC_DEFAULTED
+#undef ADAM_STATIC
+#undef ADAM_STATIC_DEFAULTED
+#endif
+#ifdef ADAM_FINALIZE_DEFAULTED
+#undef ADAM_FINALIZE
+#undef ADAM_FINALIZE_DEFAULTED
 #endif

@@ -375,7 +375,40 @@ hipError_t fl_launch_adam(const MLPDesc& d, const FLConfig& c, const FLBuffers& 
                           const FLState* st, int local_step, hipStream_t s,
                           const MLPDescB* e = nullptr, FLState* st_out = nullptr, int fold = 0,
                           int tail_a = 0, int fold_mask = FL_FOLD_B, const PeerArgs* peer = nullptr, int wx = 0,
-                          int afold = 0);
+                          int afold = 0, bool adam_spec = false);
+// (fl_adam_spec.hip: the Adam kernel specialised for the reference shape at R = 32, one client, no
+// exchange, no lag region, no undo buffer; `adam_spec` above lets fl_launch_adam pick it where
+// fl_adam_spec_ok holds.)  Its only kernel argument: what that kernel reads of FLConfig / FLBuffers
+// and of the launch -- pointers first, then the launch and optimizer scalars, the early-stop
+// scalars of the (out-of-line) metric fold last.  224 bytes, against 1016 of the generic kernel.
+struct FlAdamSpecArgs {
+    const float* pin;
+    const float* anchor;
+    float* comm;
+    const FLState* st;
+    float* slab;
+    float* local;
+    float* m;
+    float* v;
+    const float* sched;
+    const float* rtab;
+    char* pk_local;
+    int* sat;
+    unsigned long long* dbg;
+    FLState* st_out;
+    double* hist_global;
+    double* hist_rank;
+    float* hist_loss;
+    int n_slabs, slab_stride, local_steps, max_rounds;
+    int local_step, fold, tail_a, fold_mask;
+    float inv_n, omb1, omb2, beta2f, eps, weight_decay, prox_mu;
+    int es_enabled, patience, metric_mode;
+    double atol, rtol;
+};
+bool fl_adam_spec_ok(const MLPDesc& d, const MLPDescB* e, const FLConfig& c, const FLBuffers& b);
+hipError_t fl_launch_adam_spec(const FLConfig& c, const FLBuffers& b, const float* pin, const float* anchor,
+                               float* comm, const FLState* st, int local_step, int pack, FLState* st_out, int fold,
+                               int tail_a, int fold_mask, hipStream_t s);
 // (fl_adam_local.hip: the Adam kernel without the in-kernel exchange; fl_launch_adam picks it)
 hipError_t fl_launch_adam_local(const MLPDesc& d, const FLConfig& c, const FLBuffers& b, const float* pin,
                                 const float* anchor, float* comm, const FLState* st, int local_step,

@@ -362,6 +362,10 @@ class FLEngine {
         {
             const char* sp = std::getenv("FEDMI_SHAPE_SPEC");
             shape_spec_on_ = !(sp != nullptr && sp[0] == '0');
+            // the Adam kernel of the same shape (fl_adam_spec.hip): under the same switch, and
+            // FEDMI_ADAM_SPEC=0 turns it off alone; reported as layout()["adam_spec"]
+            const char* ap = std::getenv("FEDMI_ADAM_SPEC");
+            adam_spec_on_ = shape_spec_on_ && !(ap != nullptr && ap[0] == '0');
         }
 
         b_.X = as_ptr<const float>(bufs["X"].cast<uintptr_t>());
@@ -740,6 +744,7 @@ class FLEngine {
         // the train kernel of classic / fused rounds is the reference shape's specialised one
         o["shape_spec"] = shape_spec_on_ && (dtype_ == 1 ? fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED)
                                                          : fl_train_spec_ok(d_, c_, FL_EVAL_FUSED));
+        o["adam_spec"] = adam_spec_ok();  // the Adam kernel of those rounds is the specialised one
         o["eval_fedavg"] = peer_ != nullptr && !tr_.fused && tr_.eval_fedavg_fits;
         o["dtype"] = dtype_;
         o["slab_stride"] = c_.slab_stride;
@@ -822,7 +827,7 @@ class FLEngine {
                 PeerArgs pa;
                 if (m.peer) pa = peer_->args(m.par, pbuf_[m.par]);
                 HIP_CHECK(fl_launch_adam(d_, c_, b_, F(0), F(1), F(2), S(3), i[0], s, eb, S(4), i[1], i[2], i[3],
-                                         m.peer ? &pa : nullptr, (m.peer >> 1) & 1, (m.peer >> 2) & 1));
+                                         m.peer ? &pa : nullptr, (m.peer >> 1) & 1, (m.peer >> 2) & 1, adam_spec_allowed()));
                 break;
             }
             case FLLaunchRec::EVAL:
@@ -893,6 +898,14 @@ class FLEngine {
     MLPDescB ev_;  // evaluation-only layout of e_ (no delta buffers)
     int dtype_ = 0;  // 0 = fp32 MFMA, 1 = bf16 MFMA (fp32 accumulate / master weights)
     bool shape_spec_on_ = true;  // FEDMI_SHAPE_SPEC != 0: launchers may pick shape-specialised kernels
+    bool adam_spec_on_ = true;   // ... and FEDMI_ADAM_SPEC != 0: the Adam launcher too
+    // The engine allows the specialised Adam kernel: no peer plane, and the round's output is the
+    // Adam kernel's own (no DP clip, no server step after it); the launcher checks the shape, the
+    // client count, the lag region and the undo buffer per launch (fl_adam_spec_ok).
+    bool adam_spec_allowed() const { return adam_spec_on_ && peer_ == nullptr && !tr_.dp_on && !tr_.server_on; }
+    bool adam_spec_ok() const {
+        return adam_spec_allowed() && fl_adam_spec_ok(d_, dtype_ == 1 ? &e_ : nullptr, c_, b_);
+    }
     char* pk_ = nullptr;
     float* lagbuf_ = nullptr;  // FL_EVAL_LAGGED count + loss carry-over
     long long comm_len_ = 0;   // floats of a comm buffer: image + tails (+ lag region)
