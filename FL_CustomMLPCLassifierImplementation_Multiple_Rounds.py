@@ -74,6 +74,13 @@ def parse_args(argv=None):
                          "coordinate-wise, unweighted, Byzantine-robust (Yin et al. 2018)")
     ap.add_argument("--trim-ratio", type=float, default=0.1,
                     help="--aggregator trimmed_mean: fraction beta cut at EACH end, in [0, 0.5)")
+    ap.add_argument("--compress", choices=["none", "topk", "sign"], default="none",
+                    help="compress every client's round update with error feedback: topk = the largest "
+                         "--compress-ratio of its entries, sign = one bit per entry and a scale (a simulated uplink: "
+                         "the exchange stays dense; --jsonl rows carry uplink_bytes)")
+    ap.add_argument("--compress-ratio", type=float, default=0.1, help="--compress topk: fraction of entries kept, in (0, 1]")
+    ap.add_argument("--no-error-feedback", action="store_true",
+                    help="--compress: discard what the compressor drops instead of carrying it to the next round")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -176,6 +183,10 @@ def _aggregator_fields(a) -> dict:
     return dict(aggregator=a.aggregator, trim_ratio=a.trim_ratio)
 
 
+def _compress_fields(a) -> dict:
+    return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback)
+
+
 def _print_privacy(a, rounds: int) -> None:
     """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
     if a.dp_clip > 0.0:
@@ -197,7 +208,7 @@ def main_clients(a, comm):
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
-                       **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a))
+                       **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -212,7 +223,8 @@ def main_clients(a, comm):
     _print_privacy(a, int(h["rounds_run"]))
     if a.jsonl:
         w = JsonlWriter(a.jsonl)
-        w.history(h, clients=a.clients, script="C-clients", aggregation="in-process", wall_s=wall)
+        w.history(h, clients=a.clients, script="C-clients", aggregation="in-process", wall_s=wall,
+                  uplink_bytes=g.clients[0].uplink_bytes())
         w.close()
     comm.close()
     return h
@@ -243,6 +255,13 @@ def main(argv=None):
         aggregator_id(EngineConfig(**_dp_fields(a), **_aggregator_fields(a)))
     except ValueError as e:
         raise SystemExit(f"--aggregator / --trim-ratio: {e}")
+    if a.wide and a.compress != "none":
+        raise SystemExit("--compress is not supported with --wide")
+    try:
+        from fedmi.fl.compress import compress_id
+        compress_id(EngineConfig(**_dp_fields(a), **_compress_fields(a)))
+    except ValueError as e:
+        raise SystemExit(f"--compress / --compress-ratio: {e}")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -262,7 +281,8 @@ def main(argv=None):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, participation=a.participation, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
-                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a))
+                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
+                       **_compress_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,
@@ -301,6 +321,7 @@ def main(argv=None):
         w.history(h, clients=size, script="C", timings=timings,
                   aggregation=getattr(eng, "aggregation", "host"),
                   allreduce_bytes_per_round=4 * comm_floats if size > 1 else 0,
+                  uplink_bytes=eng.uplink_bytes(),
                   wall_s=t_train, samples_per_s_per_client=len(trainer.X_local) * rounds_run / max(t_train, 1e-9))
         w.close()
     if rank == 0:

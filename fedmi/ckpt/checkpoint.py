@@ -136,11 +136,15 @@ def save_checkpoint(path: str, trainer) -> None:
     # server optimizer: every rank holds the same replicated m / v; each client's file carries its copy
     sv = {} if "server_m" not in st else {"server_m": np.asarray(st["server_m"], np.float32),
                                           "server_v": np.asarray(st["server_v"], np.float32)}
+    # compression: the client's own residual (dense order) and its per-round statistic
+    cp = {} if "compress_residual" not in st else {
+        "compress_residual": np.asarray(st["compress_residual"], np.float32),
+        "compress_stat": np.asarray(st["history"]["compress_stat"], np.float32)}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
         {"local": np.asarray(st["local"], np.float32), "exp_avg": np.asarray(st["exp_avg"], np.float32),
          "exp_avg_sq": np.asarray(st["exp_avg_sq"], np.float32),
          # this client's own Adam step count (differs from rounds x local_steps when clients are sampled)
-         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv}, tmp,
+         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv, **cp}, tmp,
         metadata={"round": str(R)}))
     gflat = flat_to_dict(st["global"], eng.dims)
     if eng.rank == 0:
@@ -211,7 +215,10 @@ def resume(path: str, trainer) -> int:
         st["history"]["update_norm"] = np.asarray(c["update_norm"], np.float32)
     if "server_m" in c:
         st["server_m"], st["server_v"] = np.asarray(c["server_m"], np.float32), np.asarray(c["server_v"], np.float32)
-    eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer
+    if "compress_residual" in c:
+        st["compress_residual"] = np.asarray(c["compress_residual"], np.float32)
+        st["history"]["compress_stat"] = np.asarray(c["compress_stat"], np.float32)
+    eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer / compression
     return st["rounds"]
 
 

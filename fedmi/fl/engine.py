@@ -31,6 +31,7 @@ import torch
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
 from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, robust_aggregate_torch
+from .compress import COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
 
@@ -143,6 +144,19 @@ class EngineConfig:
     # WideClient; at most 64 clients.
     aggregator: str = "mean"
     trim_ratio: float = 0.1
+    # Update compression with error feedback (fedmi/fl/compress.py): every sampled client compresses
+    # u = (local - x) + e (x: the image the round trained from, e: its residual) before the exchange and
+    # contributes w (x + C(u)); what C drops stays in e (error_feedback=False: it is discarded).  "topk"
+    # keeps the k = max(1, min(P, ceil(compress_ratio P))) entries of largest |u| (Stich et al. 2018),
+    # "sign" sends copysign(mean |u|, u) (Karimireddy et al. 2019); both are deterministic.  A SIMULATION
+    # of the uplink: the exchange still carries the dense fp32 image, layout()["compress"] /
+    # compress.uplink_bytes report what a real uplink would carry.  "none": off (nothing of a round
+    # changes).  The local model, Adam moments, FedProx anchor and local metrics are untouched; rounds
+    # are classic; history()["compress_stat"] holds the k-th kept magnitude (top-k) / the scale (sign).
+    # Not with dp_clip > 0, trial batches (comm_buffers), fed_sweep or WideClient.
+    compress: str = "none"
+    compress_ratio: float = 0.1
+    error_feedback: bool = True
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -246,9 +260,11 @@ def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, 
 
 
 class _History:
-    def __init__(self, max_rounds: int, world: int, dp: bool = False):
+    def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False):
         # DP engines: this client's pre-clip update norm per round (0: not sampled)
         self.norm = np.zeros(max_rounds, dtype=np.float32) if dp else None
+        # compressing engines: the round's statistic (top-k: k-th kept magnitude; sign: scale; 0: not sampled)
+        self.cstat = np.zeros(max_rounds, dtype=np.float32) if compress else None
         self.glob = np.zeros((max_rounds, 4))
         self.rank = np.zeros((max_rounds, world, 4))
         self.loss = np.zeros(max_rounds, dtype=np.float32)
@@ -268,6 +284,8 @@ class _History:
         }
         if self.norm is not None:
             out["update_norm"] = self.norm[:n].copy()
+        if self.cstat is not None:
+            out["compress_stat"] = self.cstat[:n].copy()
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -282,6 +300,7 @@ class RoundEngineBase:
         self.cfg = cfg
         self.dp = dp_enabled(cfg)
         self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
+        self.compress = compress_id(cfg)   # index in COMPRESSORS; 0 = dense contributions
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
@@ -303,7 +322,8 @@ class RoundEngineBase:
         # robust aggregators are unweighted: the contribution image IS the local model (x 1.0f is exact)
         self.agg_scale = 1.0 if self.robust else float(self.n_local) / float(self.n_total)
         self.tail_stride = self.n_classes * self.n_classes + 1
-        self.hist = _History(cfg.max_rounds, self.world, dp=self.dp)
+        self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress))
+        self.compress_k = compress_k(cfg, self.P)   # entries a contribution transmits (sign, dense: P)
         assert init_flat.shape == (self.P,)
         if self.dp:
             if self.world > 1 and client_sizes is None:
@@ -406,6 +426,8 @@ class RoundEngineBase:
         self.hist.stop_trigger = int(h.get("stop_trigger", -1))
         if self.hist.norm is not None and n and "update_norm" in h:
             self.hist.norm[:n] = np.asarray(h["update_norm"], dtype=np.float32).reshape(n)
+        if self.hist.cstat is not None and n and "compress_stat" in h:
+            self.hist.cstat[:n] = np.asarray(h["compress_stat"], dtype=np.float32).reshape(n)
 
     def _load_dp_seed(self, st: dict) -> None:
         """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
@@ -415,6 +437,26 @@ class RoundEngineBase:
 
     def _set_dp_seed(self, seed: int) -> None:
         self.dp_seed = int(seed)
+
+    def uplink_bytes(self) -> int:
+        """Bytes per round a real uplink would carry for this client's contribution (the exchange
+        itself stays dense: compression is simulated)."""
+        return uplink_bytes(self.cfg.compress, self.compress_k, self.P)
+
+    def _compress_state_in(self, st: dict):
+        """The dense compression residual of a portable state for this engine, or None without
+        compression; a state and an engine that disagree on having one do not match."""
+        has = st.get("compress_residual") is not None
+        if has != bool(self.compress):
+            raise ValueError("checkpoint and engine disagree on compression: the state "
+                             + ("carries" if has else "has no") + " compress_residual, the engine has compress="
+                             + repr(self.cfg.compress))
+        if not self.compress:
+            return None
+        e = np.asarray(st["compress_residual"], np.float32).reshape(-1)
+        if e.shape != (self.P,):
+            raise ValueError(f"compression residual has {e.shape[0]} entries, the model {self.P}")
+        return e
 
     def _server_state_in(self, st: dict):
         """The dense (server_m, server_v) of a portable state for this engine, or None without a
@@ -458,6 +500,9 @@ class TorchRoundEngine(RoundEngineBase):
             # server optimizer state in dense named_parameters() order (v starts at tau^2)
             self.server_m = torch.zeros(self.P, dtype=torch.float32)
             self.server_v = torch.full((self.P,), float(np.float32(cfg.server_tau)) ** 2, dtype=torch.float32)
+        if self.compress:
+            self.compress_residual = torch.zeros(self.P, dtype=torch.float32)   # dense order
+            self._compressed = (-1, None)   # (round, x + C(u)) of the last compressed round
 
     def train_one_epoch(self) -> float:
         """``local_steps`` full-batch Adam steps + one StepLR step (reference C:63-73)."""
@@ -508,7 +553,7 @@ class TorchRoundEngine(RoundEngineBase):
     def step_train(self) -> None:
         r = self.rounds_issued
         self._active = self.rank in self.participants(r)
-        if self.dp:
+        if self.dp or self.compress:
             self._dp_input = self.model.flat.detach().cpu().clone()   # the image the round trains from
         if self._active:
             self._loss = self.train_one_epoch()
@@ -537,6 +582,8 @@ class TorchRoundEngine(RoundEngineBase):
             self.hist.norm[r] = 0.0
             if active:
                 model, noise = self._dp_clip_and_noise(r, model)
+        if self.compress:
+            model = self._compressed_model(model, active)
         if not sampling:
             buf[:self.P] = model * self.agg_scale
             if noise is not None:
@@ -568,12 +615,34 @@ class TorchRoundEngine(RoundEngineBase):
         xi = float(self.dp_sigma[r]) * dp_normals(self.P, r, self.rank, self.dp_seed)
         return local, torch.as_tensor(xi).to(local.dtype)
 
+    def _compressed_model(self, local: torch.Tensor, active: bool) -> torch.Tensor:
+        """x + C((local - x) + e) of the round being issued, in fp32 (fedmi/fl/compress.py); updates the
+        residual and records the round's statistic once per round.  An unsampled client keeps both."""
+        r = self.rounds_issued
+        if self._compressed[0] == r:
+            return self._compressed[1]
+        self.hist.cstat[r] = 0.0
+        out = local
+        if active:
+            x = self._dp_input.to(torch.float32)
+            u = (local.to(torch.float32) - x) + self.compress_residual
+            c, self.compress_residual, stat = compress_torch(u, self.cfg.compress, self.compress_k,
+                                                             bool(self.cfg.error_feedback))
+            self.hist.cstat[r] = stat
+            out = x + c
+        self._compressed = (r, out)
+        return out
+
     def _robust_contribution(self) -> torch.Tensor:
         """Robust aggregators: this client's row of the round's gather, [unscaled local model (zeros
         when not sampled) | per-rank (confusion, loss) tails | 1 when sampled, else 0]."""
         buf = torch.zeros(self.P + self.world * self.tail_stride + 1, dtype=torch.float32)
-        if getattr(self, "_active", True):
-            buf[:self.P] = self.model.flat.detach().cpu()
+        active = getattr(self, "_active", True)
+        model = self.model.flat.detach().cpu()
+        if self.compress:
+            model = self._compressed_model(model, active)
+        if active:
+            buf[:self.P] = model
             buf[-1] = 1.0
         t0 = self.P + self.rank * self.tail_stride
         buf[t0:t0 + self.n_classes ** 2] = torch.as_tensor(self._cm.reshape(-1), dtype=torch.float32)
@@ -707,15 +776,20 @@ class TorchRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
+            **({"compress_residual": self.compress_residual.numpy().copy()} if self.compress else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
         r = int(st["rounds"])
         cfg = self.cfg
         sv = self._server_state_in(st)
+        ce = self._compress_state_in(st)
         if sv is not None:
             self.server_m = torch.as_tensor(sv[0].copy())
             self.server_v = torch.as_tensor(sv[1].copy())
+        if ce is not None:
+            self.compress_residual = torch.as_tensor(ce.copy())
+            self._compressed = (-1, None)
         with torch.no_grad():
             self.model.flat.copy_(torch.as_tensor(np.asarray(st["global"], np.float32)))
         self.global_params = self.model.flat.detach().clone()
@@ -771,6 +845,8 @@ class HipRoundEngine(RoundEngineBase):
         from ..ops import native
         if int(cfg.local_steps) > MAX_LOCAL_STEPS:
             raise ValueError(f"HipRoundEngine: at most {MAX_LOCAL_STEPS} local steps per round (got {cfg.local_steps})")
+        if cfg.compress != "none" and comm_buffers is not None:
+            raise ValueError(f"trial packing (comm_buffers) does not run compression (compress={cfg.compress!r})")
         if cfg.aggregator != "mean" and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
         self.m = native()
@@ -808,9 +884,10 @@ class HipRoundEngine(RoundEngineBase):
         # round run past a stop discarded bit-exactly: FLEngine.late_fold)
         # (differential privacy: classic rounds, see fl_engine.cpp)
         # (robust aggregators: classic rounds aggregated from Python, see _aggregate)
+        # (compression: classic rounds, as with differential privacy)
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
                      and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server
-                     and not self.robust)
+                     and not self.robust and not self.compress)
         comm_len = self.Pimg + self.world * self.tail_stride * (2 if self._lag else 1)
         if comm_buffers is None:
             self.params = [torch.zeros(comm_len, **f32), torch.zeros(comm_len, **f32)]
@@ -877,6 +954,14 @@ class HipRoundEngine(RoundEngineBase):
             ecfg.update({"dp_clip": float(cfg.dp_clip), "dp_noise": float(cfg.dp_noise) > 0.0,
                          "dp_seed": int(self.dp_seed)})
             bufs.update({"dp_sigma": self.dp_sigma_dev.data_ptr(), "dp_norm": self.dp_norm.data_ptr()})
+        if self.compress:
+            # residual: two image-shaped fp32 halves, round r reads half r & 1 and writes half (r + 1) & 1
+            # (fl_compress.hip); the per-round statistic
+            self.cp_res = torch.zeros(2 * self.Pimg, **f32)
+            self.cp_stat = torch.zeros(mr, dtype=torch.float32, device=dev)
+            ecfg.update({"compress": int(self.compress), "compress_k": int(self.compress_k),
+                         "error_feedback": bool(cfg.error_feedback)})
+            bufs.update({"compress_residual": self.cp_res.data_ptr(), "compress_stat": self.cp_stat.data_ptr()})
         if self.server:
             # server optimizer state: image-shaped fp32 (m = 0; v = tau^2 everywhere, padding included)
             if comm_buffers is not None:
@@ -1120,7 +1205,7 @@ class HipRoundEngine(RoundEngineBase):
         :meth:`profile`, which runs classic phases): the native engine issues them eagerly with
         a hipEvent after every launch behind a gate kernel (FLEngine::trace), so the kernels
         run back to back.  Returns mean us per round by kernel kind (``train``, ``adam``,
-        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``server``), ``round`` and launch counts.  Each
+        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``compress``, ``server``), ``round`` and launch counts.  Each
         interval carries the eager launch + event marker cost: measured on MI355X (bench N = 1,
         profiles/kernel_trace_r5.log) ~1.5 us per kernel over the rocprofv3 kernel durations
         (markers without the system-scope fence; ~3.2 us with it).
@@ -1312,6 +1397,8 @@ class HipRoundEngine(RoundEngineBase):
                     m["loss"].copy_(self.h_loss, non_blocking=True)
                     if self.dp:
                         m["norm"].copy_(self.dp_norm, non_blocking=True)
+                    if self.compress:
+                        m["cstat"].copy_(self.cp_stat, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -1345,7 +1432,8 @@ class HipRoundEngine(RoundEngineBase):
             pin = torch.cuda.is_available()
             mk = lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
             self._mirror = [{"state": mk(self.state[0]), "glob": mk(self.h_global), "rank": mk(self.h_rank),
-                             "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {})}
+                             "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {}),
+                             **({"cstat": mk(self.cp_stat)} if self.compress else {})}
                             for _ in range(2)]
         return self._mirror
 
@@ -1359,6 +1447,8 @@ class HipRoundEngine(RoundEngineBase):
             self.hist.loss[:n] = m["loss"][:n].numpy()
             if self.dp:
                 self.hist.norm[:n] = m["norm"][:n].numpy()
+            if self.compress:
+                self.hist.cstat[:n] = m["cstat"][:n].numpy()
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1387,6 +1477,8 @@ class HipRoundEngine(RoundEngineBase):
             self.hist.loss[:n] = self.h_loss[:n].cpu().numpy()
             if self.dp:
                 self.hist.norm[:n] = self.dp_norm[:n].cpu().numpy()
+            if self.compress:
+                self.hist.cstat[:n] = self.cp_stat[:n].cpu().numpy()
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1431,6 +1523,14 @@ class HipRoundEngine(RoundEngineBase):
         self.stream.synchronize()
         return cm.cpu().numpy().reshape(self.n_classes, self.n_classes).astype(np.int64)
 
+    @property
+    def compress_residual(self) -> np.ndarray:
+        """The compression residual in dense order, as the next live round will read it (after
+        :meth:`sync_history`: the half the last live round wrote)."""
+        self.stream.synchronize()
+        half = int(self.hist.rounds_run) & 1
+        return image_to_dense(self.cp_res[half * self.Pimg:(half + 1) * self.Pimg].cpu().numpy(), self.dims)
+
     def portable_state(self) -> dict:
         self.sync_history()
         r = self.rounds_issued
@@ -1446,6 +1546,7 @@ class HipRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
+            **({"compress_residual": self.compress_residual} if self.compress else {}),
         }
 
     def load_portable_state(self, st: dict) -> None:
@@ -1453,6 +1554,7 @@ class HipRoundEngine(RoundEngineBase):
         if r > self.cfg.max_rounds:
             raise ValueError(f"checkpoint has {r} rounds > max_rounds {self.cfg.max_rounds}")
         sv = self._server_state_in(st)
+        ce = self._compress_state_in(st)
         self.stream.synchronize()
         dev = self.device
         img = lambda a: torch.as_tensor(dense_to_image(np.asarray(a, np.float32), self.dims), device=dev)
@@ -1467,6 +1569,8 @@ class HipRoundEngine(RoundEngineBase):
                 pad = torch.as_tensor(dense_to_image(np.ones(self.P, np.float32), self.dims), device=dev) == 0
                 self.server_v.copy_(torch.where(pad, torch.full_like(self.server_v, float(np.float32(self.cfg.server_tau)) ** 2),
                                                 img(sv[1])))
+            if ce is not None:   # both halves: whichever the next live round reads
+                self.cp_res.copy_(img(ce).repeat(2))
             es = st["es"]
             rec = np.zeros(1, dtype=_STATE_DTYPE)
             rec["next_round"] = r
@@ -1488,6 +1592,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.h_loss[:n].copy_(torch.as_tensor(self.hist.loss[:n], device=dev))
                 if self.dp:
                     self.dp_norm[:n].copy_(torch.as_tensor(self.hist.norm[:n], device=dev))
+                if self.compress:
+                    self.cp_stat[:n].copy_(torch.as_tensor(self.hist.cstat[:n], device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
         self.engine.invalidate()

@@ -42,7 +42,12 @@ class WideClient:
                  micro_batch: int = 131072, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  step_size: int = 30, gamma: float = 0.5, seed: int = 0, dtype: str = "bf16",
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
-                 fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean"):
+                 fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
+                 compress: str = "none"):
+        if compress != "none":
+            # the wide path all-reduces its buckets as they are; it keeps no residual
+            raise ValueError(f"WideClient does not run update compression (compress={compress!r}); "
+                             "use the round engines (EngineConfig.compress)")
         if aggregator != "mean":
             # the wide path all-reduces its buckets; nothing gathers the clients' models
             raise ValueError(f"WideClient does not run a robust aggregator (aggregator={aggregator!r}); "

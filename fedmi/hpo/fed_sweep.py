@@ -88,6 +88,9 @@ class FedTrialGroup:
         if base.server_opt != "none":
             # the trials share launches and one collective; a server step per trial is not batched
             raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")
+        if base.compress != "none":
+            # the trials share launches; a residual and a selection per trial is not batched
+            raise ValueError("fed_sweep does not run compressed trials (compress)")
         if base.aggregator != "mean":
             # the trials share one SUM all-reduce; a gather and a selection per trial is not batched
             raise ValueError("fed_sweep does not run robust-aggregator trials (aggregator)")

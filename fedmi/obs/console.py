@@ -63,6 +63,9 @@ class JsonlWriter:
         for r in range(hist["rounds_run"]):
             # (DP engines: this client's pre-clip update norm of the round, 0 when not sampled)
             norm = {"update_norm": float(hist["update_norm"][r])} if "update_norm" in hist else {}
+            # (compressing engines: the round's statistic -- k-th kept magnitude / sign scale)
+            if "compress_stat" in hist:
+                norm["compress_stat"] = float(hist["compress_stat"][r])
             self.write(round=r + 1, **{k: float(hist["global"][r][i]) for i, k in enumerate(METRIC_NAMES)},
                        per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **norm, **extra)
 

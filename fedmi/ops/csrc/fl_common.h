@@ -328,6 +328,26 @@ struct FLServer {
     float* v;            // [Pimg] fp32, caller-owned (adaptive kinds; unused by FL_SERVER_SGD)
 };
 
+// Update compression with error feedback (fl_compress.hip): parameters of the per-round compression
+// kernel, passed to that kernel alone, as FLDp is.  With x the image the round trained from and e the
+// residual, u = (local - x) + e on the P real parameters and the contribution becomes w (x + C(u)):
+//   FL_COMPRESS_TOPK : C keeps the k entries of largest |u| (ties: lower dense index first), e' = u elsewhere
+//   FL_COMPRESS_SIGN : C(u) = copysign(s, u), s = sum|u| / P;                              e' = u - C(u)
+// (Stich et al. 2018; Karimireddy et al. 2019).  The exchange still carries the dense image.
+#define FL_COMPRESS_NONE 0
+#define FL_COMPRESS_TOPK 1
+#define FL_COMPRESS_SIGN 2
+struct FLCompress {
+    int kind;            // FL_COMPRESS_*
+    int k;               // top-k: entries kept, 1 .. P
+    int P;               // dense parameter count (== MLPDesc::P)
+    int error_feedback;  // 1: what C drops is carried in the residual; 0: the residual stays 0
+    int max_rounds;      // entries of stat_hist; rounds past it are not live
+    float* residual;     // [2][Pimg] fp32, caller-owned, zero at start: round r reads half r & 1 and writes
+                         // half (r + 1) & 1 (every workgroup reads the whole old residual, fl_compress.hip)
+    float* stat_hist;    // [max_rounds] top-k: magnitude of the k-th kept entry; sign: s (0: not sampled)
+};
+
 // Robust aggregation (fl_robust.hip; Yin et al. 2018): parameters of the per-round coordinate-wise
 // median / trimmed mean over K clients' buffers, passed to that kernel alone.  Of the round's K_r
 // sampled clients (rtab mask) the fl_robust_trim lowest and highest values of every coordinate are
@@ -425,6 +445,12 @@ hipError_t fl_launch_eval(const MLPDesc& d, const FLConfig& c, const FLBuffers& 
 // first Pimg floats of `comm` from `local` and the round's input image `pg`
 hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, const float* pg, float* comm,
                         const FLState* st, const float* rtab, hipStream_t s);
+// (fl_compress.hip) compression of the round whose last Adam kernel wrote state `st`: rewrites the
+// real parameters of the first Pimg floats of `comm` from `local`, the round's input image `pg` and
+// the residual.  fl_set_lds_limit_compress: once per model before the first launch (dynamic LDS).
+hipError_t fl_set_lds_limit_compress(const MLPDesc& d);
+hipError_t fl_launch_compress(const MLPDesc& d, const FLCompress& p, const float* local, const float* pg, float* comm,
+                              const FLState* st, const float* rtab, hipStream_t s);
 // (fl_server.hip) server-optimizer step of the round whose state is `st`: `x` = the image the round
 // trained from, `a` = its aggregated image, replaced in place (first Pimg floats only) by the new
 // global image.  `e` / `pk` (bf16 mode, else null): the same launch also writes the packed

@@ -269,13 +269,19 @@ class FLEngine {
         std::memset(&dp_, 0, sizeof(dp_));
         dp_.clip = cfg.contains("dp_clip") ? cfg["dp_clip"].cast<float>() : 0.f;
         tr_.dp_on = dp_.clip > 0.f;
+        std::memset(&cp_, 0, sizeof(cp_));
+        cp_.kind = cfg.contains("compress") ? cfg["compress"].cast<int>() : FL_COMPRESS_NONE;
+        tr_.compress_on = cp_.kind != FL_COMPRESS_NONE;
+        if (tr_.compress_on && tr_.dp_on)
+            throw std::runtime_error("FLEngine: compression does not combine with differential privacy");
         std::memset(&sv_, 0, sizeof(sv_));
         sv_.kind = cfg.contains("server_opt") ? cfg["server_opt"].cast<int>() : FL_SERVER_NONE;
         tr_.server_on = sv_.kind != FL_SERVER_NONE;
         // The round's output is not the aggregated local model, so rounds are classic:
         // differential privacy (fl_dp.hip) outputs the clipped, noised contribution, not the local
         // model a fused / lagged round's next train kernel would score and stage, and a discarded
-        // late-fold round would have spent noise; a server optimizer (fl_server.hip) outputs x + (a
+        // late-fold round would have spent noise; compression (fl_compress.hip) outputs x + the compressed
+        // update and keeps a residual a discarded round would have consumed; a server optimizer (fl_server.hip) outputs x + (a
         // server step), so a fused round would score the wrong model through the global image and a
         // lagged round's in-Adam exchange would publish an image the step then has to replace.
         const bool classic_only = tr_.foreign_output();
@@ -293,6 +299,20 @@ class FLEngine {
             dp_.norm_hist = as_ptr<float>(bufs["dp_norm"].cast<uintptr_t>());
             if (dp_.sigma == nullptr || dp_.norm_hist == nullptr)
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
+        }
+        if (tr_.compress_on) {
+            if (cp_.kind != FL_COMPRESS_TOPK && cp_.kind != FL_COMPRESS_SIGN)
+                throw std::runtime_error("FLEngine: unknown compressor");
+            cp_.P = d_.P;
+            cp_.k = cp_.kind == FL_COMPRESS_TOPK ? cfg["compress_k"].cast<int>() : d_.P;
+            cp_.error_feedback = cfg["error_feedback"].cast<bool>() ? 1 : 0;
+            cp_.max_rounds = c_.max_rounds;
+            cp_.residual = as_ptr<float>(bufs["compress_residual"].cast<uintptr_t>());
+            cp_.stat_hist = as_ptr<float>(bufs["compress_stat"].cast<uintptr_t>());
+            if (cp_.k < 1 || cp_.k > d_.P) throw std::runtime_error("FLEngine: compress_k must be in 1 .. P");
+            if (cp_.residual == nullptr || cp_.stat_hist == nullptr)
+                throw std::runtime_error("FLEngine: compression needs the residual and the statistic history");
+            HIP_CHECK(fl_set_lds_limit_compress(d_));
         }
         if (tr_.server_on) {
             if (sv_.kind < FL_SERVER_SGD || sv_.kind > FL_SERVER_YOGI)
@@ -686,7 +706,7 @@ class FLEngine {
         HIP_CHECK(hipStreamSynchronize(s));
         constexpr int TR_N = FLLaunchRec::N_KINDS;  // events are tagged with the launch kind
         static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
-                                          "server", "finalize"};
+                                          "server", "finalize", "compress"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -756,6 +776,17 @@ class FLEngine {
         o["comm_len"] = comm_len_;
         o["lagged_eval"] = lagged();
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
+        {
+            // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
+            static const char* compress_names[] = {"none", "topk", "sign"};
+            const long long P = d_.P, k = tr_.compress_on ? cp_.k : P;
+            py::dict c;
+            c["kind"] = std::string(compress_names[cp_.kind]);
+            c["k"] = (int)k;
+            c["dense_bytes"] = 4 * P;
+            c["uplink_bytes"] = cp_.kind == FL_COMPRESS_TOPK ? 8 * k : cp_.kind == FL_COMPRESS_SIGN ? 4 + (P + 7) / 8 : 4 * P;
+            o["compress"] = c;
+        }
         static const char* server_names[] = {"none", "sgd", "adagrad", "adam", "yogi"};
         o["server_opt"] = std::string(server_names[sv_.kind]);  // server step after every aggregation, classic rounds
         o["state_bytes"] = (int)sizeof(FLState);
@@ -786,6 +817,7 @@ class FLEngine {
     // republish w * local over the noised contribution / the server step's image.
     void plan_relaunch(RoundPlan& p, const char* what, int r, int which) {
         if (tr_.dp_on) throw std::runtime_error(std::string(what) + ": not on a DP engine (use trace)");
+        if (tr_.compress_on) throw std::runtime_error(std::string(what) + ": not on a compressing engine (use trace)");
         if (tr_.server_on)
             throw std::runtime_error(std::string(what) + ": not on a server-optimizer engine (use trace)");
         const int par = (r + 1) & 1;
@@ -851,6 +883,9 @@ class FLEngine {
             case FLLaunchRec::DP:
                 HIP_CHECK(fl_launch_dp(d_, dp_, F(0), F(1), F(2), S(3), b_.rtab, s));
                 break;
+            case FLLaunchRec::COMPRESS:
+                HIP_CHECK(fl_launch_compress(d_, cp_, F(0), F(1), F(2), S(3), b_.rtab, s));
+                break;
             case FLLaunchRec::SERVER:
                 HIP_CHECK(fl_launch_server(d_, sv_, F(0), F(1), S(2), eb, dtype_ == 1 ? b_.pk_global : nullptr, s));
                 break;
@@ -900,9 +935,9 @@ class FLEngine {
     bool shape_spec_on_ = true;  // FEDMI_SHAPE_SPEC != 0: launchers may pick shape-specialised kernels
     bool adam_spec_on_ = true;   // ... and FEDMI_ADAM_SPEC != 0: the Adam launcher too
     // The engine allows the specialised Adam kernel: no peer plane, and the round's output is the
-    // Adam kernel's own (no DP clip, no server step after it); the launcher checks the shape, the
+    // Adam kernel's own (no DP clip, no compression, no server step after it); the launcher checks the shape, the
     // client count, the lag region and the undo buffer per launch (fl_adam_spec_ok).
-    bool adam_spec_allowed() const { return adam_spec_on_ && peer_ == nullptr && !tr_.dp_on && !tr_.server_on; }
+    bool adam_spec_allowed() const { return adam_spec_on_ && peer_ == nullptr && !tr_.foreign_output(); }
     bool adam_spec_ok() const {
         return adam_spec_allowed() && fl_adam_spec_ok(d_, dtype_ == 1 ? &e_ : nullptr, c_, b_);
     }
@@ -915,6 +950,7 @@ class FLEngine {
     float* undo_ = nullptr;          // FLBuffers::undo storage (lagged engines with early stopping)
     PeerPack pp_;                    // its bf16 pack epilogue (bf16 mode)
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
+    FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLConfig c_;
     FLBuffers b_;
@@ -960,6 +996,7 @@ class TrialBatch {
             const FLEngine& e = *engs_[k];
             if (e.peer_ != nullptr) throw std::runtime_error("TrialBatch: engines must not use the peer all-reduce");
             if (e.tr_.server_on) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
+            if (e.tr_.compress_on) throw std::runtime_error("TrialBatch: no compression (compress)");
             if (e.dtype_ != a.dtype_ || std::memcmp(&e.d_, &a.d_, sizeof(MLPDesc)) != 0 ||
                 (a.dtype_ == 1 && (std::memcmp(&e.e_, &a.e_, sizeof(MLPDescB)) != 0 ||
                                    std::memcmp(&e.ev_, &a.ev_, sizeof(MLPDescB)) != 0)))
@@ -1034,6 +1071,7 @@ class TrialBatch {
     // What a batched launch cannot do (the constructor already refuses peer and server engines).
     static void check_batchable(const FLLaunchRec& m) {
         if (m.kind == FLLaunchRec::DP) throw std::runtime_error("trial batch: no DP");
+        if (m.kind == FLLaunchRec::COMPRESS) throw std::runtime_error("trial batch: no compression");
         if (m.kind == FLLaunchRec::SERVER) throw std::runtime_error("trial batch: no server optimizer");
         if (m.kind == FLLaunchRec::ALLREDUCE || m.kind == FLLaunchRec::EVAL_FEDAVG)
             throw std::runtime_error("trial batch: no peer all-reduce");
@@ -1156,6 +1194,37 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
                                as_ptr<const FLState>(state), tails_len, as_stream(stream)));
 }
 
+// One fl_compress launch on caller-owned buffers of the image of `dims` (tests, tools): `residual` =
+// 2 x Pimg floats (halves by round parity), `stat` = max_rounds floats, `state` / `rtab`: a client's
+// round state and per-round table.
+static void compress_launch(std::vector<int> dims, int kind, int k, bool error_feedback, uintptr_t local, uintptr_t x,
+                            uintptr_t comm, uintptr_t residual, uintptr_t stat, uintptr_t state, uintptr_t rtab,
+                            int max_rounds, uintptr_t stream) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("compress_launch: 1..4 Linear layers supported");
+    if (kind != FL_COMPRESS_TOPK && kind != FL_COMPRESS_SIGN)
+        throw std::runtime_error("compress_launch: kind must be 1 (topk) or 2 (sign)");
+    if (max_rounds < 1 || !local || !x || !comm || !residual || !stat || !state || !rtab)
+        throw std::runtime_error("compress_launch: bad arguments");
+    MLPDesc d;
+    std::memset(&d, 0, sizeof(d));
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    if (kind == FL_COMPRESS_SIGN) k = d.P;
+    if (k < 1 || k > d.P) throw std::runtime_error("compress_launch: k must be in 1 .. P");
+    FLCompress p;
+    std::memset(&p, 0, sizeof(p));
+    p.kind = kind;
+    p.k = k;
+    p.P = d.P;
+    p.error_feedback = error_feedback ? 1 : 0;
+    p.max_rounds = max_rounds;
+    p.residual = as_ptr<float>(residual);
+    p.stat_hist = as_ptr<float>(stat);
+    HIP_CHECK(fl_set_lds_limit_compress(d));
+    HIP_CHECK(fl_launch_compress(d, p, as_ptr<const float>(local), as_ptr<const float>(x), as_ptr<float>(comm),
+                                 as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
+}
+
 #ifndef FEDMI_SRC_DIGEST
 #define FEDMI_SRC_DIGEST "unknown"
 #endif
@@ -1235,6 +1304,9 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
           py::arg("max_rounds"), py::arg("stream"));
+    m.def("compress_launch", &compress_launch, py::arg("dims"), py::arg("kind"), py::arg("k"),
+          py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
+          py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);

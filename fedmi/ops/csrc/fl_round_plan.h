@@ -48,9 +48,9 @@ struct FLSel {
 };
 inline bool operator==(const FLSel& a, const FLSel& b) { return a.base == b.base && a.off == b.off; }
 
-// One launch of a round.  The kinds up to SERVER double as trace tags (FLEngine::trace).
+// One launch of a round.  The kinds double as trace tags (FLEngine::trace).
 struct FLLaunchRec {
-    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, N_KINDS };
+    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, COMPRESS, N_KINDS };
     int kind;
     int i[4];     // TRAIN: ls, stage_local, mode, fold_mask | ADAM: ls, fold, tail_a, fold_mask |
                   // FINALIZE: mask | others: 0
@@ -72,7 +72,7 @@ inline bool same_buffers(const FLLaunchRec& a, const FLLaunchRec& b) {
 }
 
 // Launches of one planning call: fixed capacity, nothing allocated per round.  A round holds at
-// most 2 * local_steps + 5 records (flush, pack, the train/Adam pairs, DP, eval, all-reduce,
+// most 2 * local_steps + 5 records (flush, pack, the train/Adam pairs, DP or compression, eval, all-reduce,
 // server), so engines take at most FL_PLAN_MAX_LOCAL_STEPS = 61 local steps
 // (fedmi/fl/engine.py MAX_LOCAL_STEPS states the same number).
 #define FL_PLAN_CAP 128
@@ -102,6 +102,7 @@ struct RoundTraits {
     bool has_peer = false;
     bool emulate = false; // one process stands in for a multi-client round (measurements, tests)
     bool dp_on = false;
+    bool compress_on = false;  // never with dp_on
     bool server_on = false;
     bool eval_fedavg_fits = false;
     bool identity = false;  // FedAvg is the identity: world == 1 && agg_scale == 1
@@ -117,8 +118,9 @@ struct RoundTraits {
     // The engine produces round outputs itself: one client, its peer all-reduce, or RCCL.
     bool aggregates(bool comm_present) const { return world < 2 || has_peer || comm_present; }
     // The round's output is not the aggregated local model (DP: the clipped, noised contribution;
-    // server optimizer: x + a server step), so rounds are classic and always stage a fresh pack.
-    bool foreign_output() const { return dp_on || server_on; }
+    // compression: x + the compressed update; server optimizer: x + a server step), so rounds are
+    // classic and always stage a fresh pack.
+    bool foreign_output() const { return dp_on || compress_on || server_on; }
 };
 
 // Which metrics the last issued round left pending, and the state of the packed bf16 image.
@@ -263,6 +265,8 @@ inline void plan_train(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
     // clip + noise of the contribution the last Adam kernel stored (fl_dp.hip); `so` holds
     // the round's live flag and index
     if (t.dp_on) out.push(FLLaunchRec::DP, 0, 0, 0, 0, par, local, pg, cb, so);
+    // ... or its compression with error feedback (fl_compress.hip), in the same place
+    else if (t.compress_on) out.push(FLLaunchRec::COMPRESS, 0, 0, 0, 0, par, local, pg, cb, so);
     c.pending_cm = fused;
     c.cm_in_tail = false;
     c.prev_scored = score;
