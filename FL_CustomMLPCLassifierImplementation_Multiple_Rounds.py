@@ -81,6 +81,13 @@ def parse_args(argv=None):
     ap.add_argument("--compress-ratio", type=float, default=0.1, help="--compress topk: fraction of entries kept, in (0, 1]")
     ap.add_argument("--no-error-feedback", action="store_true",
                     help="--compress: discard what the compressor drops instead of carrying it to the next round")
+    ap.add_argument("--secagg", action="store_true",
+                    help="secure aggregation: every client's contribution is quantised to fixed point and pair-masked "
+                         "before the exchange, only the sum opens (a simulation of the arithmetic: one shared seed, no "
+                         "key agreement; not with --wide or a robust --aggregator)")
+    ap.add_argument("--secagg-bits", type=int, default=24, help="--secagg: fractional bits of the fixed point, 8 .. 30")
+    ap.add_argument("--secagg-seed", type=int, default=None,
+                    help="--secagg: mask seed of the group (default: one private draw; no result depends on it)")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -187,6 +194,10 @@ def _compress_fields(a) -> dict:
     return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback)
 
 
+def _secagg_fields(a) -> dict:
+    return dict(secagg=a.secagg, secagg_bits=a.secagg_bits, secagg_seed=a.secagg_seed)
+
+
 def _print_privacy(a, rounds: int) -> None:
     """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
     if a.dp_clip > 0.0:
@@ -208,7 +219,8 @@ def main_clients(a, comm):
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
-                       **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a))
+                       **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a),
+                       **_secagg_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -262,6 +274,14 @@ def main(argv=None):
         compress_id(EngineConfig(**_dp_fields(a), **_compress_fields(a)))
     except ValueError as e:
         raise SystemExit(f"--compress / --compress-ratio: {e}")
+    if a.wide and a.secagg:
+        raise SystemExit("--secagg is not supported with --wide")
+    try:
+        from fedmi.fl.secagg import secagg_id
+        if secagg_id(EngineConfig(**_secagg_fields(a))) and a.aggregator != "mean":
+            raise ValueError(f"secagg does not combine with aggregator={a.aggregator!r}")
+    except ValueError as e:
+        raise SystemExit(f"--secagg / --secagg-bits / --secagg-seed: {e}")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -282,7 +302,7 @@ def main(argv=None):
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
                        debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
-                       **_compress_fields(a))
+                       **_compress_fields(a), **_secagg_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

@@ -140,11 +140,15 @@ def save_checkpoint(path: str, trainer) -> None:
     cp = {} if "compress_residual" not in st else {
         "compress_residual": np.asarray(st["compress_residual"], np.float32),
         "compress_stat": np.asarray(st["history"]["compress_stat"], np.float32)}
+    # secure aggregation: the config's three fields are all a resume needs (the mask seed is no state);
+    # the client's own per-round clamp counts stay in its file, as its update norms do
+    sa = {} if "secagg_clamped" not in st["history"] else {
+        "secagg_clamped": np.asarray(st["history"]["secagg_clamped"], np.int64)}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
         {"local": np.asarray(st["local"], np.float32), "exp_avg": np.asarray(st["exp_avg"], np.float32),
          "exp_avg_sq": np.asarray(st["exp_avg_sq"], np.float32),
          # this client's own Adam step count (differs from rounds x local_steps when clients are sampled)
-         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv, **cp}, tmp,
+         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv, **cp, **sa}, tmp,
         metadata={"round": str(R)}))
     gflat = flat_to_dict(st["global"], eng.dims)
     if eng.rank == 0:
@@ -218,6 +222,8 @@ def resume(path: str, trainer) -> int:
     if "compress_residual" in c:
         st["compress_residual"] = np.asarray(c["compress_residual"], np.float32)
         st["history"]["compress_stat"] = np.asarray(c["compress_stat"], np.float32)
+    if "secagg_clamped" in c:
+        st["history"]["secagg_clamped"] = np.asarray(c["secagg_clamped"], np.int64)
     eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer / compression
     return st["rounds"]
 

@@ -34,6 +34,8 @@ from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, robust_aggregate_torch
 from .compress import COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
+from .secagg import (MAX_SECAGG_CLIENTS, SECAGG_STREAM, secagg_id, secagg_mask, secagg_open,
+                     secagg_quantize)
 
 
 # bf16 shards of at most this many rows default to 16 rows per workgroup (EngineConfig.rows_per_block = 0):
@@ -157,6 +159,21 @@ class EngineConfig:
     compress: str = "none"
     compress_ratio: float = 0.1
     error_feedback: bool = True
+    # Secure aggregation (fedmi/fl/secagg.py; Bonawitz et al. 2017): every sampled client quantises its
+    # weighted contribution to fixed point with secagg_bits fractional bits and adds / subtracts one
+    # Philox mask per pair of the round's sampled clients (mod 2^32) before the exchange; the masks
+    # cancel in the sum, so a peer sees uniform words and only the sum opens.  A SIMULATION of the
+    # protocol's arithmetic: all pair masks derive from one shared group seed (secagg_seed; None = one
+    # draw per group / rank 0's draw), there is no key agreement, dropout recovery or malicious-server
+    # round.  The opened image does not depend on the seed (config only, never state).  Metric tails stay
+    # clear floats.  False: off (nothing of a round changes); one client: the identity.  Composes with
+    # dp_clip / dp_noise, compress, server_opt, participation, prox_mu, local_steps, early_stop, both
+    # dtypes; rounds are classic and aggregated over the host gather; history()["secagg_clamped"] counts
+    # this client's clamped / NaN coordinates.  Not with a robust aggregator, more than 64 clients, trial
+    # batches (comm_buffers), fed_sweep or WideClient.
+    secagg: bool = False
+    secagg_bits: int = 24
+    secagg_seed: Optional[int] = None
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -260,7 +277,10 @@ def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, 
 
 
 class _History:
-    def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False):
+    def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False,
+                 secagg: bool = False):
+        # secure aggregation: this client's clamped / NaN coordinates per round (0: not sampled)
+        self.clamped = np.zeros(max_rounds, dtype=np.int64) if secagg else None
         # DP engines: this client's pre-clip update norm per round (0: not sampled)
         self.norm = np.zeros(max_rounds, dtype=np.float32) if dp else None
         # compressing engines: the round's statistic (top-k: k-th kept magnitude; sign: scale; 0: not sampled)
@@ -286,6 +306,8 @@ class _History:
             out["update_norm"] = self.norm[:n].copy()
         if self.cstat is not None:
             out["compress_stat"] = self.cstat[:n].copy()
+        if self.clamped is not None:
+            out["secagg_clamped"] = self.clamped[:n].copy()
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -310,6 +332,15 @@ class RoundEngineBase:
         if self.robust and self.world > MAX_ROBUST_CLIENTS:
             raise ValueError(f"aggregator={cfg.aggregator!r} takes at most {MAX_ROBUST_CLIENTS} clients "
                              f"(the width of the sampled-client mask), got {self.world}")
+        # secure aggregation: 1 = masked fixed-point contributions; one client is the identity
+        on = secagg_id(cfg)
+        if on and kind:
+            raise ValueError(f"secagg does not combine with aggregator={cfg.aggregator!r}: the robust rules need the "
+                             "individual models, secure aggregation opens only their sum")
+        self.secagg = on if self.world > 1 else 0
+        if self.secagg and self.world > MAX_SECAGG_CLIENTS:
+            raise ValueError(f"secagg takes at most {MAX_SECAGG_CLIENTS} clients (the width of the sampled-client "
+                             f"mask), got {self.world}")
         self.n_local = int(len(X))
         if self.n_local == 0:
             raise ValueError("client shard is empty (reference SURVEY Q12 would deadlock)")
@@ -322,7 +353,8 @@ class RoundEngineBase:
         # robust aggregators are unweighted: the contribution image IS the local model (x 1.0f is exact)
         self.agg_scale = 1.0 if self.robust else float(self.n_local) / float(self.n_total)
         self.tail_stride = self.n_classes * self.n_classes + 1
-        self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress))
+        self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress),
+                             secagg=bool(self.secagg))
         self.compress_k = compress_k(cfg, self.P)   # entries a contribution transmits (sign, dense: P)
         assert init_flat.shape == (self.P,)
         if self.dp:
@@ -334,6 +366,33 @@ class RoundEngineBase:
             self.dp_seed = (int.from_bytes(os.urandom(8), "little") if cfg.dp_seed is None
                             else int(cfg.dp_seed))
             self.dp_sigma = self._dp_sigma_table(client_sizes)
+        if self.secagg:
+            if float(cfg.participation) < 1.0 and client_sizes is None:
+                if not hasattr(comm, "allgather"):
+                    raise ValueError("secagg with client sampling needs client_sizes (the contribution is weighted "
+                                     "by n_i / the sampled clients' total before it is masked)")
+                client_sizes = comm.allgather(self.n_local)
+            if client_sizes is not None:
+                self._client_sizes = [int(n) for n in client_sizes]
+            # the group's mask seed: configured, or rank 0's draw over the control plane (ClientGroup
+            # draws one for its clients).  Config only, never state: no result depends on it.
+            if cfg.secagg_seed is not None:
+                self.secagg_seed = int(cfg.secagg_seed)
+            elif hasattr(comm, "bcast"):
+                self.secagg_seed = int(comm.bcast(int.from_bytes(os.urandom(8), "little"), 0))
+            else:
+                raise ValueError("secagg_seed=None needs a communicator that can broadcast rank 0's draw; "
+                                 "name one seed for the group (ClientGroup draws it itself)")
+
+    def fedavg_weight(self, r: int) -> float:
+        """This client's FedAvg weight in round ``r`` as the per-round device table holds it: n_i / N, with
+        client sampling n_i / (the sampled clients' total), 0 when it is not sampled."""
+        part = self.participants(r)
+        if self.rank not in part:
+            return 0.0
+        if len(part) == self.world:
+            return float(self.n_local) / float(self.n_total)
+        return float(self.n_local) / float(sum(int(self._client_sizes[k]) for k in part))
 
     def _dp_sigma_table(self, client_sizes) -> np.ndarray:
         """Per-round noise std of ONE client's share, sigma_r = z * S * max_{j in P_r} w_j(r) / sqrt(K_r),
@@ -428,6 +487,8 @@ class RoundEngineBase:
             self.hist.norm[:n] = np.asarray(h["update_norm"], dtype=np.float32).reshape(n)
         if self.hist.cstat is not None and n and "compress_stat" in h:
             self.hist.cstat[:n] = np.asarray(h["compress_stat"], dtype=np.float32).reshape(n)
+        if self.hist.clamped is not None and n and "secagg_clamped" in h:
+            self.hist.clamped[:n] = np.asarray(h["secagg_clamped"], dtype=np.int64).reshape(n)
 
     def _load_dp_seed(self, st: dict) -> None:
         """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
@@ -570,6 +631,8 @@ class TorchRoundEngine(RoundEngineBase):
         [w * n_i/N | per-rank (confusion, loss) tails] (+ n_i when sampling clients)."""
         if self.robust:
             return self._robust_contribution()
+        if self.secagg:
+            return self._secagg_contribution()
         sampling = float(self.cfg.participation) < 1.0 and self.world > 1
         buf = torch.zeros(self.P + self.world * self.tail_stride + int(sampling), dtype=torch.float32)
         active = getattr(self, "_active", True)
@@ -633,6 +696,55 @@ class TorchRoundEngine(RoundEngineBase):
         self._compressed = (r, out)
         return out
 
+    def _secagg_contribution(self) -> torch.Tensor:
+        """Secure aggregation: this client's clear row in the HIP engines' weighted form,
+        [w_i(r) * model (+ noise) (zeros when not sampled) | per-rank (confusion, loss) tails] with the
+        per-round table's fp32 weight -- no trailing n_i slot and no division after the sum, so both
+        backends quantise the same quantity.  :meth:`secagg_mask_` masks it in place."""
+        r = self.rounds_issued
+        buf = torch.zeros(self.P + self.world * self.tail_stride, dtype=torch.float32)
+        active = getattr(self, "_active", True)
+        model = self.model.flat.detach().cpu()
+        noise = None
+        if self.dp:
+            self.hist.norm[r] = 0.0
+            if active:
+                model, noise = self._dp_clip_and_noise(r, model)
+        if self.compress:
+            model = self._compressed_model(model, active)
+        if active:
+            buf[:self.P] = model.to(torch.float32) * torch.tensor(self.fedavg_weight(r), dtype=torch.float32)
+            if noise is not None:
+                buf[:self.P] += noise.to(torch.float32)
+        t0 = self.P + self.rank * self.tail_stride
+        buf[t0:t0 + self.n_classes ** 2] = torch.as_tensor(self._cm.reshape(-1), dtype=torch.float32)
+        buf[t0 + self.n_classes ** 2] = self._loss
+        return buf
+
+    def secagg_mask_(self, buf: torch.Tensor) -> torch.Tensor:
+        """Quantise and pair-mask the parameters of this client's contribution row in place (the host
+        model, fedmi/fl/secagg.py): the words' bit patterns take the floats' places.  An unsampled
+        client's row is left alone.  Records the round's clamp count."""
+        r = self.rounds_issued
+        part = [int(k) for k in self.participants(r)]
+        self.hist.clamped[r] = 0
+        if self.rank in part:
+            q, self.hist.clamped[r] = secagg_quantize(buf[:self.P].numpy(), int(self.cfg.secagg_bits), len(part))
+            y = secagg_mask(q, self.rank, part, r, self.secagg_seed)
+            buf[:self.P].view(torch.int32).copy_(torch.as_tensor(y.view(np.int32)))
+        return buf
+
+    def secagg_combine(self, bufs: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The clients' masked rows (rank order) -> [opened sum of the sampled clients' words | tails
+        summed in rank order], the buffer :meth:`fedavg_apply` adopts."""
+        part = [int(k) for k in self.participants(self.rounds_issued)]
+        out = bufs[0].clone()
+        for b in bufs[1:]:
+            out[self.P:] += b[self.P:]
+        ys = np.stack([bufs[k][:self.P].contiguous().view(torch.int32).numpy().view(np.uint32) for k in part])
+        out[:self.P] = torch.as_tensor(secagg_open(ys, int(self.cfg.secagg_bits)))
+        return out
+
     def _robust_contribution(self) -> torch.Tensor:
         """Robust aggregators: this client's row of the round's gather, [unscaled local model (zeros
         when not sampled) | per-rank (confusion, loss) tails | 1 when sampled, else 0]."""
@@ -666,6 +778,10 @@ class TorchRoundEngine(RoundEngineBase):
         if self.robust:
             # robust aggregators: every client's row is gathered, the rule applied on every rank alike
             buf = self.robust_combine([torch.as_tensor(b) for b in self.comm.allgather(buf.numpy())])
+        elif self.secagg:
+            # secure aggregation: every client's MASKED row is gathered, the sum opened on every rank alike
+            self.secagg_mask_(buf)
+            buf = self.secagg_combine([torch.as_tensor(b) for b in self.comm.allgather(buf.numpy())])
         elif self.comm is not None:
             self.comm.allreduce_(buf)
         self.fedavg_apply(buf)
@@ -673,7 +789,7 @@ class TorchRoundEngine(RoundEngineBase):
     def fedavg_apply(self, buf: torch.Tensor) -> None:
         """Adopt the all-reduced buffer: new global weights, metrics, early-stop rule."""
         r = self.rounds_issued
-        sampling = float(self.cfg.participation) < 1.0 and self.world > 1 and not self.robust
+        sampling = float(self.cfg.participation) < 1.0 and self.world > 1 and not self.robust and not self.secagg
         if sampling:
             buf[:self.P] /= buf[-1]
             buf = buf[:-1]
@@ -849,6 +965,8 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"trial packing (comm_buffers) does not run compression (compress={cfg.compress!r})")
         if cfg.aggregator != "mean" and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
+        if bool(cfg.secagg) and comm_buffers is not None:
+            raise ValueError("trial packing (comm_buffers) does not run secure aggregation (secagg)")
         self.m = native()
         if device is None:
             device = comm.device if comm is not None else torch.device("cuda", torch.cuda.current_device())
@@ -859,8 +977,8 @@ class HipRoundEngine(RoundEngineBase):
         else:
             Xn_len, Xshape1 = X.shape
         super().__init__(_ShapeOnly(Xn_len, Xshape1), y, n_classes, cfg, comm, init_flat, n_total, client_sizes)
-        if self.dp and client_sizes is None:
-            client_sizes = self._client_sizes
+        if (self.dp or self.secagg) and client_sizes is None:
+            client_sizes = getattr(self, "_client_sizes", None)
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         self.X = (X if isinstance(X, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(X, np.float32))).to(**f32).contiguous()
@@ -885,9 +1003,10 @@ class HipRoundEngine(RoundEngineBase):
         # (differential privacy: classic rounds, see fl_engine.cpp)
         # (robust aggregators: classic rounds aggregated from Python, see _aggregate)
         # (compression: classic rounds, as with differential privacy)
+        # (secure aggregation: classic rounds masked and opened from Python, see _aggregate)
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
                      and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server
-                     and not self.robust and not self.compress)
+                     and not self.robust and not self.compress and not self.secagg)
         comm_len = self.Pimg + self.world * self.tail_stride * (2 if self._lag else 1)
         if comm_buffers is None:
             self.params = [torch.zeros(comm_len, **f32), torch.zeros(comm_len, **f32)]
@@ -985,6 +1104,11 @@ class HipRoundEngine(RoundEngineBase):
         self.R = R
         self.layout = self.engine.layout()
         self.layout["aggregator"] = AGGREGATORS[self.robust]   # the rule that runs (one client: the identity)
+        if self.secagg:
+            self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
+            # this client's clamped / NaN coordinates per round (uint32 words; integer atomics of fl_secagg.hip)
+            self.sa_clamp = torch.zeros(mr, dtype=torch.int32, device=dev)
+            self._secagg_tab = None   # device pointer tables of the mask / gather / open, built on first use
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -997,10 +1121,11 @@ class HipRoundEngine(RoundEngineBase):
         self._native_comm = None
         # one-shot xGMI all-reduce of [image | tails] (collective set-up; None -> RCCL)
         self._peer = None
-        # (a robust aggregator gathers over the host plane: neither the peer plane nor RCCL is set
-        # up -- every rank shares the config, so that is collectively consistent)
+        # (a robust aggregator and secure aggregation gather over the host plane: neither the peer plane
+        # nor RCCL is set up -- every rank shares the config, so that is collectively consistent)
         self._robust_tab = None   # device pointer tables of the gather, built on first use
-        if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust:
+        if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust \
+                and not self.secagg:
             from ..parallel.peer import make_peer_allreduce
             torch.cuda.synchronize(dev)
             # lagged rounds reduce inside the Adam kernel: one chunk flag per Adam block + the
@@ -1010,7 +1135,7 @@ class HipRoundEngine(RoundEngineBase):
             if self._peer is not None:
                 self.engine.attach_peer(self._peer)
         if self.world > 1 and self._peer is None and comm_buffers is None and comm is not None \
-                and hasattr(comm, "rccl") and not self.robust:
+                and hasattr(comm, "rccl") and not self.robust and not self.secagg:
             # RCCL only when the peer plane is off or fell back (every rank agreed on that above),
             # so this lazy, bounded bootstrap runs on every rank or on none; if it fails too, every
             # rank continues on the host plane (aggregation 'host') instead of raising
@@ -1100,10 +1225,10 @@ class HipRoundEngine(RoundEngineBase):
     @property
     def aggregation(self) -> str:
         """Data plane of the FedAvg all-reduce: 'none' (one client), 'xgmi-oneshot', 'rccl' or 'host';
-        'host-gather': a robust aggregator over every rank's gathered buffer."""
+        'host-gather': a robust aggregator, or secure aggregation, over every rank's gathered buffer."""
         if self.world == 1:
             return "none"
-        if self.robust:
+        if self.robust or self.secagg:
             return "host-gather"
         if self._peer is not None:
             return "xgmi-oneshot+adam" if self.engine.adam_exchange else "xgmi-oneshot"
@@ -1134,6 +1259,9 @@ class HipRoundEngine(RoundEngineBase):
         output buffer: the communicator's SUM all-reduce, or (robust aggregators) a gather of every
         rank's buffer over the host plane and one fl_robust launch over the gathered stack."""
         buf = self.params[(r + 1) & 1]
+        if self.secagg:
+            self._aggregate_secagg(r)
+            return
         if not self.robust:
             self.comm.allreduce_(buf)
             return
@@ -1149,6 +1277,27 @@ class HipRoundEngine(RoundEngineBase):
                                 dst[par].data_ptr(), 1, self.state[par].data_ptr(), self.rtab.data_ptr(),
                                 self.world * self.tail_stride, int(self.cfg.max_rounds),
                                 torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _aggregate_secagg(self, r: int) -> None:
+        """Secure aggregation of round ``r`` on the current stream: fl_secagg_mask on this rank's buffer, a
+        gather of every rank's MASKED buffer over the host plane, fl_secagg_open over the gathered stack
+        into the round's output buffer."""
+        if self._secagg_tab is None:
+            i64 = dict(dtype=torch.int64, device=self.device)
+            stack = torch.empty((self.world, self.params[0].numel()), dtype=torch.float32, device=self.device)
+            src = torch.tensor([stack[k].data_ptr() for k in range(self.world)], **i64)
+            own = [torch.tensor([p.data_ptr()], **i64) for p in self.params]
+            clamp = torch.tensor([self.sa_clamp.data_ptr()], **i64)
+            self._secagg_tab = (stack, src, own, clamp)
+        stack, src, own, clamp = self._secagg_tab
+        par = (r + 1) & 1
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        bits, mr = int(self.cfg.secagg_bits), int(self.cfg.max_rounds)
+        self.m.secagg_mask(self.dims, bits, self.secagg_seed, own[par].data_ptr(), 1, self.rank,
+                           self.state[par].data_ptr(), self.rtab.data_ptr(), clamp.data_ptr(), mr, s)
+        self.comm.allgather_device(self.params[par], out=stack)
+        self.m.secagg_open(self.dims, bits, src.data_ptr(), self.world, own[par].data_ptr(), 1,
+                           self.state[par].data_ptr(), self.rtab.data_ptr(), self.world * self.tail_stride, mr, s)
 
     def server_step(self, r: int) -> None:
         """Server-optimizer step of round ``r`` on the aggregated image a caller summed into
@@ -1479,6 +1628,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.norm[:n] = self.dp_norm[:n].cpu().numpy()
             if self.compress:
                 self.hist.cstat[:n] = self.cp_stat[:n].cpu().numpy()
+            if self.secagg:
+                self.hist.clamped[:n] = self.sa_clamp[:n].cpu().numpy().view(np.uint32)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1586,6 +1737,8 @@ class HipRoundEngine(RoundEngineBase):
             self.state[r & 1].copy_(torch.as_tensor(rec.view(np.uint8).copy()).to(dev))
             self._load_history(st["history"])
             n = self.hist.rounds_run
+            if self.secagg:
+                self.sa_clamp.zero_()   # the mask kernel ADDS to a round's count: rounds run again start from 0
             if n:
                 self.h_global[:n * 4].copy_(torch.as_tensor(self.hist.glob[:n].reshape(-1), device=dev))
                 self.h_rank[:n * self.world * 4].copy_(torch.as_tensor(self.hist.rank[:n].reshape(-1), device=dev))
@@ -1594,6 +1747,9 @@ class HipRoundEngine(RoundEngineBase):
                     self.dp_norm[:n].copy_(torch.as_tensor(self.hist.norm[:n], device=dev))
                 if self.compress:
                     self.cp_stat[:n].copy_(torch.as_tensor(self.hist.cstat[:n], device=dev))
+                if self.secagg:
+                    self.sa_clamp[:n].copy_(torch.as_tensor(self.hist.clamped[:n].astype(np.uint32).view(np.int32),
+                                                            device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
         self.engine.invalidate()

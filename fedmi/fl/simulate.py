@@ -20,10 +20,16 @@ client's tail (C:165-192).
 With a robust aggregator (``EngineConfig.aggregator``) the in-process sum is replaced by the
 coordinate-wise median / trimmed mean of the sampled clients' buffers: one ``fl_robust`` launch,
 in place over the k buffers, on the device; ``robust_aggregate_torch`` on the CPU.
+
+With secure aggregation (``EngineConfig.secagg``, ``fedmi/fl/secagg.py``) the k buffers are
+quantised and pair-masked before they are summed: one ``fl_secagg_mask`` launch over the k buffers
+and one ``fl_secagg_open`` launch in place on the device, the host model on the CPU.  The ``wire``
+hook sees the buffers between the two -- what a peer would receive.
 """
 from __future__ import annotations
 
 import copy
+import os
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -53,12 +59,16 @@ class ClientGroup:
 
     def __init__(self, X, y, k: int, cfg: EngineConfig, backend: str = "hip", shard_mode: str = "compat",
                  seed: int = 0, alpha: float = 0.5, device=None, n_classes: Optional[int] = None,
-                 tamper: Optional[Callable[[int, List[torch.Tensor]], None]] = None):
+                 tamper: Optional[Callable[[int, List[torch.Tensor]], None]] = None,
+                 wire: Optional[Callable[[int, List[torch.Tensor]], None]] = None):
         """``tamper(r, bufs)``: optional hook for Byzantine-client studies, called every round after the
         local steps and before the aggregation with the round index and the k clients' contribution
         buffers in client order (hip: the device FedAvg buffers, on the group's stream, the padded
         parameter image first; torch: the ``fedavg_contribution`` rows, the dense parameters first);
-        what it writes is what gets aggregated.  ``None`` changes nothing."""
+        what it writes is what gets aggregated.  ``None`` changes nothing.
+        ``wire(r, bufs)``: optional hook called with the same arguments after the secure-aggregation mask
+        step (``EngineConfig.secagg``) and before the sum is opened: what a peer sees on the wire (tamper
+        sees the clear contributions).  Not called without secure aggregation."""
         X = np.asarray(X)
         y = np.asarray(y)
         self.k = int(k)
@@ -72,6 +82,10 @@ class ClientGroup:
             self.device = torch.device(device if device is not None else "cuda")
         else:
             self.device = torch.device("cpu")
+        if bool(cfg.secagg) and cfg.secagg_seed is None:
+            # one mask seed for the group (config only: no result depends on it)
+            cfg = copy.deepcopy(cfg)
+            cfg.secagg_seed = int.from_bytes(os.urandom(8), "little")
         self.clients: List = []
         for r in range(self.k):
             c = copy.deepcopy(cfg)
@@ -92,6 +106,8 @@ class ClientGroup:
                 raise ValueError(f"unknown backend {backend!r}")
             self.clients.append(e)
         self.tamper = tamper
+        self.wire = wire
+        self._secagg_tab = None   # hip, secure aggregation: device pointer tables (buffers per parity, clamp counts)
         self._robust_tab = None   # hip, robust aggregators: device pointer tables of the k buffers, per parity
         if backend == "hip":
             self.stream = torch.cuda.Stream(device=self.device)
@@ -121,6 +137,22 @@ class ClientGroup:
             lead.m.robust_aggregate(lead.dims, lead.robust, float(lead.cfg.trim_ratio), tab, self.k, tab, self.k,
                                     lead.state[par].data_ptr(), lead.rtab.data_ptr(), self.k * lead.tail_stride,
                                     int(lead.cfg.max_rounds), s)
+        elif lead.secagg:
+            # one mask launch over the k buffers, the wire hook, one open launch in place; the round's
+            # live flag, index and sampled mask are the lead client's (identical on all)
+            if self._secagg_tab is None:
+                i64 = dict(dtype=torch.int64, device=self.device)
+                self._secagg_tab = ([torch.tensor([e.params[q].data_ptr() for e in self.clients], **i64) for q in (0, 1)],
+                                    torch.tensor([e.sa_clamp.data_ptr() for e in self.clients], **i64))
+            tab, clamp = self._secagg_tab[0][par].data_ptr(), self._secagg_tab[1].data_ptr()
+            bits, mr = int(lead.cfg.secagg_bits), int(lead.cfg.max_rounds)
+            lead.m.secagg_mask(lead.dims, bits, lead.secagg_seed, tab, self.k, 0, lead.state[par].data_ptr(),
+                               lead.rtab.data_ptr(), clamp, mr, s)
+            if self.wire is not None:
+                with torch.cuda.stream(self.stream):
+                    self.wire(r, bufs)
+            lead.m.secagg_open(lead.dims, bits, tab, self.k, tab, self.k, lead.state[par].data_ptr(),
+                               lead.rtab.data_ptr(), self.k * lead.tail_stride, mr, s)
         else:
             self._sum_hip(bufs)
         for e in self.clients:
@@ -147,6 +179,12 @@ class ClientGroup:
             self.tamper(self.rounds, bufs)
         if self.clients[0].robust:
             tot = self.clients[0].robust_combine(bufs)
+        elif self.clients[0].secagg:
+            for e, b in zip(self.clients, bufs):
+                e.secagg_mask_(b)
+            if self.wire is not None:
+                self.wire(self.rounds, bufs)
+            tot = self.clients[0].secagg_combine(bufs)
         else:
             tot = bufs[0].clone()
             for b in bufs[1:]:

@@ -151,6 +151,14 @@ class FederatedMLPLearning:
             wd.close()
         gflat = eng.global_flat()
         self.global_weights = flat_to_dict(gflat, eng.dims)
+        clamped = eng.history().get("secagg_clamped") if getattr(eng, "secagg", 0) else None
+        if clamped is not None and int(np.sum(clamped)) and not getattr(self, "_secagg_warned", False):
+            # once per trainer: a clamped coordinate entered the sum at +-(2^31 - 1) / K_r 2^-bits, not at its value
+            self._secagg_warned = True
+            import warnings
+            warnings.warn(f"secure aggregation clamped {int(np.sum(clamped))} coordinates of rank {self.rank}'s "
+                          f"contributions (secagg_bits={eng.cfg.secagg_bits}: |value| above (2^31 - 1) / K_r 2^-bits, "
+                          "or NaN); lower secagg_bits", RuntimeWarning, stacklevel=2)
         if comm is not None and getattr(comm, "size", 1) > 1:
             # every client must end the run holding the same global model and metric history
             # (C:119-120); a data-plane fault raises here instead of passing as a result

@@ -91,6 +91,9 @@ class FedTrialGroup:
         if base.compress != "none":
             # the trials share launches; a residual and a selection per trial is not batched
             raise ValueError("fed_sweep does not run compressed trials (compress)")
+        if bool(base.secagg):
+            # the trials share one SUM all-reduce; a mask, a gather and an open per trial is not batched
+            raise ValueError("fed_sweep does not run secure-aggregation trials (secagg)")
         if base.aggregator != "mean":
             # the trials share one SUM all-reduce; a gather and a selection per trial is not batched
             raise ValueError("fed_sweep does not run robust-aggregator trials (aggregator)")

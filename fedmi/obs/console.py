@@ -66,6 +66,9 @@ class JsonlWriter:
             # (compressing engines: the round's statistic -- k-th kept magnitude / sign scale)
             if "compress_stat" in hist:
                 norm["compress_stat"] = float(hist["compress_stat"][r])
+            # (secure aggregation: this client's clamped / NaN coordinates of the round)
+            if "secagg_clamped" in hist:
+                norm["secagg_clamped"] = int(hist["secagg_clamped"][r])
             self.write(round=r + 1, **{k: float(hist["global"][r][i]) for i, k in enumerate(METRIC_NAMES)},
                        per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **norm, **extra)
 

@@ -371,6 +371,26 @@ __host__ __device__ inline int fl_robust_trim(int kind, double beta, int kr) {
     return t < med ? t : med;
 }
 
+// Secure aggregation (fl_secagg.hip; Bonawitz et al. 2017, the arithmetic only): parameters of the
+// per-round mask and open launches, passed to those kernels alone.  A sampled client's contribution c
+// becomes q = clamp(rint(c 2^bits), -L, L), L = (2^31 - 1) / K_r, plus / minus the pair masks
+// m(a, b)[p] = word p % 4 of Philox4x32-10 at counter (p / 4, round, 64 a + b, FL_SECAGG_STREAM) under
+// (key0, key1), mod 2^32; the open sums the sampled clients' words and scales by 2^-bits.
+#define FL_SECAGG_STREAM 0x47414353u  // distinct from the DP noise stream 0x46454450 (fl_dp.hip)
+#define FL_SECAGG_MAX_K 64            // width of the rtab mask
+#define FL_SECAGG_MIN_BITS 8
+#define FL_SECAGG_MAX_BITS 30
+struct FLSecAgg {
+    int bits;            // fractional bits F, FL_SECAGG_MIN_BITS .. FL_SECAGG_MAX_BITS
+    int K;               // open: sources, 1 .. FL_SECAGG_MAX_K (source k is client k)
+    int first_client;    // mask: client index of the launch's first buffer
+    int max_rounds;      // rounds of rtab / entries of a clamp history; rounds past it are not live
+    uint32_t key0, key1; // mask: Philox key, the group's 64-bit seed, low and high word
+    float scale;         // 2^bits, 2^-bits: filled in by the launchers
+    float inv_scale;
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+};
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -464,6 +484,17 @@ hipError_t fl_launch_server(const MLPDesc& d, const FLServer& p, const float* x,
 // the left fold in source order.  No per-round host argument: the launch is replayable.
 hipError_t fl_launch_robust(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
                             const FLState* st, int tails_len, hipStream_t s);
+// (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
+// place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
+// first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);
+// `clamp`: device table of the n clients' uint32 [max_rounds] clamp histories.  Open: over the K buffers
+// of Pimg + `tails_len` floats named by `src`, written to the `n_dst` buffers named by `dst` (destinations
+// may be sources).  Image: the scaled integer sum of the round's sampled clients, padding exact 0; tails,
+// and the whole buffer of a round that is not live: the left fold in source order.  Both replayable.
+hipError_t fl_launch_secagg_mask(const MLPDesc& d, const FLSecAgg& p, float* const* bufs, int n,
+                                 uint32_t* const* clamp, const FLState* st, hipStream_t s);
+hipError_t fl_launch_secagg_open(const MLPDesc& d, const FLSecAgg& p, const float* const* src, float* const* dst,
+                                 int n_dst, const FLState* st, int tails_len, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

@@ -1194,6 +1194,60 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
                                as_ptr<const FLState>(state), tails_len, as_stream(stream)));
 }
 
+// Secure aggregation (fl_secagg.hip) across engines' buffers, as robust_aggregate is.  `bufs` / `clamp`:
+// device tables of n buffer / uint32 [max_rounds] clamp-history addresses (int64) of clients
+// first_client .. first_client + n - 1; `state` / `rtab`: a client's round state and per-round table.
+static void secagg_mask(std::vector<int> dims, int bits, unsigned long long seed, uintptr_t bufs, int n,
+                        int first_client, uintptr_t state, uintptr_t rtab, uintptr_t clamp, int max_rounds,
+                        uintptr_t stream) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("secagg_mask: 1..4 Linear layers supported");
+    if (bits < FL_SECAGG_MIN_BITS || bits > FL_SECAGG_MAX_BITS)
+        throw std::runtime_error("secagg_mask: bits must be in 8 .. 30, got " + std::to_string(bits));
+    if (n < 1 || first_client < 0 || first_client + n > FL_SECAGG_MAX_K)
+        throw std::runtime_error("secagg_mask: clients 0.." + std::to_string(FL_SECAGG_MAX_K - 1) +
+                                 " (the width of the sampled-client mask), got " + std::to_string(first_client) +
+                                 " + " + std::to_string(n));
+    if (max_rounds < 1 || !bufs || !state || !rtab || !clamp) throw std::runtime_error("secagg_mask: bad arguments");
+    MLPDesc d;
+    std::memset(&d, 0, sizeof(d));
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    FLSecAgg p;
+    std::memset(&p, 0, sizeof(p));
+    p.bits = bits;
+    p.first_client = first_client;
+    p.max_rounds = max_rounds;
+    p.key0 = (uint32_t)seed;
+    p.key1 = (uint32_t)(seed >> 32);
+    p.rtab = as_ptr<const float>(rtab);
+    HIP_CHECK(fl_launch_secagg_mask(d, p, as_ptr<float* const>(bufs), n, as_ptr<uint32_t* const>(clamp),
+                                    as_ptr<const FLState>(state), as_stream(stream)));
+}
+
+static void secagg_open(std::vector<int> dims, int bits, uintptr_t src, int K, uintptr_t dst, int n_dst,
+                        uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds, uintptr_t stream) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("secagg_open: 1..4 Linear layers supported");
+    if (bits < FL_SECAGG_MIN_BITS || bits > FL_SECAGG_MAX_BITS)
+        throw std::runtime_error("secagg_open: bits must be in 8 .. 30, got " + std::to_string(bits));
+    if (K < 1 || K > FL_SECAGG_MAX_K)
+        throw std::runtime_error("secagg_open: 1.." + std::to_string(FL_SECAGG_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (n_dst < 1 || n_dst > FL_SECAGG_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !dst || !state || !rtab)
+        throw std::runtime_error("secagg_open: bad arguments");
+    MLPDesc d;
+    std::memset(&d, 0, sizeof(d));
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    FLSecAgg p;
+    std::memset(&p, 0, sizeof(p));
+    p.bits = bits;
+    p.K = K;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    HIP_CHECK(fl_launch_secagg_open(d, p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
+                                    as_ptr<const FLState>(state), tails_len, as_stream(stream)));
+}
+
 // One fl_compress launch on caller-owned buffers of the image of `dims` (tests, tools): `residual` =
 // 2 x Pimg floats (halves by round parity), `stat` = max_rounds floats, `state` / `rtab`: a client's
 // round state and per-round table.
@@ -1307,6 +1361,13 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.def("compress_launch", &compress_launch, py::arg("dims"), py::arg("kind"), py::arg("k"),
           py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
           py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+    m.def("secagg_mask", &secagg_mask, py::arg("dims"), py::arg("bits"), py::arg("seed"), py::arg("bufs"), py::arg("n"),
+          py::arg("first_client"), py::arg("state"), py::arg("rtab"), py::arg("clamp"), py::arg("max_rounds"),
+          py::arg("stream"));
+    m.def("secagg_open", &secagg_open, py::arg("dims"), py::arg("bits"), py::arg("src"), py::arg("K"), py::arg("dst"),
+          py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"), py::arg("max_rounds"),
+          py::arg("stream"));
+    m.attr("SECAGG_STREAM") = (unsigned)FL_SECAGG_STREAM;
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);
