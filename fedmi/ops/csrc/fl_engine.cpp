@@ -588,6 +588,17 @@ class FLEngine {
         return py::bytes(out);
     }
 
+    // ... and the packed image of the LOCAL model, which the Adam kernel writes beside the fp32
+    // step and a one-client round stages instead of packing its input again (plan_train_launch:
+    // solo).  A copy-out like packed_global; tests compare it with the stand-alone pack.
+    py::bytes packed_local(uintptr_t stream) const {
+        if (dtype_ != 1) throw std::runtime_error("packed_local: bf16 engines only");
+        HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+        std::string out((size_t)e_.param_bytes, '\0');
+        HIP_CHECK(hipMemcpy(out.data(), b_.pk_local, out.size(), hipMemcpyDeviceToHost));
+        return py::bytes(out);
+    }
+
     // The host wrote the global weights (set_weights / resume): the next round repacks them.
     void invalidate() { carry_.need_pack = true; }
 
@@ -758,6 +769,10 @@ class FLEngine {
         o["lds_bytes"] = dtype_ == 0 ? d_.lds_floats * 4 : e_.lds_bytes;
         o["bank_level"] = dtype_ == 0 ? -1 : e_.level;
         o["eval_lds_bytes"] = dtype_ == 0 ? d_.lds_floats * 4 : ev_.lds_bytes;
+        // bf16: the packed image (packed_global / packed_local) is [W hi | fp32 biases | W lo], each
+        // lo element wlo_delta bytes behind its hi element; param_bytes in all
+        o["wlo_delta"] = dtype_ == 1 ? e_.wlo_delta : 0;
+        o["param_bytes"] = dtype_ == 1 ? e_.param_bytes : 0;
         o["lag_reg"] = dtype_ == 1 && e_.lag_reg != 0;  // lagged rounds score in registers (fl_layout.h)
         o["plain_fwd"] = c_.plain_fwd != 0;              // plain-bf16 training forward (several clients)
         o["split_score"] = c_.split_score != 0;          // lagged scoring on workgroups of its own
@@ -1334,6 +1349,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def("invalidate", &FLEngine::invalidate)
         .def("set_dp_seed", &FLEngine::set_dp_seed)
         .def("packed_global", &FLEngine::packed_global)
+        .def("packed_local", &FLEngine::packed_local)
         .def("set_early_stop", &FLEngine::set_early_stop)
         .def("reset_pending", &FLEngine::reset_pending)
         .def("attach_peer", &FLEngine::attach_peer, py::keep_alive<1, 2>())

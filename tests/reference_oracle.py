@@ -199,25 +199,39 @@ def _bf(x):
     return x.to(torch.bfloat16).to(torch.float64)
 
 
-def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False):
-    """Host model of the bf16 train kernel's arithmetic (fl_kernels_bf16.hip), in float64:
-    split-bf16 forward (hi.hi + lo.hi + hi.lo, hidden outputs split into hi/lo after ReLU),
-    softmax-CE deltas rounded to bf16, backward on the hi parts with bf16 deltas."""
+def _bf16_forward(flat, X, dims, plain=False):
+    """Forward pass of the bf16 kernels (fl_kernels_bf16.hip) in float64: every layer multiplies the
+    bf16 parts of its input and weights, x_hi = bf16(x), x_lo = bf16(x - x_hi) -- split-bf16
+    hi.hi + (lo.hi + hi.lo), or with ``plain`` hi.hi alone (FLConfig::plain_fwd) -- and adds the
+    fp32 bias; hidden outputs are rounded to fp32 after ReLU and split again.  Returns (Ws, the hi
+    part of every layer's input, the logits)."""
     from fedmi.models.mlp import flat_to_dict
     d = flat_to_dict(flat, dims)
     L = len(dims) - 1
     Ws = [torch.as_tensor(d[f"model.{2 * l}.weight"], dtype=torch.float64) for l in range(L)]
     bs = [torch.as_tensor(d[f"model.{2 * l}.bias"], dtype=torch.float64) for l in range(L)]
     a = torch.as_tensor(X, dtype=torch.float32).to(torch.float64)
-    yt = torch.as_tensor(y, dtype=torch.long)
-    his, pre = [], []
+    his = []
     for l in range(L):
         ah, wh = _bf(a), _bf(Ws[l])
-        al, wl = _bf(a - ah), _bf(Ws[l] - wh)
-        z = ah @ wh.T + (al @ wh.T + ah @ wl.T) + bs[l]
+        if plain:
+            z = ah @ wh.T + bs[l]
+        else:
+            al, wl = _bf(a - ah), _bf(Ws[l] - wh)
+            z = ah @ wh.T + (al @ wh.T + ah @ wl.T) + bs[l]
         his.append(ah)
-        pre.append(z)
         a = torch.relu(z).to(torch.float32).to(torch.float64)
+    return Ws, his, z
+
+
+def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False, plain=False):
+    """Host model of the bf16 train kernel's arithmetic (fl_kernels_bf16.hip), in float64:
+    split-bf16 forward (hi.hi + lo.hi + hi.lo, hidden outputs split into hi/lo after ReLU; with
+    ``plain`` the hi.hi forward of several clients' training pass), softmax-CE deltas rounded to
+    bf16, backward on the hi parts with bf16 deltas."""
+    L = len(dims) - 1
+    Ws, his, z = _bf16_forward(flat, X, dims, plain)
+    yt = torch.as_tensor(y, dtype=torch.long)
     n = len(y)
     p = torch.softmax(z, 1)
     dz = p.clone()
