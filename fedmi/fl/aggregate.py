@@ -43,6 +43,44 @@ def trim_count(kind: str, beta: float, k_r: int) -> int:
     return min(int(math.floor(beta * float(k_r))), med)
 
 
+class _AggLaunch:
+    """The Python-launched aggregation kernels (``robust_aggregate``, ``secagg_mask``, ``secagg_open``) of
+    one federation, over buffers that keep their addresses.  ``lead``: the engine whose dims, round
+    state, ``rtab`` and config every launch uses (identical on all clients); ``src[par]`` / ``dst[par]``:
+    the source and destination buffers of a round of output parity ``par``; :meth:`mask` masks the
+    destinations in place -- what a process publishes is where it receives the aggregate -- as clients
+    ``first_client ..`` with the clamp histories ``clamps``.  Owns the device pointer tables."""
+
+    def __init__(self, lead, src, dst, clamps=(), first_client: int = 0):
+        def table(ts):
+            return torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=lead.device)
+        self._lead, self._bufs = lead, (src, dst, clamps)   # (the tables hold addresses: keep the buffers)
+        self._k, self._n, self._first = len(src[0]), len(dst[0]), int(first_client)
+        self._src = [table(s) for s in src]
+        self._dst = self._src if dst is src else [table(s) for s in dst]
+        self._clamp = table(clamps)
+
+    def _round(self, par: int):
+        e = self._lead
+        return e.state[par].data_ptr(), e.rtab.data_ptr()
+
+    def robust(self, par: int, stream: int) -> None:
+        e = self._lead
+        e.m.robust_aggregate(e.dims, e.robust, float(e.cfg.trim_ratio), self._src[par].data_ptr(), self._k,
+                             self._dst[par].data_ptr(), self._n, *self._round(par), self._k * e.tail_stride,
+                             int(e.cfg.max_rounds), stream)
+
+    def mask(self, par: int, stream: int) -> None:
+        e = self._lead
+        e.m.secagg_mask(e.dims, int(e.cfg.secagg_bits), e.secagg_seed, self._dst[par].data_ptr(), self._n, self._first,
+                        *self._round(par), self._clamp.data_ptr(), int(e.cfg.max_rounds), stream)
+
+    def open(self, par: int, stream: int) -> None:
+        e = self._lead
+        e.m.secagg_open(e.dims, int(e.cfg.secagg_bits), self._src[par].data_ptr(), self._k, self._dst[par].data_ptr(),
+                        self._n, *self._round(par), self._k * e.tail_stride, int(e.cfg.max_rounds), stream)
+
+
 def _sort_keys(stack: torch.Tensor) -> torch.Tensor:
     """int64 keys whose order is the total order of the values: NaN above +inf, -0 == +0."""
     stack = stack.contiguous()

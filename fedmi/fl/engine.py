@@ -30,7 +30,7 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
-from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, robust_aggregate_torch
+from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, _AggLaunch, robust_aggregate_torch
 from .compress import COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
@@ -1108,7 +1108,6 @@ class HipRoundEngine(RoundEngineBase):
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
             # this client's clamped / NaN coordinates per round (uint32 words; integer atomics of fl_secagg.hip)
             self.sa_clamp = torch.zeros(mr, dtype=torch.int32, device=dev)
-            self._secagg_tab = None   # device pointer tables of the mask / gather / open, built on first use
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -1123,7 +1122,7 @@ class HipRoundEngine(RoundEngineBase):
         self._peer = None
         # (a robust aggregator and secure aggregation gather over the host plane: neither the peer plane
         # nor RCCL is set up -- every rank shares the config, so that is collectively consistent)
-        self._robust_tab = None   # device pointer tables of the gather, built on first use
+        self._agg = None   # gathered stack + launcher of the aggregation kernels over it (_gather_launch)
         if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust \
                 and not self.secagg:
             from ..parallel.peer import make_peer_allreduce
@@ -1265,39 +1264,30 @@ class HipRoundEngine(RoundEngineBase):
         if not self.robust:
             self.comm.allreduce_(buf)
             return
-        if self._robust_tab is None:
-            stack = torch.empty((self.world, buf.numel()), dtype=torch.float32, device=self.device)
-            src = torch.tensor([stack[k].data_ptr() for k in range(self.world)], dtype=torch.int64, device=self.device)
-            dst = [torch.tensor([p.data_ptr()], dtype=torch.int64, device=self.device) for p in self.params]
-            self._robust_tab = (stack, src, dst)
-        stack, src, dst = self._robust_tab
+        stack, agg = self._gather_launch()
         self.comm.allgather_device(buf, out=stack)
-        par = (r + 1) & 1
-        self.m.robust_aggregate(self.dims, self.robust, float(self.cfg.trim_ratio), src.data_ptr(), self.world,
-                                dst[par].data_ptr(), 1, self.state[par].data_ptr(), self.rtab.data_ptr(),
-                                self.world * self.tail_stride, int(self.cfg.max_rounds),
-                                torch.cuda.current_stream(self.device).cuda_stream)
+        agg.robust((r + 1) & 1, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _gather_launch(self):
+        """The gathered stack of every rank's buffer and the launcher of the aggregation kernels over it
+        (sources: its rows; destination and masked buffer: this rank's ``params[par]``), built on first use."""
+        if self._agg is None:
+            stack = torch.empty((self.world, self.params[0].numel()), dtype=torch.float32, device=self.device)
+            rows = [stack[k] for k in range(self.world)]
+            self._agg = (stack, _AggLaunch(self, [rows, rows], [[p] for p in self.params],
+                                           clamps=[self.sa_clamp] if self.secagg else (), first_client=self.rank))
+        return self._agg
 
     def _aggregate_secagg(self, r: int) -> None:
         """Secure aggregation of round ``r`` on the current stream: fl_secagg_mask on this rank's buffer, a
         gather of every rank's MASKED buffer over the host plane, fl_secagg_open over the gathered stack
         into the round's output buffer."""
-        if self._secagg_tab is None:
-            i64 = dict(dtype=torch.int64, device=self.device)
-            stack = torch.empty((self.world, self.params[0].numel()), dtype=torch.float32, device=self.device)
-            src = torch.tensor([stack[k].data_ptr() for k in range(self.world)], **i64)
-            own = [torch.tensor([p.data_ptr()], **i64) for p in self.params]
-            clamp = torch.tensor([self.sa_clamp.data_ptr()], **i64)
-            self._secagg_tab = (stack, src, own, clamp)
-        stack, src, own, clamp = self._secagg_tab
+        stack, agg = self._gather_launch()
         par = (r + 1) & 1
         s = torch.cuda.current_stream(self.device).cuda_stream
-        bits, mr = int(self.cfg.secagg_bits), int(self.cfg.max_rounds)
-        self.m.secagg_mask(self.dims, bits, self.secagg_seed, own[par].data_ptr(), 1, self.rank,
-                           self.state[par].data_ptr(), self.rtab.data_ptr(), clamp.data_ptr(), mr, s)
+        agg.mask(par, s)
         self.comm.allgather_device(self.params[par], out=stack)
-        self.m.secagg_open(self.dims, bits, src.data_ptr(), self.world, own[par].data_ptr(), 1,
-                           self.state[par].data_ptr(), self.rtab.data_ptr(), self.world * self.tail_stride, mr, s)
+        agg.open(par, s)
 
     def server_step(self, r: int) -> None:
         """Server-optimizer step of round ``r`` on the aggregated image a caller summed into

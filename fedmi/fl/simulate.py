@@ -37,6 +37,7 @@ import torch
 
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
+from .aggregate import _AggLaunch
 from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine
 
 
@@ -107,9 +108,11 @@ class ClientGroup:
             self.clients.append(e)
         self.tamper = tamper
         self.wire = wire
-        self._secagg_tab = None   # hip, secure aggregation: device pointer tables (buffers per parity, clamp counts)
-        self._robust_tab = None   # hip, robust aggregators: device pointer tables of the k buffers, per parity
         if backend == "hip":
+            lead = self.clients[0]
+            if lead.robust or lead.secagg:   # in place over the k clients' buffers, client r = buffer r
+                bufs = [[e.params[q] for e in self.clients] for q in (0, 1)]
+                self._agg = _AggLaunch(lead, bufs, bufs, clamps=[e.sa_clamp for e in self.clients] if lead.secagg else ())
             self.stream = torch.cuda.Stream(device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             for e in self.clients:
@@ -130,29 +133,14 @@ class ClientGroup:
         if lead.robust:
             # one launch, in place: every client's buffer is a source and a destination; the round's
             # live flag, index and sampled mask are the lead client's (identical on all)
-            if self._robust_tab is None:
-                self._robust_tab = [torch.tensor([e.params[q].data_ptr() for e in self.clients], dtype=torch.int64,
-                                                 device=self.device) for q in (0, 1)]
-            tab = self._robust_tab[par].data_ptr()
-            lead.m.robust_aggregate(lead.dims, lead.robust, float(lead.cfg.trim_ratio), tab, self.k, tab, self.k,
-                                    lead.state[par].data_ptr(), lead.rtab.data_ptr(), self.k * lead.tail_stride,
-                                    int(lead.cfg.max_rounds), s)
+            self._agg.robust(par, s)
         elif lead.secagg:
-            # one mask launch over the k buffers, the wire hook, one open launch in place; the round's
-            # live flag, index and sampled mask are the lead client's (identical on all)
-            if self._secagg_tab is None:
-                i64 = dict(dtype=torch.int64, device=self.device)
-                self._secagg_tab = ([torch.tensor([e.params[q].data_ptr() for e in self.clients], **i64) for q in (0, 1)],
-                                    torch.tensor([e.sa_clamp.data_ptr() for e in self.clients], **i64))
-            tab, clamp = self._secagg_tab[0][par].data_ptr(), self._secagg_tab[1].data_ptr()
-            bits, mr = int(lead.cfg.secagg_bits), int(lead.cfg.max_rounds)
-            lead.m.secagg_mask(lead.dims, bits, lead.secagg_seed, tab, self.k, 0, lead.state[par].data_ptr(),
-                               lead.rtab.data_ptr(), clamp, mr, s)
+            # one mask launch over the k buffers, the wire hook, one open launch in place
+            self._agg.mask(par, s)
             if self.wire is not None:
                 with torch.cuda.stream(self.stream):
                     self.wire(r, bufs)
-            lead.m.secagg_open(lead.dims, bits, tab, self.k, tab, self.k, lead.state[par].data_ptr(),
-                               lead.rtab.data_ptr(), self.k * lead.tail_stride, mr, s)
+            self._agg.open(par, s)
         else:
             self._sum_hip(bufs)
         for e in self.clients:

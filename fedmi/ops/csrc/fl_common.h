@@ -70,24 +70,7 @@ struct MLPDesc {
     int lds_floats;                   // LDS floats needed per block
 };
 
-// Real parameters of the image's float4 that starts at float `idx` (a multiple of 4): its elements
-// j < fl_image_lim are parameters, the rest image padding (rows >= N, columns >= K, the 4 pad floats
-// of a row, bias slots >= N); <= 0: all padding.  The layer by compile-time-indexed selects; a
-// float4 lies in one row and one 4-float swizzle chunk (fl_ldw and the chunk swizzle are multiples
-// of 4).
-__host__ __device__ inline int fl_image_lim(const MLPDesc& d, int idx) {
-    int K = d.dim[0], N = d.dim[1], iwo = d.iw_off[0], ibo = d.ib_off[0];
-#pragma unroll
-    for (int t = 1; t < FL_MAX_LAYERS; ++t)
-        if (t < d.L && idx >= d.iw_off[t]) {
-            K = d.dim[t]; N = d.dim[t + 1]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-        }
-    if (idx >= ibo) return N - (idx - ibo);
-    const int ldw = fl_ldw(K);
-    const int q = idx - iwo;
-    const int n = q / ldw, c = q - n * ldw;
-    return n < N ? K - (c ^ fl_swz(n)) : 0;
-}
+// (dense index <-> image position, fl_image_index / fl_image_lim: fl_image.h)
 
 // bf16 LDS layout of the fused kernels (fl_kernels_bf16.hip).  All offsets are BYTES into
 // the dynamic LDS window.  Every fan-in dimension is padded to kp = roundup32(dim) (one

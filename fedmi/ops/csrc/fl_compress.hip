@@ -34,24 +34,10 @@
 // fedmi/fl/compress.py is the host model.
 #include "fl_common.h"
 #include "fl_device.h"
+#include "fl_image.h"
 
 #define FL_CP_THREADS 1024
 #define FL_CP_BINS 256
-
-// dense (named_parameters() order) index -> image position, as the Adam kernel maps it
-// (fl_adam_body.inc; fl_dp.hip dp_image_index)
-__device__ __forceinline__ int cp_image_index(const MLPDesc& d, int di) {
-    int K = d.dim[0], wo = d.w_off[0], bo = d.b_off[0], iwo = d.iw_off[0], ibo = d.ib_off[0];
-#pragma unroll
-    for (int t = 1; t < FL_MAX_LAYERS; ++t)
-        if (t < d.L && di >= d.w_off[t]) {
-            K = d.dim[t]; wo = d.w_off[t]; bo = d.b_off[t]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-        }
-    if (di >= bo) return ibo + (di - bo);
-    const int q = di - wo;
-    const int n = q / K, k = q - n * K;
-    return iwo + n * fl_ldw(K) + (k ^ fl_swz(n));
-}
 
 // One pass of a radix select.  `hist` holds the counts of the pass's digit over the entries still in
 // play; `want` (1 <= want <= their number) is the rank looked for, counted from the highest digit.
@@ -88,10 +74,9 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
     __shared__ int hist[FL_CP_BINS];
     __shared__ int sel[2];
     __shared__ float wsum[FL_CP_THREADS / 64];
-    if (!st->live) return;  // past a stop / max_rounds: the Adam kernel republished the global image
-    const int r = st->cur_round;
-    if (r < 0 || r >= p.max_rounds) return;
-    const float w = rtab[4 * (size_t)r];
+    int r;
+    if (!fl_round_gate(st, p.max_rounds, r)) return;  // past a stop / max_rounds: the Adam kernel republished the global image
+    const float w = fl_round_weight(rtab, r);
     const float* __restrict__ ein = p.residual + (size_t)(r & 1) * d.Pimg;
     float* __restrict__ eout = p.residual + (size_t)((r + 1) & 1) * d.Pimg;
     const int q = blockIdx.x * FL_CP_THREADS + threadIdx.x;  // block of 4 dense parameters
@@ -101,7 +86,7 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
         for (int k = 0; k < 4; ++k) {
             const int di = 4 * q + k;
             if (di < d.P) {
-                const int j = cp_image_index(d, di);
+                const int j = fl_image_index(d, di);
                 eout[j] = ein[j];
             }
         }
@@ -109,7 +94,6 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
     }
     const int P = d.P;
     const int per = (P + FL_CP_THREADS - 1) / FL_CP_THREADS;  // entries per thread: t, t + 1024, ...
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 
     // Entries are taken four at a time with unconditional loads (index clamped into the model), so a
     // thread has 12 global / 4 LDS loads in flight instead of waiting for each entry's in turn: one
@@ -120,7 +104,7 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int di = (it + i) * FL_CP_THREADS + threadIdx.x;
-            const int j = cp_image_index(d, di < P ? di : P - 1);
+            const int j = fl_image_index(d, di < P ? di : P - 1);
             a[i] = local[j]; x[i] = pg[j]; e[i] = ein[j];
         }
 #pragma unroll
@@ -138,13 +122,7 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
     unsigned thr = 0;       // top-k: key of the k-th largest magnitude
     int cut = 0;            // top-k: entries with that key are kept up to this dense index
     if (p.kind == FL_COMPRESS_SIGN) {
-        acc = wave_sum(acc);
-        if (lane == 0) wsum[wave] = acc;
-        __syncthreads();
-        float ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < FL_CP_THREADS / 64; ++k) ss = __fadd_rn(ss, wsum[k]);
-        s = __fdiv_rn(ss, (float)P);
+        s = __fdiv_rn(block_sum_ordered<FL_CP_THREADS>(acc, wsum), (float)P);
         if (blockIdx.x == 0 && threadIdx.x == 0) p.stat_hist[r] = s;
     } else {
         int want = p.k;
@@ -219,7 +197,7 @@ fl_compress_kernel(MLPDesc d, FLCompress p, const float* __restrict__ local, con
     for (int k = 0; k < 4; ++k) {
         const int di = 4 * q + k;
         if (di >= P) break;
-        const int j = cp_image_index(d, di);
+        const int j = fl_image_index(d, di);
         const float u = ubuf[di];
         float c, en;
         if (p.kind == FL_COMPRESS_SIGN) {

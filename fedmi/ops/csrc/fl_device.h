@@ -75,6 +75,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Sum over a workgroup of THREADS threads in ONE fixed order -- the xor tree over each wave, then
+// the waves' sums in wave order -- so every workgroup that adds the same values holds the same
+// bits.  `wsum`: THREADS / 64 floats of LDS.
+template <int THREADS>
+__device__ __forceinline__ float block_sum_ordered(float acc, float* wsum) {
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < THREADS / 64; ++k) ss = __fadd_rn(ss, wsum[k]);
+    return ss;
+}
+
 // ---------------------------------------------------------------------------------------
 // Metrics + early stopping on the device (reference C:85-90, C:165-195).
 // ---------------------------------------------------------------------------------------

@@ -21,39 +21,23 @@
 // fedmi/privacy/philox.py is the host model of the stream.
 #include "fl_common.h"
 #include "fl_device.h"
+#include "fl_image.h"
 #include "fl_philox.h"
 #include <math.h>
 
 #define FL_DP_THREADS 1024
 
-// dense (named_parameters() order) index -> image position, as the Adam kernel maps it
-// (fl_adam_body.inc): the layer's offsets by compile-time-indexed selects
-__device__ __forceinline__ int dp_image_index(const MLPDesc& d, int di) {
-    int K = d.dim[0], wo = d.w_off[0], bo = d.b_off[0], iwo = d.iw_off[0], ibo = d.ib_off[0];
-#pragma unroll
-    for (int t = 1; t < FL_MAX_LAYERS; ++t)
-        if (t < d.L && di >= d.w_off[t]) {
-            K = d.dim[t]; wo = d.w_off[t]; bo = d.b_off[t]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-        }
-    if (di >= bo) return ibo + (di - bo);
-    const int q = di - wo;
-    const int n = q / K, k = q - n * K;
-    return iwo + n * fl_ldw(K) + (k ^ fl_swz(n));
-}
-
 __global__ void __launch_bounds__(FL_DP_THREADS)
 fl_dp_kernel(MLPDesc d, FLDp p, const float* __restrict__ local, const float* __restrict__ pg,
              float* __restrict__ comm, const FLState* __restrict__ st, const float* __restrict__ rtab) {
     __shared__ float wsum[FL_DP_THREADS / 64];
-    if (!st->live) return;  // past a stop / max_rounds: the Adam kernel republished the global image
-    const int r = st->cur_round;
-    if (r < 0 || r >= p.max_rounds) return;
-    const float w = rtab[4 * (size_t)r];
+    int r;
+    if (!fl_round_gate(st, p.max_rounds, r)) return;  // past a stop / max_rounds: the Adam kernel republished the global image
+    const float w = fl_round_weight(rtab, r);
     if (w == 0.f) {  // not sampled this round: zeros from the Adam kernel, no noise
         if (blockIdx.x == 0 && threadIdx.x == 0) p.norm_hist[r] = 0.f;
         return;
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float acc = 0.f;
     const float4* l4 = reinterpret_cast<const float4*>(local);
     const float4* g4 = reinterpret_cast<const float4*>(pg);
@@ -65,13 +49,7 @@ fl_dp_kernel(MLPDesc d, FLDp p, const float* __restrict__ local, const float* __
         acc = __fmaf_rn(d2, d2, acc);
         acc = __fmaf_rn(d3, d3, acc);
     }
-    acc = wave_sum(acc);
-    if (lane == 0) wsum[wave] = acc;
-    __syncthreads();
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < FL_DP_THREADS / 64; ++k) ss += wsum[k];
-    const float nrm = sqrtf(ss);
+    const float nrm = sqrtf(block_sum_ordered<FL_DP_THREADS>(acc, wsum));
     if (blockIdx.x == 0 && threadIdx.x == 0) p.norm_hist[r] = nrm;
     const bool clipped = nrm > p.clip;
     if (!clipped && !p.noise) return;  // the Adam kernel's w * local stands
@@ -96,7 +74,7 @@ fl_dp_kernel(MLPDesc d, FLDp p, const float* __restrict__ local, const float* __
     for (int k = 0; k < 4; ++k) {
         const int di = 4 * q + k;
         if (di >= d.P) break;
-        const int j = dp_image_index(d, di);
+        const int j = fl_image_index(d, di);
         float t = local[j];
         if (clipped) {
             const float x = pg[j];

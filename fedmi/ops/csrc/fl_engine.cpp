@@ -1179,14 +1179,22 @@ static void synth(uintptr_t X, uintptr_t y, long long n, int F, unsigned long lo
                               as_ptr<const float>(w2), H, as_stream(stream), label_noise));
 }
 
+// Image descriptor of `dims` for the stand-alone launches below (`who` names the caller in the refusal).
+static MLPDesc desc_of(const std::vector<int>& dims, const char* who) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error(std::string(who) + ": 1..4 Linear layers supported");
+    MLPDesc d;
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    return d;
+}
+
 // Robust aggregate (fl_robust.hip) over K buffers of the image of `dims` + `tails_len` floats.  `src` /
 // `dst`: device tables of K / n_dst buffer addresses (int64); `state` / `rtab`: a client's round
 // state and per-round table.  Works across engines' buffers, so it is not an FLEngine phase.
 static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintptr_t src, int K, uintptr_t dst,
                              int n_dst, uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds,
                              uintptr_t stream) {
-    const int L = (int)dims.size() - 1;
-    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("robust_aggregate: 1..4 Linear layers supported");
+    const MLPDesc d = desc_of(dims, "robust_aggregate");
     if (K < 1 || K > FL_ROBUST_MAX_K)
         throw std::runtime_error("robust_aggregate: 1.." + std::to_string(FL_ROBUST_MAX_K) +
                                  " clients (the width of the sampled-client mask), got " + std::to_string(K));
@@ -1195,9 +1203,6 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
     if (!(beta >= 0.0 && beta < 0.5)) throw std::runtime_error("robust_aggregate: beta must be in [0, 0.5)");
     if (n_dst < 1 || n_dst > FL_ROBUST_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !dst || !state || !rtab)
         throw std::runtime_error("robust_aggregate: bad arguments");
-    MLPDesc d;
-    std::memset(&d, 0, sizeof(d));
-    fl_build_fp32_layout(dims.data(), L, 16, &d);
     FLRobust p;
     std::memset(&p, 0, sizeof(p));
     p.kind = kind;
@@ -1215,8 +1220,7 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
 static void secagg_mask(std::vector<int> dims, int bits, unsigned long long seed, uintptr_t bufs, int n,
                         int first_client, uintptr_t state, uintptr_t rtab, uintptr_t clamp, int max_rounds,
                         uintptr_t stream) {
-    const int L = (int)dims.size() - 1;
-    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("secagg_mask: 1..4 Linear layers supported");
+    const MLPDesc d = desc_of(dims, "secagg_mask");
     if (bits < FL_SECAGG_MIN_BITS || bits > FL_SECAGG_MAX_BITS)
         throw std::runtime_error("secagg_mask: bits must be in 8 .. 30, got " + std::to_string(bits));
     if (n < 1 || first_client < 0 || first_client + n > FL_SECAGG_MAX_K)
@@ -1224,9 +1228,6 @@ static void secagg_mask(std::vector<int> dims, int bits, unsigned long long seed
                                  " (the width of the sampled-client mask), got " + std::to_string(first_client) +
                                  " + " + std::to_string(n));
     if (max_rounds < 1 || !bufs || !state || !rtab || !clamp) throw std::runtime_error("secagg_mask: bad arguments");
-    MLPDesc d;
-    std::memset(&d, 0, sizeof(d));
-    fl_build_fp32_layout(dims.data(), L, 16, &d);
     FLSecAgg p;
     std::memset(&p, 0, sizeof(p));
     p.bits = bits;
@@ -1241,8 +1242,7 @@ static void secagg_mask(std::vector<int> dims, int bits, unsigned long long seed
 
 static void secagg_open(std::vector<int> dims, int bits, uintptr_t src, int K, uintptr_t dst, int n_dst,
                         uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds, uintptr_t stream) {
-    const int L = (int)dims.size() - 1;
-    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("secagg_open: 1..4 Linear layers supported");
+    const MLPDesc d = desc_of(dims, "secagg_open");
     if (bits < FL_SECAGG_MIN_BITS || bits > FL_SECAGG_MAX_BITS)
         throw std::runtime_error("secagg_open: bits must be in 8 .. 30, got " + std::to_string(bits));
     if (K < 1 || K > FL_SECAGG_MAX_K)
@@ -1250,9 +1250,6 @@ static void secagg_open(std::vector<int> dims, int bits, uintptr_t src, int K, u
                                  " clients (the width of the sampled-client mask), got " + std::to_string(K));
     if (n_dst < 1 || n_dst > FL_SECAGG_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !dst || !state || !rtab)
         throw std::runtime_error("secagg_open: bad arguments");
-    MLPDesc d;
-    std::memset(&d, 0, sizeof(d));
-    fl_build_fp32_layout(dims.data(), L, 16, &d);
     FLSecAgg p;
     std::memset(&p, 0, sizeof(p));
     p.bits = bits;
@@ -1269,15 +1266,11 @@ static void secagg_open(std::vector<int> dims, int bits, uintptr_t src, int K, u
 static void compress_launch(std::vector<int> dims, int kind, int k, bool error_feedback, uintptr_t local, uintptr_t x,
                             uintptr_t comm, uintptr_t residual, uintptr_t stat, uintptr_t state, uintptr_t rtab,
                             int max_rounds, uintptr_t stream) {
-    const int L = (int)dims.size() - 1;
-    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error("compress_launch: 1..4 Linear layers supported");
+    const MLPDesc d = desc_of(dims, "compress_launch");
     if (kind != FL_COMPRESS_TOPK && kind != FL_COMPRESS_SIGN)
         throw std::runtime_error("compress_launch: kind must be 1 (topk) or 2 (sign)");
     if (max_rounds < 1 || !local || !x || !comm || !residual || !stat || !state || !rtab)
         throw std::runtime_error("compress_launch: bad arguments");
-    MLPDesc d;
-    std::memset(&d, 0, sizeof(d));
-    fl_build_fp32_layout(dims.data(), L, 16, &d);
     if (kind == FL_COMPRESS_SIGN) k = d.P;
     if (k < 1 || k > d.P) throw std::runtime_error("compress_launch: k must be in 1 .. P");
     FLCompress p;

@@ -40,6 +40,7 @@
 // their own; the tails run in workgroups of their own (no wave mixes the two paths).  Plain vector
 // stores only.
 #include "fl_common.h"
+#include "fl_image.h"
 
 #define FL_ROBUST_THREADS 64
 
@@ -48,30 +49,6 @@ __device__ __forceinline__ uint32_t robust_key(float x) {
     const uint32_t u = __float_as_uint(x);
     const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return (u & 0x7fffffffu) > 0x7f800000u ? 0xfffffffeu : (u == 0x80000000u ? 0x80000000u : k);
-}
-
-// Clients' values of a float / float4 at float `idx`: all loads issued, nothing used.
-template <int KB, int VEC>
-__device__ __forceinline__ void robust_load(const float* const* __restrict__ src, int K, int idx, float (&v)[KB][VEC]) {
-#pragma unroll
-    for (int i = 0; i < KB; ++i) {
-        const float* s = src[i < K ? i : K - 1];
-        if constexpr (VEC == 4) {
-            const float4 x = *reinterpret_cast<const float4*>(s + idx);
-            v[i][0] = x.x; v[i][1] = x.y; v[i][2] = x.z; v[i][3] = x.w;
-        } else {
-            v[i][0] = s[idx];
-        }
-    }
-}
-
-// Left fold in source order (tails; rounds that are not live).
-template <int KB, int VEC>
-__device__ __forceinline__ float robust_fold(const float (&v)[KB][VEC], int K, int e) {
-    float acc = v[0][e];
-#pragma unroll
-    for (int i = 1; i < KB; ++i) acc = i < K ? __fadd_rn(acc, v[i][e]) : acc;
-    return acc;
 }
 
 // Median / trimmed mean of column e: ranks in [lo, hi) are kept, n = float(hi - lo).
@@ -107,9 +84,7 @@ fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, fl
         // metric tails: one float per thread
         const int j = ((int)blockIdx.x - img_blocks) * FL_ROBUST_THREADS + threadIdx.x;
         if (j >= tails_len) return;
-        float v[KB][1];
-        robust_load<KB, 1>(src, p.K, d.Pimg + j, v);
-        const float out = robust_fold<KB, 1>(v, p.K, 0);
+        const float out = fl_src_fold<KB, KB>(src, p.K, d.Pimg + j);  // (K <= KB, the launcher's bucket)
         for (int q = 0; q < n_dst; ++q) dst[q][d.Pimg + j] = out;
         return;
     }
@@ -117,22 +92,15 @@ fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, fl
     const int idx = VEC * u;
     if (idx >= d.Pimg) return;
     float v[KB][VEC];
-    robust_load<KB, VEC>(src, p.K, idx, v);
+    fl_src_load<KB, VEC>(src, p.K, 0, idx, v);
     // the round's sampled clients
-    uint64_t mask = 0;
-    if (st->live) {
-        const int r = st->cur_round;
-        if (r >= 0 && r < p.max_rounds) {
-            const uint32_t* rt = reinterpret_cast<const uint32_t*>(p.rtab) + 4 * (size_t)r;
-            mask = ((uint64_t)rt[3] << 32) | rt[2];
-            if (p.K < 64) mask &= (1ull << p.K) - 1ull;
-        }
-    }
+    int r;
+    const uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r, p.K) : 0;
     const int kr = __popcll(mask);
     float out[VEC];
     if (kr == 0) {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) out[e] = robust_fold<KB, VEC>(v, p.K, e);
+        for (int e = 0; e < VEC; ++e) out[e] = fl_fold_loaded<KB, VEC>(v, p.K, 0, e, 0.f);
     } else {
         const int t = fl_robust_trim(p.kind, p.beta, kr);
         const float n = (float)(kr - 2 * t);

@@ -38,33 +38,11 @@
 // workgroups of their own.  No float atomics, no LDS, no grid barrier, plain vector stores; no
 // per-round host argument, so both launches are replayable.
 #include "fl_common.h"
+#include "fl_image.h"
 #include "fl_philox.h"
 
 #define FL_SECAGG_THREADS 64
 #define FL_SECAGG_BATCH 8
-
-// dense (named_parameters() order) index -> image position, as the Adam kernel maps it
-// (fl_adam_body.inc; fl_dp.hip dp_image_index)
-__device__ __forceinline__ int sa_image_index(const MLPDesc& d, int di) {
-    int K = d.dim[0], wo = d.w_off[0], bo = d.b_off[0], iwo = d.iw_off[0], ibo = d.ib_off[0];
-#pragma unroll
-    for (int t = 1; t < FL_MAX_LAYERS; ++t)
-        if (t < d.L && di >= d.w_off[t]) {
-            K = d.dim[t]; wo = d.w_off[t]; bo = d.b_off[t]; iwo = d.iw_off[t]; ibo = d.ib_off[t];
-        }
-    if (di >= bo) return ibo + (di - bo);
-    const int q = di - wo;
-    const int n = q / K, k = q - n * K;
-    return iwo + n * fl_ldw(K) + (k ^ fl_swz(n));
-}
-
-// The round's sampled-client mask; 0: the round is not live (past a stop / outside [0, max_rounds)).
-__device__ __forceinline__ uint64_t sa_round_mask(const FLSecAgg& p, const FLState* __restrict__ st, int& r) {
-    r = st->cur_round;
-    if (!st->live || r < 0 || r >= p.max_rounds) return 0;
-    const uint32_t* rt = reinterpret_cast<const uint32_t*>(p.rtab) + 4 * (size_t)r;
-    return ((uint64_t)rt[3] << 32) | rt[2];
-}
 
 // Fixed-point image of a contribution: clamp(rint(c * 2^F), -L, L), +-inf -> +-L, NaN -> 0; `bad`: the
 // coordinate was clamped or NaN.  The product is exact (a power of two) or inf; the compare is an integer one.
@@ -81,7 +59,7 @@ __global__ void __launch_bounds__(FL_SECAGG_THREADS)
 fl_secagg_mask_kernel(MLPDesc d, FLSecAgg p, float* const* __restrict__ bufs, uint32_t* const* __restrict__ clamp,
                       const FLState* __restrict__ st) {
     int r;
-    const uint64_t mask = sa_round_mask(p, st, r);
+    const uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r) : 0;
     const int me = p.first_client + (int)blockIdx.y;
     if (!((mask >> me) & 1)) return;  // not live, or not sampled: the buffer stands (block-uniform)
     const int L = 0x7fffffff / __popcll(mask);
@@ -94,7 +72,7 @@ fl_secagg_mask_kernel(MLPDesc d, FLSecAgg p, float* const* __restrict__ bufs, ui
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int di = 4 * q + k;
-            j[k] = sa_image_index(d, di < d.P ? di : d.P - 1);
+            j[k] = fl_image_index(d, di < d.P ? di : d.P - 1);
             c[k] = comm[j[k]];
         }
         // (a partial last quad re-read parameter P - 1 in its spare slots: neither counted nor stored)
@@ -122,23 +100,6 @@ fl_secagg_mask_kernel(MLPDesc d, FLSecAgg p, float* const* __restrict__ bufs, ui
     if (threadIdx.x == 0 && cnt) atomicAdd(&clamp[blockIdx.y][r], (uint32_t)cnt);
 }
 
-// Sources [i0, i0 + FL_SECAGG_BATCH) of a float / float4 at float `idx`: all loads issued, nothing
-// used; slots past K re-read source K - 1.
-template <int VEC>
-__device__ __forceinline__ void sa_load(const float* const* __restrict__ src, int K, int i0, int idx,
-                                        float (&v)[FL_SECAGG_BATCH][VEC]) {
-#pragma unroll
-    for (int i = 0; i < FL_SECAGG_BATCH; ++i) {
-        const float* s = src[i0 + i < K ? i0 + i : K - 1];
-        if constexpr (VEC == 4) {
-            const float4 x = *reinterpret_cast<const float4*>(s + idx);
-            v[i][0] = x.x; v[i][1] = x.y; v[i][2] = x.z; v[i][3] = x.w;
-        } else {
-            v[i][0] = s[idx];
-        }
-    }
-}
-
 __global__ void __launch_bounds__(FL_SECAGG_THREADS)
 fl_secagg_open_kernel(MLPDesc d, FLSecAgg p, const float* const* __restrict__ src, float* const* __restrict__ dst,
                       int n_dst, const FLState* __restrict__ st, int tails_len, int img_blocks) {
@@ -146,33 +107,25 @@ fl_secagg_open_kernel(MLPDesc d, FLSecAgg p, const float* const* __restrict__ sr
         // metric tails: one float per thread, the left fold in source order
         const int j = ((int)blockIdx.x - img_blocks) * FL_SECAGG_THREADS + threadIdx.x;
         if (j >= tails_len) return;
-        float acc = 0.f;
-        for (int i0 = 0; i0 < p.K; i0 += FL_SECAGG_BATCH) {
-            float v[FL_SECAGG_BATCH][1];
-            sa_load<1>(src, p.K, i0, d.Pimg + j, v);
-#pragma unroll
-            for (int i = 0; i < FL_SECAGG_BATCH; ++i)
-                acc = i0 + i == 0 ? v[i][0] : (i0 + i < p.K ? __fadd_rn(acc, v[i][0]) : acc);
-        }
+        const float acc = fl_src_fold<FL_SECAGG_BATCH, FL_SECAGG_MAX_K>(src, p.K, d.Pimg + j);
         for (int q = 0; q < n_dst; ++q) dst[q][d.Pimg + j] = acc;
         return;
     }
     const int idx = 4 * (blockIdx.x * FL_SECAGG_THREADS + threadIdx.x);
     if (idx >= d.Pimg) return;
     int r;
-    uint64_t mask = sa_round_mask(p, st, r);
-    if (p.K < 64) mask &= (1ull << p.K) - 1ull;
+    const uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r, p.K) : 0;
     uint32_t S[4] = {0u, 0u, 0u, 0u};
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i0 = 0; i0 < p.K; i0 += FL_SECAGG_BATCH) {
         float v[FL_SECAGG_BATCH][4];
-        sa_load<4>(src, p.K, i0, idx, v);
+        fl_src_load<FL_SECAGG_BATCH, 4>(src, p.K, i0, idx, v);
 #pragma unroll
         for (int i = 0; i < FL_SECAGG_BATCH; ++i) {
             const bool in = i0 + i < p.K;
             const bool on = in && ((mask >> ((i0 + i) & 63)) & 1);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
+            for (int e = 0; e < 4; ++e) {  // the integer sum, and beside it the left fold of a round that is not live
                 S[e] += on ? __float_as_uint(v[i][e]) : 0u;
                 acc[e] = i0 + i == 0 ? v[i][e] : (in ? __fadd_rn(acc[e], v[i][e]) : acc[e]);
             }

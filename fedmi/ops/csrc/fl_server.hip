@@ -39,6 +39,7 @@
 //     image always matches the fp32 image the next round reads.
 #include "fl_common.h"
 #include "fl_bf16.h"
+#include "fl_image.h"
 
 #define FL_SERVER_THREADS 64
 
@@ -76,19 +77,14 @@ __device__ __forceinline__ void server_quad(const FLServer& p, bool r0, bool r1,
     server_elem<KIND>(p, r3, x.w, a.w, m.w, v.w);
 }
 
-__device__ __forceinline__ bool server_live(const FLServer& p, const FLState* __restrict__ st) {
-    if (!st->live) return false;
-    const int r = st->cur_round;
-    return r >= 0 && r < p.max_rounds;
-}
-
 // fp32 mode: float4 i of the image.  Its layer by compile-time-indexed selects; a float4 lies in one
 // row and one 4-float swizzle chunk (fl_ldw and the chunk swizzle are multiples of 4).
 template <int KIND>
 __global__ void __launch_bounds__(FL_SERVER_THREADS)
 fl_server_kernel(MLPDesc d, FLServer p, const float* __restrict__ xg, float* __restrict__ ag,
                  const FLState* __restrict__ st) {
-    if (!server_live(p, st)) return;
+    int r;
+    if (!fl_round_gate(st, p.max_rounds, r)) return;
     const int i = blockIdx.x * FL_SERVER_THREADS + threadIdx.x;
     if (i >= (d.Pimg >> 2)) return;
     const float4 x = reinterpret_cast<const float4*>(xg)[i];
@@ -108,7 +104,8 @@ template <int KIND>
 __global__ void __launch_bounds__(FL_SERVER_THREADS)
 fl_server_pack_kernel(MLPDesc d, MLPDescB e, FLServer p, const float* __restrict__ xg, float* __restrict__ ag,
                       const FLState* __restrict__ st, char* __restrict__ out) {
-    const bool step = server_live(p, st);
+    int r;
+    const bool step = fl_round_gate(st, p.max_rounds, r);
     const int id = blockIdx.x * FL_SERVER_THREADS + threadIdx.x;
     const int total = e.item_base[d.L];
     if (id < total) {

@@ -120,8 +120,8 @@ def _host_rows(c, part, r, bits):
 
 
 KERNEL_CASES = [(SMALL, 2, [0, 1]), (SMALL, 5, [0, 2, 4]), (SMALL, 8, list(range(8))), (SMALL, 64, list(range(64))),
-                (INCOME, 8, list(range(8)))]
-KERNEL_IDS = ["small-2", "small-3of5", "small-8", "small-64", "income-8"]
+                (INCOME, 8, list(range(8))), (SMALL, 9, [0, 2, 4, 6, 8])]
+KERNEL_IDS = ["small-2", "small-3of5", "small-8", "small-64", "income-8", "small-5of9"]
 
 
 # ---- 1. the mask kernel ----
