@@ -88,6 +88,10 @@ def parse_args(argv=None):
     ap.add_argument("--secagg-bits", type=int, default=24, help="--secagg: fractional bits of the fixed point, 8 .. 30")
     ap.add_argument("--secagg-seed", type=int, default=None,
                     help="--secagg: mask seed of the group (default: one private draw; no result depends on it)")
+    ap.add_argument("--gather-plane", choices=["host", "xgmi"], default="host",
+                    help="robust --aggregator / --secagg on several ranks: host = every rank's buffer gathered over the "
+                         "host plane; xgmi = the rule runs inside the one-shot xGMI peer kernel (at most 8 ranks; rounds "
+                         "are graph-captured; falls back to host when the peer plane is unavailable). Same results")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -198,6 +202,10 @@ def _secagg_fields(a) -> dict:
     return dict(secagg=a.secagg, secagg_bits=a.secagg_bits, secagg_seed=a.secagg_seed)
 
 
+def _gather_fields(a) -> dict:
+    return dict(gather_plane=a.gather_plane)
+
+
 def _print_privacy(a, rounds: int) -> None:
     """The run's (epsilon, delta) on one line (fedmi/privacy/accountant.py)."""
     if a.dp_clip > 0.0:
@@ -220,7 +228,7 @@ def main_clients(a, comm):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
                        **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a),
-                       **_secagg_fields(a))
+                       **_secagg_fields(a), **_gather_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -302,7 +310,7 @@ def main(argv=None):
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
                        debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
-                       **_compress_fields(a), **_secagg_fields(a))
+                       **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

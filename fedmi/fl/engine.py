@@ -174,6 +174,14 @@ class EngineConfig:
     secagg: bool = False
     secagg_bits: int = 24
     secagg_seed: Optional[int] = None
+    # Data plane of a robust aggregator / secure aggregation on a multi-rank HipRoundEngine: "host" = every
+    # rank's buffer gathered over the host plane, the rule launched from Python (aggregation 'host-gather');
+    # "xgmi" = the one-shot xGMI peer kernel selects / opens instead of summing (peer_allreduce.hip
+    # peer_select_kernel; aggregation 'xgmi-select'): the native engine aggregates, so rounds are traced and
+    # graph-captured like any peer engine's.  At most 8 ranks; if the peer set-up fails on every rank they
+    # warn and continue on the host gather.  A run-time choice, not state: results are bitwise equal on both
+    # planes.  Ignored by every other engine kind (one client, the weighted mean, ClientGroup, torch).
+    gather_plane: str = "host"
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -251,6 +259,16 @@ def aggregator_id(cfg: EngineConfig) -> int:
     return kind
 
 
+GATHER_PLANES = ("host", "xgmi")
+
+
+def gather_plane_id(cfg: EngineConfig) -> int:
+    """Validate ``gather_plane``; the plane's index in ``GATHER_PLANES`` (0 = the host gather)."""
+    if not isinstance(cfg.gather_plane, str) or cfg.gather_plane not in GATHER_PLANES:
+        raise ValueError(f"gather_plane must be one of {GATHER_PLANES}, got {cfg.gather_plane!r}")
+    return GATHER_PLANES.index(cfg.gather_plane)
+
+
 def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, m: torch.Tensor,
                 v: Optional[torch.Tensor]) -> torch.Tensor:
     """One server-optimizer step in the tensors' dtype: updates ``m`` (and ``v``) in place and
@@ -323,6 +341,7 @@ class RoundEngineBase:
         self.dp = dp_enabled(cfg)
         self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
         self.compress = compress_id(cfg)   # index in COMPRESSORS; 0 = dense contributions
+        gather_plane_id(cfg)               # validated by every engine; only a multi-rank HIP engine reads it
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
@@ -967,6 +986,13 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
         if bool(cfg.secagg) and comm_buffers is not None:
             raise ValueError("trial packing (comm_buffers) does not run secure aggregation (secagg)")
+        # robust rule / secure aggregation over the one-shot xGMI peer kernel: one node's ranks at most
+        from ..parallel.peer import PEER_MAX_WORLD
+        xgmi_select = (bool(gather_plane_id(cfg)) and comm is not None and int(comm.size) > 1
+                       and (aggregator_id(cfg) != 0 or bool(secagg_id(cfg))))
+        if xgmi_select and int(comm.size) > PEER_MAX_WORLD:
+            raise ValueError(f"gather_plane='xgmi' takes at most {PEER_MAX_WORLD} ranks (the peers of one node), "
+                             f"got {int(comm.size)}; use gather_plane='host'")
         self.m = native()
         if device is None:
             device = comm.device if comm is not None else torch.device("cuda", torch.cuda.current_device())
@@ -1001,9 +1027,11 @@ class HipRoundEngine(RoundEngineBase):
         # which folds each round's metrics in time, or over RCCL, folded one round late with the
         # round run past a stop discarded bit-exactly: FLEngine.late_fold)
         # (differential privacy: classic rounds, see fl_engine.cpp)
-        # (robust aggregators: classic rounds aggregated from Python, see _aggregate)
+        # (robust aggregators: classic rounds aggregated from Python, see _aggregate, or by the peer
+        # kernel's select call, gather_plane="xgmi")
         # (compression: classic rounds, as with differential privacy)
-        # (secure aggregation: classic rounds masked and opened from Python, see _aggregate)
+        # (secure aggregation: classic rounds masked and opened from Python, see _aggregate, or by the
+        # native engine on the peer plane, gather_plane="xgmi")
         self._lag = ((self.world > 1 or emulate_clients) and cfg.dtype == "bf16"
                      and comm_buffers is None and bool(cfg.lagged_eval) and not self.dp and not self.server
                      and not self.robust and not self.compress and not self.secagg)
@@ -1091,6 +1119,17 @@ class HipRoundEngine(RoundEngineBase):
                          "server_momentum": float(cfg.server_momentum), "server_beta2": float(cfg.server_beta2),
                          "server_tau": float(cfg.server_tau)})
             bufs.update({"server_m": self.server_m.data_ptr(), "server_v": self.server_v.data_ptr()})
+        if self.secagg:
+            # this client's clamped / NaN coordinates per round (uint32 words; integer atomics of fl_secagg.hip)
+            self.sa_clamp = torch.zeros(mr, dtype=torch.int32, device=dev)
+        # gather_plane="xgmi": the native engine aggregates with the peer kernel's select / open call once the
+        # peer plane is attached below (it needs the rule's parameters; the host plane launches from Python)
+        want_select = xgmi_select and bool(self.robust or self.secagg) and comm_buffers is None
+        if want_select and self.robust:
+            ecfg.update({"robust": int(self.robust), "trim_ratio": float(cfg.trim_ratio)})
+        elif want_select:
+            ecfg.update({"secagg": True, "secagg_bits": int(cfg.secagg_bits), "secagg_seed": int(self.secagg_seed)})
+            bufs["sa_clamp"] = self.sa_clamp.data_ptr()
         for i, R in enumerate(R_try):
             self.slab = torch.zeros(((self.n_local + R - 1) // R) * slab_stride, **f32)
             ecfg["R"] = R
@@ -1106,8 +1145,6 @@ class HipRoundEngine(RoundEngineBase):
         self.layout["aggregator"] = AGGREGATORS[self.robust]   # the rule that runs (one client: the identity)
         if self.secagg:
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
-            # this client's clamped / NaN coordinates per round (uint32 words; integer atomics of fl_secagg.hip)
-            self.sa_clamp = torch.zeros(mr, dtype=torch.int32, device=dev)
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -1120,8 +1157,9 @@ class HipRoundEngine(RoundEngineBase):
         self._native_comm = None
         # one-shot xGMI all-reduce of [image | tails] (collective set-up; None -> RCCL)
         self._peer = None
-        # (a robust aggregator and secure aggregation gather over the host plane: neither the peer plane
-        # nor RCCL is set up -- every rank shares the config, so that is collectively consistent)
+        # (a robust aggregator and secure aggregation gather over the host plane -- neither the sum's peer
+        # plane nor RCCL is set up; every rank shares the config, so that is collectively consistent -- or,
+        # with gather_plane="xgmi", aggregate inside the peer kernel: the select set-up below)
         self._agg = None   # gathered stack + launcher of the aggregation kernels over it (_gather_launch)
         if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust \
                 and not self.secagg:
@@ -1133,6 +1171,21 @@ class HipRoundEngine(RoundEngineBase):
             self._peer = make_peer_allreduce(comm, comm_len, dev, n_chunks=n_chunks)
             if self._peer is not None:
                 self.engine.attach_peer(self._peer)
+        if want_select:
+            # the peer kernel selects / opens instead of summing: no chunk flags (classic rounds); a set-up
+            # that fails does so on every rank (make_peer_allreduce), and every rank then stays on the host gather
+            if getattr(comm, "peer_allreduce", False):
+                from ..parallel.peer import make_peer_allreduce
+                torch.cuda.synchronize(dev)
+                self._peer = make_peer_allreduce(comm, comm_len, dev, n_chunks=0)
+            if self._peer is not None:
+                self.engine.attach_peer(self._peer)
+                self.layout["peer_select"] = self.engine.layout()["peer_select"]
+            else:
+                import warnings
+                warnings.warn("gather_plane='xgmi': the one-shot xGMI peer plane is unavailable on this communicator; "
+                              "aggregating over the host gather", RuntimeWarning, stacklevel=2)
+        self.layout["gather_plane"] = "xgmi" if (want_select and self._peer is not None) else "host"
         if self.world > 1 and self._peer is None and comm_buffers is None and comm is not None \
                 and hasattr(comm, "rccl") and not self.robust and not self.secagg:
             # RCCL only when the peer plane is off or fell back (every rank agreed on that above),
@@ -1224,11 +1277,12 @@ class HipRoundEngine(RoundEngineBase):
     @property
     def aggregation(self) -> str:
         """Data plane of the FedAvg all-reduce: 'none' (one client), 'xgmi-oneshot', 'rccl' or 'host';
-        'host-gather': a robust aggregator, or secure aggregation, over every rank's gathered buffer."""
+        'host-gather': a robust aggregator, or secure aggregation, over every rank's gathered buffer;
+        'xgmi-select': the same rules inside the one-shot xGMI peer kernel (``gather_plane='xgmi'``)."""
         if self.world == 1:
             return "none"
         if self.robust or self.secagg:
-            return "host-gather"
+            return "xgmi-select" if self._peer is not None else "host-gather"
         if self._peer is not None:
             return "xgmi-oneshot+adam" if self.engine.adam_exchange else "xgmi-oneshot"
         return "rccl" if self._native_comm is not None else "host"
@@ -1538,6 +1592,8 @@ class HipRoundEngine(RoundEngineBase):
                         m["norm"].copy_(self.dp_norm, non_blocking=True)
                     if self.compress:
                         m["cstat"].copy_(self.cp_stat, non_blocking=True)
+                    if self.secagg:
+                        m["clamp"].copy_(self.sa_clamp, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -1572,7 +1628,8 @@ class HipRoundEngine(RoundEngineBase):
             mk = lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
             self._mirror = [{"state": mk(self.state[0]), "glob": mk(self.h_global), "rank": mk(self.h_rank),
                              "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {}),
-                             **({"cstat": mk(self.cp_stat)} if self.compress else {})}
+                             **({"cstat": mk(self.cp_stat)} if self.compress else {}),
+                             **({"clamp": mk(self.sa_clamp)} if self.secagg else {})}
                             for _ in range(2)]
         return self._mirror
 
@@ -1588,6 +1645,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.norm[:n] = m["norm"][:n].numpy()
             if self.compress:
                 self.hist.cstat[:n] = m["cstat"][:n].numpy()
+            if self.secagg:
+                self.hist.clamped[:n] = m["clamp"][:n].numpy().view(np.uint32)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1

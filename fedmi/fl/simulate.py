@@ -38,7 +38,7 @@ import torch
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
 from .aggregate import _AggLaunch
-from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine
+from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, gather_plane_id
 
 
 class SimRank:
@@ -93,6 +93,8 @@ class ClientGroup:
             if backend == "hip":
                 c.lagged_eval = False    # classic rounds: each client evaluates itself
                 c.graph_rounds = 0
+                gather_plane_id(c)       # (validated; the group aggregates in place over its clients' buffers)
+                c.gather_plane = "host"
             comm = SimRank(self.k, r, self.device)
             # FederatedMLPLearning's seeding: one init stream per (seed, rank)
             # (server optimizer: one common starting model, see FederatedMLPLearning)

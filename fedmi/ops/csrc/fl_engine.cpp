@@ -330,6 +330,37 @@ class FLEngine {
             if (sv_.m == nullptr || (sv_.kind != FL_SERVER_SGD && sv_.v == nullptr))
                 throw std::runtime_error("FLEngine: the server optimizer needs its state buffers");
         }
+        // Aggregation rule of a multi-rank engine on the peer plane (peer_select.h): a robust aggregator
+        // selects, secure aggregation masks this rank's send buffer and opens -- instead of the sum.
+        // Used only once a peer is attached (attach_peer); over RCCL such an engine refuses to aggregate.
+        std::memset(&sel_, 0, sizeof(sel_));
+        {
+            const int robust = cfg.contains("robust") ? cfg["robust"].cast<int>() : 0;
+            const bool secagg = cfg.contains("secagg") && cfg["secagg"].cast<bool>();
+            if (robust && secagg) throw std::runtime_error("FLEngine: secure aggregation does not combine with a robust rule");
+            if (robust && tr_.dp_on)
+                throw std::runtime_error("FLEngine: a robust rule does not combine with differential privacy");
+            if (robust) {
+                if (robust != FL_ROBUST_MEDIAN && robust != FL_ROBUST_TRIMMED)
+                    throw std::runtime_error("FLEngine: unknown robust rule");
+                sel_.mode = PEER_SELECT_ROBUST;
+                sel_.rb.kind = robust;
+                sel_.rb.K = c_.world;
+                sel_.rb.max_rounds = c_.max_rounds;
+                sel_.rb.beta = cfg["trim_ratio"].cast<double>();
+            } else if (secagg) {
+                const unsigned long long seed = cfg["secagg_seed"].cast<unsigned long long>();
+                sel_.mode = PEER_SELECT_OPEN;
+                sel_.sa.bits = cfg["secagg_bits"].cast<int>();
+                sel_.sa.K = c_.world;
+                sel_.sa.first_client = c_.rank;
+                sel_.sa.max_rounds = c_.max_rounds;
+                sel_.sa.key0 = (uint32_t)seed;
+                sel_.sa.key1 = (uint32_t)(seed >> 32);
+                sa_clamp_ = as_ptr<uint32_t>(bufs["sa_clamp"].cast<uintptr_t>());
+                if (sa_clamp_ == nullptr) throw std::runtime_error("FLEngine: secure aggregation needs the clamp history");
+            }
+        }
         {
             // The fused evaluation + FedAvg grid (evaluation blocks + all-reduce blocks) must be
             // resident in one wave, which needs two evaluation workgroups per CU (measured: with one
@@ -438,6 +469,7 @@ class FLEngine {
     ~FLEngine() {
         drop_graph();
         if (undo_) (void)hipFree(undo_);
+        if (sa_tab_) (void)hipFree(sa_tab_);
         if (pk_) (void)hipFree(pk_);
         if (lagbuf_) (void)hipFree(lagbuf_);
     }
@@ -615,9 +647,26 @@ class FLEngine {
             throw std::runtime_error("attach_peer: communicator does not match this engine");
         if (p.n_floats() != comm_len_)
             throw std::runtime_error("attach_peer: buffer length != parameter image + tails");
+        if (sel_.mode != 0 && (p.n_chunks() != 0 || tr_.lag_ok))
+            throw std::runtime_error("attach_peer: a selecting engine runs classic rounds on a communicator without "
+                                     "chunk flags");
         drop_graph();
         peer_ = &p;
         tr_.has_peer = true;
+        if (sel_.mode != 0) {
+            // gather-select rounds are classic: train/Adam pairs, the optional DP or compression
+            // launch, the evaluation, then the ALLREDUCE record (select / mask + open) and the optional
+            // server step -- no fused evaluation + FedAvg kernel, which sums
+            tr_.eval_fedavg_fits = false;
+            sel_.d = d_;
+            sel_.rb.rtab = sel_.sa.rtab = b_.rtab;
+            if (sel_.mode == PEER_SELECT_OPEN) {
+                // device pointer tables of the mask launch: this rank's two send buffers, its clamp history
+                if (sa_tab_ == nullptr) HIP_CHECK(hipMalloc(&sa_tab_, 3 * sizeof(void*)));
+                void* tab[3] = {p.send(0), p.send(1), sa_clamp_};
+                HIP_CHECK(hipMemcpy(sa_tab_, tab, sizeof(tab), hipMemcpyHostToDevice));
+            }
+        }
         fill_bases();
         p.prepare_eval((c_.n_rows + c_.R - 1) / c_.R);
         // lagged rounds reduce inside the Adam kernel when the communicator has a chunk-flag
@@ -781,6 +830,9 @@ class FLEngine {
                                                          : fl_train_spec_ok(d_, c_, FL_EVAL_FUSED));
         o["adam_spec"] = adam_spec_ok();  // the Adam kernel of those rounds is the specialised one
         o["eval_fedavg"] = peer_ != nullptr && !tr_.fused && tr_.eval_fedavg_fits;
+        // the peer call selects / opens instead of summing (peer_select.h): "none", "robust", "secagg"
+        o["peer_select"] = std::string(peer_ == nullptr || sel_.mode == 0 ? "none"
+                                       : sel_.mode == PEER_SELECT_ROBUST ? "robust" : "secagg");
         o["dtype"] = dtype_;
         o["slab_stride"] = c_.slab_stride;
         o["n_slabs"] = c_.n_slabs;
@@ -883,8 +935,21 @@ class FLEngine {
                 else HIP_CHECK(fl_launch_eval_bf16(d_, ev_, c_, b_, F(0), F(1), S(2), s));
                 break;
             case FLLaunchRec::ALLREDUCE:
-                if (peer_ != nullptr) HIP_CHECK(peer_->launch(m.par, pbuf_[m.par], dtype_ == 1 ? &pp_ : nullptr, s));
-                else comm->allreduce_f32((uintptr_t)pbuf_[m.par], (size_t)comm_len_, (uintptr_t)s);
+                if (sel_.mode != 0) {
+                    // robust rule / secure aggregation: select or open over the peers' send buffers under the
+                    // round's state (that of the output parity); never a sum
+                    if (peer_ == nullptr)
+                        throw std::runtime_error("FLEngine: a robust rule / secure aggregation aggregates over the "
+                                                 "peer plane or from the caller, not over RCCL");
+                    if (sel_.mode == PEER_SELECT_OPEN)  // this rank's contribution becomes its masked words, in place
+                        HIP_CHECK(fl_launch_secagg_mask(d_, sel_.sa, (float* const*)sa_tab_ + m.par, 1,
+                                                        (uint32_t* const*)sa_tab_ + 2, st_[m.par], s));
+                    HIP_CHECK(peer_->launch_select(m.par, pbuf_[m.par], dtype_ == 1 ? &pp_ : nullptr, sel_, st_[m.par], s));
+                } else if (peer_ != nullptr) {
+                    HIP_CHECK(peer_->launch(m.par, pbuf_[m.par], dtype_ == 1 ? &pp_ : nullptr, s));
+                } else {
+                    comm->allreduce_f32((uintptr_t)pbuf_[m.par], (size_t)comm_len_, (uintptr_t)s);
+                }
                 break;
             case FLLaunchRec::EVAL_FEDAVG: {
                 const PeerArgs a = peer_->args(m.par, pbuf_[m.par], d_.Pimg);
@@ -964,6 +1029,9 @@ class FLEngine {
     PeerAllReduce* peer_ = nullptr;  // one-shot xGMI all-reduce (nullptr: RCCL)
     float* undo_ = nullptr;          // FLBuffers::undo storage (lagged engines with early stopping)
     PeerPack pp_;                    // its bf16 pack epilogue (bf16 mode)
+    PeerSelect sel_;                 // mode != 0: the peer call selects (robust rule) or opens (secure aggregation)
+    uint32_t* sa_clamp_ = nullptr;   // secure aggregation: this client's clamp history [max_rounds] (caller-owned)
+    void** sa_tab_ = nullptr;        // ... device pointer tables of the mask launch: {send 0, send 1, clamp history}
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation

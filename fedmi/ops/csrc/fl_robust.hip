@@ -41,40 +41,12 @@
 // stores only.
 #include "fl_common.h"
 #include "fl_image.h"
+#include "fl_robust_select.h"
 
 #define FL_ROBUST_THREADS 64
 
-// Sortable image of a float: unsigned order of the keys = the total order above.
-__device__ __forceinline__ uint32_t robust_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return (u & 0x7fffffffu) > 0x7f800000u ? 0xfffffffeu : (u == 0x80000000u ? 0x80000000u : k);
-}
-
-// Median / trimmed mean of column e: ranks in [lo, hi) are kept, n = float(hi - lo).
-template <int KB, int VEC>
-__device__ __forceinline__ float robust_select(const float (&v)[KB][VEC], int e, uint64_t mask, int lo, int hi,
-                                               float n) {
-    uint32_t key[KB];
-    int rank[KB];
-#pragma unroll
-    for (int i = 0; i < KB; ++i) {
-        key[i] = ((mask >> i) & 1) ? robust_key(v[i][e]) : 0xffffffffu;
-        rank[i] = 0;
-    }
-#pragma unroll
-    for (int i = 1; i < KB; ++i)
-#pragma unroll
-        for (int j = 0; j < i; ++j) {
-            const int before = key[j] <= key[i] ? 1 : 0;  // j < i: j sorts before i on a tie
-            rank[i] += before;
-            rank[j] += 1 - before;
-        }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < KB; ++i) acc = (rank[i] >= lo && rank[i] < hi) ? __fadd_rn(acc, v[i][e]) : acc;
-    return __fdiv_rn(acc, n);
-}
+// (robust_key, robust_select and the whole per-coordinate rule robust_apply: fl_robust_select.h, shared with
+// the one-shot xGMI gather-select kernel of peer_allreduce.hip)
 
 template <int KB, int VEC>
 __global__ void __launch_bounds__(FL_ROBUST_THREADS)
@@ -96,21 +68,8 @@ fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, fl
     // the round's sampled clients
     int r;
     const uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r, p.K) : 0;
-    const int kr = __popcll(mask);
     float out[VEC];
-    if (kr == 0) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) out[e] = fl_fold_loaded<KB, VEC>(v, p.K, 0, e, 0.f);
-    } else {
-        const int t = fl_robust_trim(p.kind, p.beta, kr);
-        const float n = (float)(kr - 2 * t);
-        const int lim = fl_image_lim(d, idx & ~3) - (idx & 3);  // elements e < lim are real parameters
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float a = robust_select<KB, VEC>(v, e, mask, t, kr - t, n);
-            out[e] = e < lim ? a : 0.f;
-        }
-    }
+    robust_apply<KB, VEC>(d, p, v, p.K, idx, mask, out);
     for (int q = 0; q < n_dst; ++q) {
         float* o = dst[q] + idx;
         if constexpr (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(out[0], out[1], out[2], out[3]);

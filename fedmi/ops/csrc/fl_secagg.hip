@@ -40,6 +40,7 @@
 #include "fl_common.h"
 #include "fl_image.h"
 #include "fl_philox.h"
+#include "fl_secagg_open.h"
 
 #define FL_SECAGG_THREADS 64
 #define FL_SECAGG_BATCH 8
@@ -124,36 +125,18 @@ fl_secagg_open_kernel(MLPDesc d, FLSecAgg p, const float* const* __restrict__ sr
         for (int i = 0; i < FL_SECAGG_BATCH; ++i) {
             const bool in = i0 + i < p.K;
             const bool on = in && ((mask >> ((i0 + i) & 63)) & 1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {  // the integer sum, and beside it the left fold of a round that is not live
-                S[e] += on ? __float_as_uint(v[i][e]) : 0u;
-                acc[e] = i0 + i == 0 ? v[i][e] : (in ? __fadd_rn(acc[e], v[i][e]) : acc[e]);
-            }
+            sa_open_add(S, acc, v[i], i0 + i, in, on);  // (fl_secagg_open.h, shared with peer_allreduce.hip)
         }
     }
     float out[4];
-    if (mask == 0) {  // not live: the rank-order sum of the whole buffer, padding included
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[e] = acc[e];
-    } else {
-        const int lim = fl_image_lim(d, idx);  // elements e < lim are real parameters
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[e] = e < lim ? __fmul_rn((float)(int)S[e], p.inv_scale) : 0.f;
-    }
+    sa_open_finish(d, idx, mask, S, acc, p.inv_scale, out);
     for (int q = 0; q < n_dst; ++q) *reinterpret_cast<float4*>(dst[q] + idx) = make_float4(out[0], out[1], out[2], out[3]);
-}
-
-static bool sa_scales(FLSecAgg& p) {
-    if (p.bits < FL_SECAGG_MIN_BITS || p.bits > FL_SECAGG_MAX_BITS) return false;
-    p.scale = (float)(1u << p.bits);
-    p.inv_scale = 1.f / p.scale;  // powers of two: exact
-    return true;
 }
 
 hipError_t fl_launch_secagg_mask(const MLPDesc& d, const FLSecAgg& p_in, float* const* bufs, int n,
                                  uint32_t* const* clamp, const FLState* st, hipStream_t s) {
     FLSecAgg p = p_in;
-    if ((d.Pimg & 3) != 0 || d.P < 1 || !sa_scales(p) || bufs == nullptr || clamp == nullptr || st == nullptr ||
+    if ((d.Pimg & 3) != 0 || d.P < 1 || !fl_secagg_scales(p) || bufs == nullptr || clamp == nullptr || st == nullptr ||
         p.rtab == nullptr || n < 1 || p.first_client < 0 || p.first_client + n > FL_SECAGG_MAX_K || p.max_rounds < 1)
         return hipErrorInvalidValue;
     const int quads = (d.P + 3) / 4;
@@ -165,7 +148,7 @@ hipError_t fl_launch_secagg_mask(const MLPDesc& d, const FLSecAgg& p_in, float* 
 hipError_t fl_launch_secagg_open(const MLPDesc& d, const FLSecAgg& p_in, const float* const* src, float* const* dst,
                                  int n_dst, const FLState* st, int tails_len, hipStream_t s) {
     FLSecAgg p = p_in;
-    if ((d.Pimg & 3) != 0 || d.Pimg < 4 || !sa_scales(p) || src == nullptr || dst == nullptr || st == nullptr ||
+    if ((d.Pimg & 3) != 0 || d.Pimg < 4 || !fl_secagg_scales(p) || src == nullptr || dst == nullptr || st == nullptr ||
         p.rtab == nullptr || p.K < 1 || p.K > FL_SECAGG_MAX_K || n_dst < 1 || tails_len < 0 || p.max_rounds < 1)
         return hipErrorInvalidValue;
     const int img_blocks = (d.Pimg / 4 + FL_SECAGG_THREADS - 1) / FL_SECAGG_THREADS;

@@ -8,6 +8,7 @@
 
 #include "fl_common.h"
 #include "peer_device.h"
+#include "peer_select.h"
 
 
 class PeerAllReduce {
@@ -23,6 +24,12 @@ class PeerAllReduce {
     float* send(int parity) const;                      // this rank's send buffer of a parity
     // out[0:n] = sum over ranks (rank order) of send(parity); optional bf16 pack epilogue
     hipError_t launch(int parity, float* out, const PeerPack* pack, hipStream_t s) const;
+    // Gather-select call (peer_select.h): out[0:Pimg] = the robust aggregate (PEER_SELECT_ROBUST) or the
+    // opened integer sum (PEER_SELECT_OPEN) of the ranks' send(parity) under the round state `st`,
+    // out[Pimg:n] = the rank-order fold of the metric tails; the same optional bf16 pack epilogue.
+    // `sel`: the mode, the image descriptor and that mode's parameters with K = world.
+    hipError_t launch_select(int parity, float* out, const PeerPack* pack, const PeerSelect& sel, const FLState* st,
+                             hipStream_t s) const;
     // Kernel arguments of a call on `parity` writing `out` (peer_device.h), for kernels that
     // fuse the all-reduce with other work; `n_w` = floats of the weights part (default: all
     // whole float4s).

@@ -34,6 +34,7 @@
 // chunk flags: publish / wait / pull).  Start-up self-tests all three protocols on a known
 // payload (fedmi/parallel/peer.py) before the engine may use them.
 #include "peer_allreduce.h"
+#include "fl_layout.h"
 
 #include <pybind11/stl.h>
 
@@ -66,6 +67,25 @@ __global__ void __launch_bounds__(PEER_THREADS) peer_allreduce_kernel(PeerArgs a
     peer_wait(a, a.ctl->flags, target);
     peer_reduce4<PEER_MAX_WORLD>(a, pk, 0, a.n >> 2, blockIdx.x, gridDim.x);
     if (blockIdx.x == 0) peer_reduce1(a, a.n & ~3ll, a.n);
+    peer_finish(a, target, gridDim.x);
+}
+
+// Gather-select call: the all-reduce's protocol in the same order -- block 0 publishes both flags, every
+// block waits and then pulls its share of all send buffers -- but the image [0, Pimg) is selected
+// (robust aggregators) or opened (secure aggregation) per coordinate instead of summed (peer_select.h);
+// the metric tails [Pimg, n) are the rank-order fold, as in the all-reduce.  A block publishes before it
+// waits and no block waits for another block of its launch, so ranks sharing one GPU cannot deadlock.
+template <int MODE, int KB>
+__global__ void __launch_bounds__(PEER_THREADS)
+peer_select_kernel(PeerArgs a, PeerPack pk, PeerSelect p, const FLState* __restrict__ st) {
+    const unsigned target = peer_target(a);
+    if (blockIdx.x == 0) {
+        peer_publish(a.flag_dst, a.world, target, a.uc);
+        peer_publish(a.tflag_dst, a.world, target, a.uc);
+    }
+    peer_wait(a, a.ctl->flags, target);
+    peer_select4<MODE, KB>(a, pk, p, st, blockIdx.x, gridDim.x);
+    if (blockIdx.x == 0) peer_reduce1(a, a.n_w, a.n);
     peer_finish(a, target, gridDim.x);
 }
 
@@ -337,6 +357,50 @@ hipError_t PeerAllReduce::launch(int parity, float* out, const PeerPack* pack, h
     return hipGetLastError();
 }
 
+hipError_t PeerAllReduce::launch_select(int parity, float* out, const PeerPack* pack, const PeerSelect& sel,
+                                        const FLState* st, hipStream_t s) const {
+    if (!open_) return hipErrorNotInitialized;
+    PeerSelect p = sel;
+    const MLPDesc& d = p.d;
+    // (the image is the call's first Pimg floats, whole float4s; the rest are the metric tails)
+    if (out == nullptr || st == nullptr || (d.Pimg & 3) != 0 || d.Pimg < 4 || d.Pimg > n_) return hipErrorInvalidValue;
+    if (p.mode == PEER_SELECT_ROBUST) {
+        if (p.rb.rtab == nullptr || p.rb.K != world_ || p.rb.max_rounds < 1 ||
+            (p.rb.kind != FL_ROBUST_MEDIAN && p.rb.kind != FL_ROBUST_TRIMMED) || !(p.rb.beta >= 0.0 && p.rb.beta < 0.5))
+            return hipErrorInvalidValue;
+    } else if (p.mode == PEER_SELECT_OPEN) {
+        if (p.sa.rtab == nullptr || p.sa.K != world_ || p.sa.max_rounds < 1 || !fl_secagg_scales(p.sa))
+            return hipErrorInvalidValue;
+    } else {
+        return hipErrorInvalidValue;
+    }
+    const PeerArgs a = args(parity, out, d.Pimg);
+    PeerPack pk;
+    std::memset(&pk, 0, sizeof(pk));
+    if (pack != nullptr) pk = *pack;
+    const long long n4 = d.Pimg / 4;
+    const int blocks = (int)std::min<long long>(PEER_MAX_BLOCKS, std::max<long long>(1, (n4 + PEER_THREADS - 1) / PEER_THREADS));
+    const dim3 g(blocks), b(PEER_THREADS);
+    // world <= PEER_MAX_WORLD = 8: the K buckets 4 and 8 of the rules
+    if (p.mode == PEER_SELECT_ROBUST) {
+        if (world_ <= 4) hipLaunchKernelGGL((peer_select_kernel<PEER_SELECT_ROBUST, 4>), g, b, 0, s, a, pk, p, st);
+        else hipLaunchKernelGGL((peer_select_kernel<PEER_SELECT_ROBUST, 8>), g, b, 0, s, a, pk, p, st);
+    } else {
+        if (world_ <= 4) hipLaunchKernelGGL((peer_select_kernel<PEER_SELECT_OPEN, 4>), g, b, 0, s, a, pk, p, st);
+        else hipLaunchKernelGGL((peer_select_kernel<PEER_SELECT_OPEN, 8>), g, b, 0, s, a, pk, p, st);
+    }
+    return hipGetLastError();
+}
+
+// Image descriptor of `dims` for the kernel-level entry points below.
+static MLPDesc peer_desc_of(const std::vector<int>& dims, const char* who) {
+    const int L = (int)dims.size() - 1;
+    if (L < 1 || L > FL_MAX_LAYERS) throw std::runtime_error(std::string(who) + ": 1..4 Linear layers supported");
+    MLPDesc d;
+    fl_build_fp32_layout(dims.data(), L, 16, &d);
+    return d;
+}
+
 void register_peer(py::module_& m) {
     py::class_<PeerAllReduce>(m, "PeerAllReduce")
         .def(py::init<int, int, int, long long, double, int>(), py::arg("world"), py::arg("rank"), py::arg("device"),
@@ -348,6 +412,63 @@ void register_peer(py::module_& m) {
         .def("allreduce",
              [](const PeerAllReduce& p, int parity, uintptr_t out, uintptr_t stream) {
                  PHIP(p.launch(parity, reinterpret_cast<float*>(out), nullptr, reinterpret_cast<hipStream_t>(stream)));
+             })
+        // Kernel-level gather-select calls (tests, tools): out[0:n] = the robust aggregate / the opened sum of
+        // every rank's send(parity) over the image of `dims`, the rank-order fold behind it; `state` / `rtab`:
+        // a client's round state and per-round table (fl_common.h).  Arguments are checked as
+        // robust_aggregate / secagg_open (fl_engine.cpp) check theirs.
+        .def("robust",
+             [](const PeerAllReduce& p, int parity, std::vector<int> dims, int kind, double beta, uintptr_t out,
+                uintptr_t state, uintptr_t rtab, int max_rounds, uintptr_t stream) {
+                 PeerSelect sel;
+                 std::memset(&sel, 0, sizeof(sel));
+                 sel.mode = PEER_SELECT_ROBUST;
+                 sel.d = peer_desc_of(dims, "robust");
+                 if (kind != FL_ROBUST_MEDIAN && kind != FL_ROBUST_TRIMMED)
+                     throw std::runtime_error("robust: kind must be 1 (median) or 2 (trimmed mean)");
+                 if (!(beta >= 0.0 && beta < 0.5)) throw std::runtime_error("robust: beta must be in [0, 0.5)");
+                 if (sel.d.Pimg > p.n_floats())
+                     throw std::runtime_error("robust: the image of dims is longer than the communicator's buffers");
+                 if (max_rounds < 1 || !out || !state || !rtab) throw std::runtime_error("robust: bad arguments");
+                 sel.rb.kind = kind;
+                 sel.rb.K = p.world();
+                 sel.rb.max_rounds = max_rounds;
+                 sel.rb.beta = beta;
+                 sel.rb.rtab = reinterpret_cast<const float*>(rtab);
+                 PHIP(p.launch_select(parity, reinterpret_cast<float*>(out), nullptr, sel,
+                                      reinterpret_cast<const FLState*>(state), reinterpret_cast<hipStream_t>(stream)));
+             },
+             py::arg("parity"), py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("out"), py::arg("state"),
+             py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"))
+        .def("secagg_open",
+             [](const PeerAllReduce& p, int parity, std::vector<int> dims, int bits, uintptr_t out, uintptr_t state,
+                uintptr_t rtab, int max_rounds, uintptr_t stream) {
+                 PeerSelect sel;
+                 std::memset(&sel, 0, sizeof(sel));
+                 sel.mode = PEER_SELECT_OPEN;
+                 sel.d = peer_desc_of(dims, "secagg_open");
+                 if (bits < FL_SECAGG_MIN_BITS || bits > FL_SECAGG_MAX_BITS)
+                     throw std::runtime_error("secagg_open: bits must be in 8 .. 30, got " + std::to_string(bits));
+                 if (sel.d.Pimg > p.n_floats())
+                     throw std::runtime_error("secagg_open: the image of dims is longer than the communicator's buffers");
+                 if (max_rounds < 1 || !out || !state || !rtab) throw std::runtime_error("secagg_open: bad arguments");
+                 sel.sa.bits = bits;
+                 sel.sa.K = p.world();
+                 sel.sa.max_rounds = max_rounds;
+                 sel.sa.rtab = reinterpret_cast<const float*>(rtab);
+                 PHIP(p.launch_select(parity, reinterpret_cast<float*>(out), nullptr, sel,
+                                      reinterpret_cast<const FLState*>(state), reinterpret_cast<hipStream_t>(stream)));
+             },
+             py::arg("parity"), py::arg("dims"), py::arg("bits"), py::arg("out"), py::arg("state"), py::arg("rtab"),
+             py::arg("max_rounds"), py::arg("stream"))
+        // this rank's send buffer of a parity from the host, from float `off` on (tests): the raw bytes of
+        // fp32 values -- bit patterns travel unchanged (masked words, NaN payloads)
+        .def("write",
+             [](const PeerAllReduce& p, int parity, long long off, py::bytes data) {
+                 const std::string v = data;
+                 if (off < 0 || (v.size() & 3) != 0 || off + (long long)(v.size() / 4) > p.n_floats())
+                     throw std::runtime_error("write: out of range");
+                 if (!v.empty()) PHIP(hipMemcpy(p.send(parity) + off, v.data(), v.size(), hipMemcpyHostToDevice));
              })
         .def("chunk_test",
              [](const PeerAllReduce& p, int parity, unsigned target, uintptr_t out, uintptr_t stream) {
