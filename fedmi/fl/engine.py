@@ -1018,7 +1018,6 @@ class HipRoundEngine(RoundEngineBase):
         auto = [16, 32] if (Xn_len <= SMALL_SHARD_ROWS and cfg.dtype == "bf16") else [32, 16]
         R_try = auto if rpb == 0 else ([64, 32, 16] if cfg.dtype == "bf16" else [32, 16]) if rpb == -1 else [rpb]
         R = R_try[0]
-        slab_stride = ((self.P + 1) + 3) & ~3
         # device parameter buffers use the padded image layout (fl_common.h)
         self.Pimg = image_layout(self.dims)[2]
         # lagged evaluation carries a second metric region after the tails (fl_common.h)
@@ -1082,6 +1081,9 @@ class HipRoundEngine(RoundEngineBase):
             "lagged_eval": self._lag,
             "emulate_clients": bool(emulate_clients),
             "slab_f16": self._pick_slab_f16(cfg),
+            # the native engine may keep its fp16 slab rows blocked (layout()["slab_blocked"]: the
+            # reference shape's specialised train / Adam pair); engines of a trial batch keep dense rows
+            "slab_blocked": comm_buffers is None,
             "plain_fwd": -1 if cfg.plain_fwd is None else int(bool(cfg.plain_fwd)),
         }
         bufs = {
@@ -1131,9 +1133,13 @@ class HipRoundEngine(RoundEngineBase):
             ecfg.update({"secagg": True, "secagg_bits": int(cfg.secagg_bits), "secagg_seed": int(self.secagg_seed)})
             bufs["sa_clamp"] = self.sa_clamp.data_ptr()
         for i, R in enumerate(R_try):
-            self.slab = torch.zeros(((self.n_local + R - 1) // R) * slab_stride, **f32)
+            # rows sized for the longest row the engine may choose (the blocked row of the reference shape)
+            # (an older library loaded through FEDMI_NATIVE_SO for an A/B knows the dense row only)
+            row = self.m.slab_row_floats(self.dims, R) if hasattr(self.m, "slab_row_floats") else ((self.P + 1) + 3) & ~3
+            self.slab = torch.zeros(((self.n_local + R - 1) // R) * row, **f32)
             ecfg["R"] = R
             bufs["slab"] = self.slab.data_ptr()
+            bufs["slab_floats"] = self.slab.numel()
             try:
                 self.engine = self.m.FLEngine(self.dims, ecfg, bufs)
                 break
@@ -1212,8 +1218,12 @@ class HipRoundEngine(RoundEngineBase):
         lay = self.engine.layout()
         ns, stride, P = int(lay["n_slabs"]), int(lay["slab_stride"]), self.P
         if self.slab_f16:  # fp16 partial e at half e of the row (fl_device.h slab_store_h)
-            return self.slab.view(torch.float16).view(-1, 2 * stride)[:ns, :P].clone()
-        return self.slab.view(-1, stride)[:ns, :P].clone()
+            rows = self.slab.view(torch.float16)[:ns * 2 * stride].view(ns, 2 * stride)
+            if lay.get("slab_blocked"):  # blocked rows (fl_layout.h FlSlabBlk): gathered into dense order
+                pos = torch.as_tensor(self.engine.slab_map(), dtype=torch.long, device=rows.device)
+                return rows[:, pos].clone()
+            return rows[:, :P].clone()
+        return self.slab[:ns * stride].view(ns, stride)[:, :P].clone()
 
     def _pick_slab_f16(self, cfg) -> bool:
         if cfg.grad_slab not in ("auto", "fp16", "fp32"):

@@ -20,6 +20,17 @@
 #define ADAM_EARLY 0
 #define ADAM_EARLY_DEFAULTED
 #endif
+// Slab row order.  Default: the dense row -- position p of a row is dense parameter p, d.P of them, the
+// loss partial the fp32 at float index d.P.  fl_adam_spec.hip's blocked instantiation reads the blocked
+// row of fl_layout.h (FlSlabBlk): ADAM_SLAB_LEN positions, ADAM_SLAB_DENSE(p) their dense index (-1: a
+// pad column, its lane stays idle), ADAM_SLAB_VALID(di) whether the lane owns a parameter.  A block
+// still owns 64 consecutive positions and sums them in the same order.
+#ifndef ADAM_SLAB_LEN
+#define ADAM_SLAB_LEN d.P
+#define ADAM_SLAB_DENSE(p) (p)
+#define ADAM_SLAB_VALID(di) ((di) < d.P)
+#define ADAM_SLAB_DEFAULTED
+#endif
 #ifndef ADAM_PA_RSAG  // weight chunks by reduce-scatter + all-gather on the LL ring (peer_device.h peer_rsag)
 #define ADAM_PA_RSAG false
 #define ADAM_PA_RSAG_DEFAULTED
@@ -142,14 +153,14 @@
 #pragma unroll
         for (int v = 0; v < TVW; ++v) {
             const int s0 = threadIdx.x + ADAM_WAVES * 64 * v;
-            lp[v] = s0 < c.n_slabs ? b.slab[(size_t)s0 * c.slab_stride + d.P] : 0.f;
+            lp[v] = s0 < c.n_slabs ? b.slab[(size_t)s0 * c.slab_stride + ADAM_SLAB_LEN] : 0.f;
         }
         round_state();
 #pragma unroll
         for (int v = 0; v < TVW; ++v) {
             const int s0 = threadIdx.x + ADAM_WAVES * 64 * v;
             for (int s = s0 + ADAM_CANON * 64; s < c.n_slabs; s += ADAM_CANON * 64)
-                lp[v] += b.slab[(size_t)s * c.slab_stride + d.P];
+                lp[v] += b.slab[(size_t)s * c.slab_stride + ADAM_SLAB_LEN];
             part[wave + ADAM_WAVES * v][lane] = lp[v];
         }
         lds_barrier();
@@ -227,8 +238,8 @@
         return;
     }
     const int pblk = ADAM_BLK - 1;
-    const int di = pblk * 64 + lane;  // dense index
-    const bool valid = di < d.P;
+    const int di = ADAM_SLAB_DENSE(pblk * 64 + lane);  // dense index of the lane's slab position
+    const bool valid = ADAM_SLAB_VALID(di);
     // dense index -> image index (and, in bf16 mode, -> packed bf16 LDS-layout position), on
     // wave 0 (the update runs there): fl_adam_map.h, shared with the host
     int j = 0, pk = 0;
@@ -291,7 +302,7 @@
         constexpr int LPR = 64 / (VEC), VW = ADAM_CANON / ADAM_WAVES;                               \
         const int q = lane & (LPR - 1), r = lane / LPR;                                             \
         const int p0i = pblk * 64 + q * (VEC);                                                      \
-        const ET* base = reinterpret_cast<const ET*>(b.slab) + (p0i < d.P ? p0i : 0);               \
+        const ET* base = reinterpret_cast<const ET*>(b.slab) + (p0i < ADAM_SLAB_LEN ? p0i : 0);     \
         const size_t rs = (size_t)c.slab_stride * (sizeof(float) / sizeof(ET)); /* ET per row */    \
         float acc[VW][VEC];                                                                         \
         bool sat = false; /* fp16 slab: a saturated (clamped) or non-finite partial was read */     \
@@ -393,6 +404,12 @@
 #ifdef ADAM_BLK_DEFAULTED
 #undef ADAM_BLK
 #undef ADAM_BLK_DEFAULTED
+#endif
+#ifdef ADAM_SLAB_DEFAULTED
+#undef ADAM_SLAB_LEN
+#undef ADAM_SLAB_DENSE
+#undef ADAM_SLAB_VALID
+#undef ADAM_SLAB_DEFAULTED
 #endif
 #ifdef ADAM_PA_RSAG_DEFAULTED
 #undef ADAM_PA_RSAG

@@ -78,10 +78,17 @@ __device__ __forceinline__ FLState fl_adam_spec_folded(const FlAdamSpecArgs& a, 
     return r;
 }
 
-template <int PACK, int SLAB_F16>
+// BLK (fp16 slab only): the slab rows are blocked rows (fl_layout.h FlSlabBlk, written by the blocked
+// instantiation of fl_train_bf16_spec.hip).  A block owns 64 consecutive row positions instead of 64
+// dense indices -- a few more blocks -- and maps each to its dense index (a pad column: an idle lane)
+// before fl_adam_pos; the row reduction is the body's, so every parameter's partials are added in the
+// same order as from dense rows.  Pads hold zeros: the saturation flag never sees them fire.
+template <int PACK, int SLAB_F16, bool BLK = false>
 __global__ void __launch_bounds__(ADAM_WAVES * 64) fl_adam_spec_kernel(FlAdamSpecArgs a) {
+    static_assert(!BLK || SLAB_F16, "the blocked row is an fp16 row");
     constexpr MLPDesc d = FlRefShape<32>::d;  // (local copies: folded, fl_layout.h FL_SHAPE_D)
     constexpr MLPDescB e = FlRefShape<32>::e;
+    constexpr FlSlabBlk sb = FlRefSlabBlk<32>::s;
     constexpr int pack = PACK;
     FLConfig c = {};
     c.R = 32;
@@ -126,7 +133,13 @@ __global__ void __launch_bounds__(ADAM_WAVES * 64) fl_adam_spec_kernel(FlAdamSpe
 // (S0 is still the state at `st` where round_state folds; S_sh: the body's LDS copy, which wave 0
 // alone writes before the block's barrier)
 #define ADAM_FINALIZE(S0, hist) fl_adam_spec_folded(a, anchor, fold_mask, hist, st, &S_sh)
+#define ADAM_SLAB_LEN (BLK ? sb.P : d.P)
+#define ADAM_SLAB_DENSE(p) (BLK ? fl_slab_blk_dense(d, sb, (p)) : (p))
+#define ADAM_SLAB_VALID(di) (BLK ? (di) >= 0 : (di) < d.P)
 #include "fl_adam_body.inc"
+#undef ADAM_SLAB_VALID
+#undef ADAM_SLAB_DENSE
+#undef ADAM_SLAB_LEN
 #undef ADAM_FINALIZE
 #undef ADAM_EARLY
 #undef ADAM_STATIC
@@ -146,8 +159,9 @@ bool fl_adam_spec_ok(const MLPDesc& d, const MLPDescB* e, const FLConfig& c, con
 
 hipError_t fl_launch_adam_spec(const FLConfig& c, const FLBuffers& b, const float* pin, const float* anchor,
                                float* comm, const FLState* st, int local_step, int pack, FLState* st_out, int fold,
-                               int tail_a, int fold_mask, hipStream_t s) {
+                               int tail_a, int fold_mask, hipStream_t s, bool slab_blocked) {
     if (!pack && c.slab_f16) return hipErrorInvalidValue;
+    if (slab_blocked && (!c.slab_f16 || c.slab_stride < FlRefSlabBlk<32>::s.P + 1)) return hipErrorInvalidValue;
     FlAdamSpecArgs a = {};
     a.pin = pin;
     a.anchor = anchor;
@@ -186,9 +200,10 @@ hipError_t fl_launch_adam_spec(const FLConfig& c, const FLBuffers& b, const floa
     a.metric_mode = c.metric_mode;
     a.atol = c.atol;
     a.rtol = c.rtol;
-    const int blocks = (FlRefShape<32>::d.P + 63) / 64 + 1;
+    const int blocks = ((slab_blocked ? FlRefSlabBlk<32>::s.P : FlRefShape<32>::d.P) + 63) / 64 + 1;
     const dim3 grid(blocks), block(ADAM_WAVES * 64);
-    if (pack && c.slab_f16) hipLaunchKernelGGL((fl_adam_spec_kernel<1, 1>), grid, block, 0, s, a);
+    if (slab_blocked) hipLaunchKernelGGL((fl_adam_spec_kernel<1, 1, true>), grid, block, 0, s, a);
+    else if (pack && c.slab_f16) hipLaunchKernelGGL((fl_adam_spec_kernel<1, 1>), grid, block, 0, s, a);
     else if (pack) hipLaunchKernelGGL((fl_adam_spec_kernel<1, 0>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((fl_adam_spec_kernel<0, 0>), grid, block, 0, s, a);
     return hipGetLastError();

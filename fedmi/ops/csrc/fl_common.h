@@ -154,7 +154,8 @@ struct FLConfig {
     int world;
     int rank;
     float agg_scale;    // n_rank / N_total (sample-size-weighted FedAvg, C:110-116)
-    int slab_stride;    // floats per slab row (dense P + loss slot, padded)
+    int slab_stride;    // floats per slab row (dense P + loss slot, padded; an engine with blocked fp16
+                        // rows: the blocked row's P, fl_layout.h FlSlabBlk)
     int n_slabs;        // workgroups of the train kernel = ceil(n_rows / R)
     int slab_f16;       // bf16 kernels: the slab holds fp16 partial SUMS (the 1/n is applied by
                         // Adam after the fp32 reduction; fl_device.h slab_store_h)
@@ -214,7 +215,9 @@ struct FLBuffers {
     const float* X;     // [n_rows, dim0] row-major, device resident
     const int* y;       // [n_rows]
     float* slab;        // [n_slabs, slab_stride] dense gradient partials (fp32; slab_f16: fp16 in the
-                        // first P halves of each row, the loss partial stays the fp32 at [P])
+                        // first P halves of each row, the loss partial stays the fp32 at [P]; the
+                        // reference shape's specialised train / Adam pair keeps the fp16 row blocked
+                        // instead, fl_layout.h FlSlabBlk)
     float* local;       // [Pimg] post-step local weights (evaluated, C:148)
     float* m;           // [Pimg] Adam exp_avg
     float* v;           // [Pimg] Adam exp_avg_sq
@@ -398,7 +401,7 @@ hipError_t fl_launch_adam(const MLPDesc& d, const FLConfig& c, const FLBuffers& 
                           const FLState* st, int local_step, hipStream_t s,
                           const MLPDescB* e = nullptr, FLState* st_out = nullptr, int fold = 0,
                           int tail_a = 0, int fold_mask = FL_FOLD_B, const PeerArgs* peer = nullptr, int wx = 0,
-                          int afold = 0, bool adam_spec = false);
+                          int afold = 0, bool adam_spec = false, bool slab_blocked = false);
 // (fl_adam_spec.hip: the Adam kernel specialised for the reference shape at R = 32, one client, no
 // exchange, no lag region, no undo buffer; `adam_spec` above lets fl_launch_adam pick it where
 // fl_adam_spec_ok holds.)  Its only kernel argument: what that kernel reads of FLConfig / FLBuffers
@@ -431,7 +434,7 @@ struct FlAdamSpecArgs {
 bool fl_adam_spec_ok(const MLPDesc& d, const MLPDescB* e, const FLConfig& c, const FLBuffers& b);
 hipError_t fl_launch_adam_spec(const FLConfig& c, const FLBuffers& b, const float* pin, const float* anchor,
                                float* comm, const FLState* st, int local_step, int pack, FLState* st_out, int fold,
-                               int tail_a, int fold_mask, hipStream_t s);
+                               int tail_a, int fold_mask, hipStream_t s, bool slab_blocked = false);
 // (fl_adam_local.hip: the Adam kernel without the in-kernel exchange; fl_launch_adam picks it)
 hipError_t fl_launch_adam_local(const MLPDesc& d, const FLConfig& c, const FLBuffers& b, const float* pin,
                                 const float* anchor, float* comm, const FLState* st, int local_step,
@@ -488,14 +491,18 @@ hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffe
 hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                 const float* pg, const FLState* st_in, FLState* st_out, int local_step,
                                 hipStream_t s, bool stage_local = false, int mode = FL_EVAL_CLASSIC,
-                                float* cm_out = nullptr, int fold_mask = FL_FOLD_B, bool shape_spec = false);
+                                float* cm_out = nullptr, int fold_mask = FL_FOLD_B, bool shape_spec = false,
+                                bool slab_blocked = false);
 // (fl_train_bf16_spec.hip: the train kernel specialised for the reference shape, fl_layout.h FlRefShape.
 // `shape_spec` above lets fl_launch_train_bf16 pick it where fl_train_bf16_spec_ok holds: descriptors
 // byte-equal to the compile-time ones, and a round kind that is instantiated)
+// `slab_blocked` (FLEngine's flag, the same value to fl_launch_adam): the fp16 slab row is the blocked
+// one of fl_layout.h (FlSlabBlk), which only the specialised train / Adam pair writes and reads; a
+// launch that would take another kernel fails instead, so a mixed pair never runs.
 bool fl_train_bf16_spec_ok(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, int mode);
 hipError_t fl_launch_train_bf16_spec(const FLConfig& c, const FLBuffers& b, const float* pg, const FLState* st_in,
                                      FLState* st_out, int local_step, hipStream_t s, bool stage_local, int mode,
-                                     float* cm_out, int fold_mask);
+                                     float* cm_out, int fold_mask, bool slab_blocked = false);
 hipError_t fl_set_lds_limit_bf16_spec(size_t bytes);
 hipError_t fl_launch_eval_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                const float* params, float* comm, const FLState* st, hipStream_t s);

@@ -68,6 +68,26 @@ __device__ __forceinline__ void slab_store_h(uint16_t* p, float v) {
     __hip_atomic_store(p, *reinterpret_cast<const uint16_t*>(&h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
 }
+// Four consecutive fp16 partials in one 8-byte store (`p` 8-byte aligned; the blocked slab row of
+// fl_layout.h): slab_store_h's clamp, NaN behaviour, rounding and store policy, element by element.
+__device__ __forceinline__ void slab_store_h4(uint16_t* p, float v0, float v1, float v2, float v3) {
+    const float v[4] = {v0, v1, v2, v3};
+    unsigned long long w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float c = v[j] == v[j] ? fminf(fmaxf(v[j], -65504.f), 65504.f) : v[j];
+        const _Float16 h = (_Float16)c;
+        w |= (unsigned long long)*reinterpret_cast<const uint16_t*>(&h) << (16 * j);
+    }
+    unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
+#if defined(FL_SLAB_CACHED)
+    *q = w;
+#elif defined(FL_SLAB_NT)
+    __builtin_nontemporal_store(w, q);
+#else
+    __hip_atomic_store(q, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -464,6 +464,27 @@ class FLEngine {
         }
         refresh_undo();
         fill_bases();
+        // Blocked fp16 slab row (fl_layout.h FlSlabBlk), reported as layout()["slab_blocked"]: every train
+        // launch of this engine takes the specialised bf16 kernel (no lagged rounds, hence every mode
+        // fl_train_bf16_spec_ok accepts), every Adam launch the specialised Adam kernel, the slab is
+        // fp16, and the caller sized the slab for the longer row (bufs["slab_floats"]) and did not opt
+        // out (cfg["slab_blocked"]: engines of a trial batch keep the dense row of the batch kernels).
+        // Both launchers get the flag with every launch and refuse any other kernel under it.
+        // FEDMI_SLAB_BLOCKED=0 keeps the dense row under the same kernels (A/B, tests).
+        {
+            const char* sbe = std::getenv("FEDMI_SLAB_BLOCKED");
+            const bool want = (!cfg.contains("slab_blocked") || cfg["slab_blocked"].cast<bool>()) &&
+                              !(sbe != nullptr && sbe[0] == '0');
+            const long long have = bufs.contains("slab_floats") ? bufs["slab_floats"].cast<long long>() : 0;
+            const int stride = ((FlRefSlabBlk<32>::s.P + 1) + 3) & ~3;
+            slab_blocked_ = want && dtype_ == 1 && c_.slab_f16 && shape_spec_on_ && !tr_.lag_ok &&
+                            fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED) && adam_spec_ok() &&
+                            have >= (long long)c_.n_slabs * stride;
+#ifdef FL_ADAM_GENERAL_ONLY
+            slab_blocked_ = false;
+#endif
+            if (slab_blocked_) c_.slab_stride = stride;
+        }
     }
 
     ~FLEngine() {
@@ -653,6 +674,7 @@ class FLEngine {
         drop_graph();
         peer_ = &p;
         tr_.has_peer = true;
+        slab_blocked_ = false;  // the Adam kernel of an engine with a peer is a generic one: dense rows (same stride)
         if (sel_.mode != 0) {
             // gather-select rounds are classic: train/Adam pairs, the optional DP or compression
             // launch, the evaluation, then the ALLREDUCE record (select / mask + open) and the optional
@@ -837,6 +859,8 @@ class FLEngine {
         o["slab_stride"] = c_.slab_stride;
         o["n_slabs"] = c_.n_slabs;
         o["slab_f16"] = c_.slab_f16;
+        // the slab rows are blocked rows (fl_layout.h FlSlabBlk; slab_map() gives each dense index's position)
+        o["slab_blocked"] = slab_blocked_;
         o["tail_off"] = c_.tail_off;
         o["tail_stride"] = c_.tail_stride;
         o["tail_len"] = c_.tail_len;
@@ -858,6 +882,15 @@ class FLEngine {
         o["server_opt"] = std::string(server_names[sv_.kind]);  // server step after every aggregation, classic rounds
         o["state_bytes"] = (int)sizeof(FLState);
         return o;
+    }
+
+    // Position (in slab elements from the row's start) of every dense parameter index: the identity for
+    // dense rows, fl_slab_blk_pos for blocked ones (layout()["slab_blocked"]).
+    std::vector<int> slab_map() const {
+        std::vector<int> pos((size_t)d_.P);
+        const FlSlabBlk sb = FlRefSlabBlk<32>::s;
+        for (int di = 0; di < d_.P; ++di) pos[(size_t)di] = slab_blocked_ ? fl_slab_blk_pos(d_, sb, di) : di;
+        return pos;
     }
 
   private:
@@ -892,6 +925,8 @@ class FLEngine {
         if (which == 0) plan_train_launch(tr_, carry_, p, par, pg, so, so, 1);
         else if (which == 1)
             p.push(FLLaunchRec::ADAM, 1, 0, 0, FL_FOLD_B, par, fl_at(FL_TB_LOCAL), pg, plan_comm_buf(tr_, par), so);
+        else if (which == 3 && dtype_ == 1 && slab_blocked_)
+            throw std::runtime_error(std::string(what) + ": no lagged train step on an engine with the blocked slab row");
         else if (which == 3 && dtype_ == 1)
             plan_train_launch(tr_, carry_, p, par, pg, so, so, 0, FL_EVAL_LAGGED, fl_at(FL_TB_LAG), 0);
         else plan_eval(tr_, p, r);
@@ -920,13 +955,14 @@ class FLEngine {
                                                               shape_spec_on_));
                 else
                     HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
-                                                   i[3], shape_spec_on_));
+                                                   i[3], shape_spec_on_, slab_blocked_));
                 break;
             case FLLaunchRec::ADAM: {
                 PeerArgs pa;
                 if (m.peer) pa = peer_->args(m.par, pbuf_[m.par]);
                 HIP_CHECK(fl_launch_adam(d_, c_, b_, F(0), F(1), F(2), S(3), i[0], s, eb, S(4), i[1], i[2], i[3],
-                                         m.peer ? &pa : nullptr, (m.peer >> 1) & 1, (m.peer >> 2) & 1, adam_spec_allowed()));
+                                         m.peer ? &pa : nullptr, (m.peer >> 1) & 1, (m.peer >> 2) & 1, adam_spec_allowed(),
+                                         slab_blocked_));
                 break;
             }
             case FLLaunchRec::EVAL:
@@ -1014,6 +1050,7 @@ class FLEngine {
     int dtype_ = 0;  // 0 = fp32 MFMA, 1 = bf16 MFMA (fp32 accumulate / master weights)
     bool shape_spec_on_ = true;  // FEDMI_SHAPE_SPEC != 0: launchers may pick shape-specialised kernels
     bool adam_spec_on_ = true;   // ... and FEDMI_ADAM_SPEC != 0: the Adam launcher too
+    bool slab_blocked_ = false;  // the fp16 slab rows are blocked rows (fl_layout.h FlSlabBlk; see the constructor)
     // The engine allows the specialised Adam kernel: no peer plane, and the round's output is the
     // Adam kernel's own (no DP clip, no compression, no server step after it); the launcher checks the shape, the
     // client count, the lag region and the undo buffer per launch (fl_adam_spec_ok).
@@ -1080,6 +1117,9 @@ class TrialBatch {
             if (e.peer_ != nullptr) throw std::runtime_error("TrialBatch: engines must not use the peer all-reduce");
             if (e.tr_.server_on) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
             if (e.tr_.compress_on) throw std::runtime_error("TrialBatch: no compression (compress)");
+            // the batch kernels write and read dense slab rows: from here on the engine's own launches do
+            // too (the row stride stays; train / Adam pairs are issued together, so no pair is split)
+            engs_[k]->slab_blocked_ = false;
             if (e.dtype_ != a.dtype_ || std::memcmp(&e.d_, &a.d_, sizeof(MLPDesc)) != 0 ||
                 (a.dtype_ == 1 && (std::memcmp(&e.e_, &a.e_, sizeof(MLPDescB)) != 0 ||
                                    std::memcmp(&e.ev_, &a.ev_, sizeof(MLPDescB)) != 0)))
@@ -1422,7 +1462,8 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def_property_readonly("late_fold", &FLEngine::late_fold)
         .def("launch_one", &FLEngine::launch_one)
         .def("confusion", &FLEngine::confusion)
-        .def("layout", &FLEngine::layout);
+        .def("layout", &FLEngine::layout)
+        .def("slab_map", &FLEngine::slab_map);
     py::class_<TrialBatch>(m, "TrialBatch")
         .def(py::init<std::vector<FLEngine*>>(), py::keep_alive<1, 2>())
         .def("run", &TrialBatch::run, py::arg("r0"), py::arg("n"), py::arg("stream"), py::arg("close") = true)
@@ -1448,6 +1489,17 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);
+    // floats per slab row an engine of this model may need at R rows per workgroup: the dense row, or the
+    // longer blocked row where the engine may choose it (the caller sizes the slab before it constructs
+    // the engine and passes the size as bufs["slab_floats"])
+    m.def("slab_row_floats", [](const std::vector<int>& dims, int R) {
+        int P = 0;
+        for (size_t l = 0; l + 1 < dims.size(); ++l) P += dims[l] * dims[l + 1] + dims[l + 1];
+        const MLPDesc rd = FlRefShape<32>::d;
+        bool ref = R == 32 && (int)dims.size() == rd.L + 1;
+        for (int l = 0; ref && l <= rd.L; ++l) ref = dims[l] == rd.dim[l];
+        return (((ref ? std::max(P, FlRefSlabBlk<32>::s.P) : P) + 1) + 3) & ~3;
+    });
     m.attr("SRC_DIGEST") = std::string(kSrcDigestMarker + sizeof("FEDMI_SRC_DIGEST:") - 1);
     register_trainer(m);
     register_peer(m);

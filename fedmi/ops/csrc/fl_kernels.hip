@@ -620,8 +620,14 @@ hipError_t fl_launch_train(const MLPDesc& d, const FLConfig& c, const FLBuffers&
 hipError_t fl_launch_adam(const MLPDesc& d, const FLConfig& c, const FLBuffers& b, const float* pin,
                           const float* anchor, float* comm, const FLState* st, int local_step, hipStream_t s,
                           const MLPDescB* e, FLState* st_out, int fold, int tail_a, int fold_mask,
-                          const PeerArgs* peer, int wx, int afold, bool adam_spec) {
+                          const PeerArgs* peer, int wx, int afold, bool adam_spec, bool slab_blocked) {
     if (fold && st_out == nullptr) return hipErrorInvalidValue;
+    // the blocked slab row (fl_layout.h FlSlabBlk) is read by the specialised kernel alone
+    if (slab_blocked && !(adam_spec && peer == nullptr && !wx && !afold && fl_adam_spec_ok(d, e, c, b)))
+        return hipErrorInvalidValue;
+#ifdef FL_ADAM_GENERAL_ONLY
+    if (slab_blocked) return hipErrorInvalidValue;
+#endif
     // the exchanges' call index advances in the folded state: an exchange needs the fold
     if ((wx || afold) &&
         (peer == nullptr || !fold || local_step != c.local_steps - 1 || peer->n_chunks < (d.P + 63) / 64 + 2 ||
@@ -638,7 +644,7 @@ hipError_t fl_launch_adam(const MLPDesc& d, const FLConfig& c, const FLBuffers& 
     // the reference shape's kernel (fl_adam_spec.hip): one client, nothing exchanged, lagged or undone
     if (adam_spec && peer == nullptr && !wx && !afold && fl_adam_spec_ok(d, e, c, b))
         return fl_launch_adam_spec(c, b, pin, anchor, comm, st, local_step, e != nullptr ? 1 : 0, st_out, fold, tail_a,
-                                   fold_mask, s);
+                                   fold_mask, s, slab_blocked);
     if (peer == nullptr && !wx && !afold)
         return fl_launch_adam_local(d, c, b, pin, anchor, comm, st, local_step, ee, e != nullptr ? 1 : 0, st_out, fold,
                                     tail_a, fold_mask, s);

@@ -362,6 +362,7 @@ __device__ __forceinline__ void fwd_layer_bf16(const MLPDesc& d_, const MLPDescB
 // dW_l[o][i] = sum_r D_{l+1}[r][o] act_l[r][i] (fp32 accumulate -> slab, dense [N][K]);
 // gb_l[o] = sum_r D_{l+1}[r][o].  Both operands are read transposed (K = rows).  F16: the slab
 // holds fp16 partials (element e at half e of the row, fl_device.h slab_store_h), else fp32.
+// SP::kSlabBlocked (fp16 slab, reference shape): the row is the blocked one of fl_layout.h instead.
 template <bool F16>
 __device__ __forceinline__ void slab_put(float* slab, int idx, float v) {
     if (F16) slab_store_h(reinterpret_cast<uint16_t*>(slab) + idx, v);
@@ -375,6 +376,7 @@ __device__ void wgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, c
                                  int nw) {
     FL_SHAPE_D(SP, d, d_);
     FL_SHAPE_E(SP, e, e_);
+    [[maybe_unused]] constexpr FlSlabBlk sb = SP::kSlabBlocked ? *SP::ps : FlSlabBlk{};  // (blocked fp16 slab row, fl_layout.h)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lr = lane & 15, lg = lane >> 4, lq = lr >> 2, lp = lr & 3;
     const int K = d.dim[l], N = d.dim[l + 1];
@@ -394,7 +396,12 @@ __device__ void wgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, c
                 const char* pb = act + (r0 * lda + it * 16 + 4 * lp) * 2;
                 const bf16x8 a = cat8(ld_tr(pa), ld_tr(pa + 16 * ldd * 2));
                 const bf16x8 b = cat8(ld_tr(pb), ld_tr(pb + 16 * lda * 2));
-                acc = mfma32(a, b, acc);
+                // blocked slab row: the operands exchange roles, the tile comes out transposed (lane
+                // (lr, lg): inputs it*16 + 4lg + j of output ot*16 + lr).  Every product keeps its k
+                // position in the same MFMA, so the accumulators hold the same bits (see the scoring
+                // pass below, which relies on the same exchange).
+                if constexpr (SP::kSlabBlocked && F16) acc = mfma32(b, a, acc);
+                else acc = mfma32(a, b, acc);
             }
         } else {
             const int r0 = 4 * lg + lq;
@@ -402,6 +409,27 @@ __device__ void wgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, c
             const bf16x4 b = ld_tr(act + (r0 * lda + it * 16 + 4 * lp) * 2);
             acc = mfma16(a, b, acc);
         }
+        if constexpr (SP::kSlabBlocked && F16) {
+            // one aligned 8-byte store per lane; the tile is one contiguous run of the row (fl_layout.h)
+            static_assert(RT >= 2, "blocked slab row: R = 32 kernels");
+            const int o = ot * 16 + lr, w = fl_slab_blk_w(K, it);
+            if (o < N && 4 * lg < w)
+                slab_store_h4(reinterpret_cast<uint16_t*>(slab) + fl_slab_blk_off(sb, l, it) + o * w + 4 * lg, acc[0],
+                              acc[1], acc[2], acc[3]);
+            continue;
+        }
+#ifdef FL_PROBE_SLAB_LINEAR
+        // Timing probes only (profiles/slab_blocked_probe.log): under the static shape policy every
+        // tile's 256 fp16 values go out as one 8-byte store per lane at tile_base + 8 lane bytes, the
+        // tiles of all layers packed back to back (69 x 512 bytes, inside the row's fp16 half).  Wrong
+        // places: bounds what the store pattern alone is worth.  Never a default build.
+        if constexpr (SP::kStatic && F16) {
+            int tb = 0;
+            for (int q = 0; q < l; ++q) tb += ((d.dim[q] + 15) >> 4) * ((d.dim[q + 1] + 15) >> 4);
+            slab_store_h4(reinterpret_cast<uint16_t*>(slab) + (tb + t) * 256 + lane * 4, acc[0], acc[1], acc[2], acc[3]);
+            continue;
+        }
+#endif
         const int i = it * 16 + lr;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -417,7 +445,7 @@ __device__ void wgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, c
             s0 += bf16_to_f32(Dh[r * ldd + o]);
             s1 += bf16_to_f32(Dh[(r + 1) * ldd + o]);
         }
-        slab_put<F16>(slab, d.b_off[l] + o, s0 + s1);
+        slab_put<F16>(slab, (SP::kSlabBlocked && F16 ? sb.b_off[l] : d.b_off[l]) + o, s0 + s1);
     }
 }
 
@@ -1056,10 +1084,12 @@ fl_eval_fedavg_bf16_kernel(MLPDesc d, MLPDescB e, FLConfig c, FLBuffers b, const
 // ---------------------------------------------------------------------------------------
 hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                 const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
-                                bool stage_local, int mode, float* cm_out, int fold_mask, bool shape_spec) {
+                                bool stage_local, int mode, float* cm_out, int fold_mask, bool shape_spec,
+                                bool slab_blocked) {
     if ((mode == FL_EVAL_FUSED || mode == FL_EVAL_LAGGED) && cm_out == nullptr) return hipErrorInvalidValue;
     if (shape_spec && fl_train_bf16_spec_ok(d, e, c, mode))
-        return fl_launch_train_bf16_spec(c, b, pg, si, so, ls, s, stage_local, mode, cm_out, fold_mask);
+        return fl_launch_train_bf16_spec(c, b, pg, si, so, ls, s, stage_local, mode, cm_out, fold_mask, slab_blocked);
+    if (slab_blocked) return hipErrorInvalidValue;  // only the specialised kernel writes the blocked slab row
     const size_t lds = (size_t)e.lds_bytes;
     const bool lag = mode == FL_EVAL_LAGGED;
     // split scoring (FLConfig::split_score): the lagged round's first local step scores on

@@ -190,6 +190,93 @@ inline bool fl_ref_shape_match(const MLPDesc& d, const MLPDescB& e) {
     return std::memcmp(&d, &rd, sizeof(d)) == 0 && std::memcmp(&e, &re, sizeof(e)) == 0;
 }
 
+// Blocked fp16 gradient-slab row (reference shape, R = 32: the specialised bf16 train kernel writes it,
+// the specialised Adam kernel reads it; every other kernel pair keeps the dense [o][K] order).  The
+// weight gradient of layer l (K inputs, N outputs) is stored as blocks of 16 inputs, [it][o][w]:
+// block `it` holds inputs 16 it .. 16 it + w - 1 of every output, w = min(16, K - 16 it) rounded up to
+// a multiple of 4, so element (o, i) sits at fl_slab_blk_off(l, it) + o w + i % 16.  Every block starts
+// on a multiple of 32 halves (64 bytes), and a 16 x 16 wgrad tile whose lanes hold 4 consecutive
+// inputs of one output (fl_kernels_bf16.hip wgrad_layer_bf16) is one contiguous run of at most 512
+// bytes, one aligned 8-byte store per lane.  Columns i >= K inside a block are pads: the train kernel
+// writes them on every launch (exact zeros: the padded activation columns are zero), no parameter
+// maps to them.  The bias gradients follow in dense order; the row's P halves are rounded up to a
+// multiple of 8 with zeros (the Adam kernel reads 16-byte chunks), and the loss partial stays the
+// fp32 at float index P of the row, as in the dense row.
+struct FlSlabBlk {
+    int lay_off[FL_MAX_LAYERS];  // first block of layer l's weight gradient (halves)
+    int bstride[FL_MAX_LAYERS];  // halves from one block of the layer to the next: roundup32(16 N)
+    int b_off[FL_MAX_LAYERS];    // bias gradient of layer l
+    int P;                       // halves of the row that hold gradients (pads included)
+    int Pz;                      // P rounded up to a multiple of 8: [P, Pz) is zero-filled
+};
+__host__ __device__ constexpr int fl_slab_blk_w(int K, int it) { return ((K - 16 * it < 16 ? K - 16 * it : 16) + 3) & ~3; }
+__host__ __device__ constexpr int fl_slab_blk_off(const FlSlabBlk& s, int l, int it) { return s.lay_off[l] + it * s.bstride[l]; }
+constexpr FlSlabBlk fl_slab_blk_build(const MLPDesc& d) {
+    FlSlabBlk s{};
+    int off = 0;
+    for (int l = 0; l < d.L; ++l) {
+        const int K = d.dim[l], N = d.dim[l + 1], itiles = (K + 15) >> 4;
+        off = (off + 31) & ~31;
+        s.lay_off[l] = off;
+        s.bstride[l] = (16 * N + 31) & ~31;
+        off += (itiles - 1) * s.bstride[l] + N * fl_slab_blk_w(K, itiles - 1);
+    }
+    off = (off + 7) & ~7;
+    for (int l = 0; l < d.L; ++l) {
+        s.b_off[l] = off;
+        off += d.dim[l + 1];
+    }
+    s.P = off;
+    s.Pz = (off + 7) & ~7;
+    return s;
+}
+// The row is gap-free when every block ends where the next one starts (each position below P is
+// then a gradient or a pad column, all of them written by the train kernel).
+constexpr bool fl_slab_blk_gapfree(const MLPDesc& d, const FlSlabBlk& s) {
+    for (int l = 0; l < d.L; ++l) {
+        const int K = d.dim[l], N = d.dim[l + 1], itiles = (K + 15) >> 4;
+        if (itiles > 1 && s.bstride[l] != 16 * N) return false;
+        const int end = fl_slab_blk_off(s, l, itiles - 1) + N * fl_slab_blk_w(K, itiles - 1);
+        if (end != (l + 1 < d.L ? s.lay_off[l + 1] : s.b_off[0])) return false;
+    }
+    return true;
+}
+// Dense parameter index -> position in the blocked row.
+__host__ __device__ constexpr int fl_slab_blk_pos(const MLPDesc& d, const FlSlabBlk& s, int di) {
+    int l = 0;
+    for (int t = 1; t < d.L; ++t)
+        if (di >= d.w_off[t]) l = t;
+    if (di >= d.b_off[l]) return s.b_off[l] + (di - d.b_off[l]);
+    const int K = d.dim[l], q = di - d.w_off[l];
+    const int o = q / K, i = q - o * K, it = i >> 4;
+    return fl_slab_blk_off(s, l, it) + o * fl_slab_blk_w(K, it) + (i & 15);
+}
+// Position in the blocked row -> dense parameter index, -1 for a pad (the inverse of fl_slab_blk_pos;
+// one arm per layer, so under constant descriptors every division is by a constant).
+__host__ __device__ constexpr int fl_slab_blk_dense(const MLPDesc& d, const FlSlabBlk& s, int pos) {
+    if (pos < 0 || pos >= s.P) return -1;
+    int di = -1;
+#pragma unroll
+    for (int l = 0; l < FL_MAX_LAYERS; ++l) {
+        if (l >= d.L) continue;
+        const int K = d.dim[l], N = d.dim[l + 1], itiles = (K + 15) >> 4;
+        if (pos >= s.b_off[l] && pos < s.b_off[l] + N) di = d.b_off[l] + (pos - s.b_off[l]);
+        const int q = pos - s.lay_off[l];
+        if (q < 0 || q >= (itiles - 1) * s.bstride[l] + N * fl_slab_blk_w(K, itiles - 1)) continue;
+        int it = q / s.bstride[l];
+        it = it < itiles ? it : itiles - 1;
+        const int r = q - it * s.bstride[l], w = fl_slab_blk_w(K, it);
+        const int o = r / w, i = 16 * it + (r - o * w);
+        if (o < N && i < K) di = d.w_off[l] + o * K + i;
+    }
+    return di;
+}
+template <int R>
+struct FlRefSlabBlk {
+    static constexpr FlSlabBlk s = fl_slab_blk_build(FlRefShape<R>::d);
+    static_assert(fl_slab_blk_gapfree(FlRefShape<R>::d, s), "reference shape: the blocked slab row has no gaps");
+};
+
 // Shape policies of the train kernels' device functions (template parameter SP): where a function
 // takes its descriptors from.  FlShapeDyn: the by-value kernel arguments, as passed.  FlShapeRef<R>:
 // the reference shape's constants -- the arguments are ignored, every stride, offset and trip count
@@ -199,14 +286,20 @@ inline bool fl_ref_shape_match(const MLPDesc& d, const MLPDescB& e) {
 // policy; under FlShapeRef to a function-local constexpr copy of the constants, which the compiler
 // folds (a load from the class-scope object is not folded in device code: such objects are
 // constant-memory symbols the host may overwrite).
+// kSlabBlocked (FlShapeRef<R, true>, bf16 train kernel only): the fp16 slab row is the blocked one
+// above (FlRefSlabBlk<R>) instead of the dense row.
 struct FlShapeDyn {
     static constexpr bool kStatic = false;
+    static constexpr bool kSlabBlocked = false;
     static constexpr const MLPDesc* pd = nullptr;
     static constexpr const MLPDescB* pe = nullptr;
+    static constexpr const FlSlabBlk* ps = nullptr;
 };
-template <int R>
+template <int R, bool BLK = false>
 struct FlShapeRef {
     static constexpr bool kStatic = true;
+    static constexpr bool kSlabBlocked = BLK;
+    static constexpr const FlSlabBlk* ps = &FlRefSlabBlk<R>::s;
     static constexpr const MLPDesc* pd = &FlRefShape<R>::d;
     static constexpr const MLPDescB* pe = &FlRefShape<R>::e;
 };

@@ -203,7 +203,15 @@
     }
     if (threadIdx.x < 64) {
         lossv = wave_sum(lossv);
-        if (threadIdx.x == 0) slab[d.P] = lossv;
+        if constexpr (SP::kSlabBlocked) {
+            // blocked fp16 row (fl_layout.h): the loss slot follows its P halves' floats, and the row's
+            // last 16-byte chunk is completed with zeros (the Adam kernel reads whole chunks)
+            constexpr FlSlabBlk sb = SP::kSlabBlocked ? *SP::ps : FlSlabBlk{};  // (non-dependent SP: see FL_SHAPE_D)
+            if (threadIdx.x == 0) slab[sb.P] = lossv;
+            if ((int)threadIdx.x < sb.Pz - sb.P) slab_store_h(reinterpret_cast<uint16_t*>(slab) + sb.P + threadIdx.x, 0.f);
+        } else {
+            if (threadIdx.x == 0) slab[d.P] = lossv;
+        }
     }
     lds_barrier();
     if (score || lagged)
@@ -222,7 +230,7 @@
 #pragma unroll SP::kStatic ? FL_MAX_LAYERS : 1  // static shape: one copy per layer, constants throughout
     for (int l = L - 1; l >= 0; --l) {
         const int nw = wgrad_waves_bf16<SP>(e, l);
-        if (c.slab_f16) wgrad_layer_bf16<RT, true, SP>(d, e, l, lds, slab, nw);
+        if (SP::kSlabBlocked || c.slab_f16) wgrad_layer_bf16<RT, true, SP>(d, e, l, lds, slab, nw);
         else wgrad_layer_bf16<RT, false, SP>(d, e, l, lds, slab, nw);
 #ifdef FL_STAMP_FINE  // profiling builds only (tools/probes/stamps_fine.py): wgrad / dgrad split
         if (l == L - 2) FL_STAMP(7);

@@ -28,8 +28,12 @@ e.run(3)
 nb = (rows + R - 1) // R
 dbg = torch.zeros(nb * 16, dtype=torch.int64, device=e.device)
 order = [0, 8, 9, 1, 10, 11, 12, 2, 3, 4, 5, 6, 7, 15]
-kinds = [(0, "train"), (2, "eval")] + ([(3, "train, lagged scoring")] if dtype == "bf16" else [])
+# (an engine with the blocked slab row, layout()["slab_blocked"], has no lagged train step to re-run)
+kinds = [(0, "train"), (2, "eval")] + ([(3, "train, lagged scoring")] if dtype == "bf16"
+                                        and not e.engine.layout().get("slab_blocked") else [])
 nadam = 1 + (e.engine.layout()["P"] + 63) // 64 if "P" in e.engine.layout() else None
+if nadam is not None and e.engine.layout().get("slab_blocked"):  # one block per 64 positions of the blocked row
+    nadam = 1 + (max(e.engine.slab_map()) + 1 + 63) // 64
 for which, name in kinds:
     for rep in range(5):
         dbg.zero_()
