@@ -74,6 +74,14 @@ def parse_args(argv=None):
                          "coordinate-wise, unweighted, Byzantine-robust (Yin et al. 2018)")
     ap.add_argument("--trim-ratio", type=float, default=0.1,
                     help="--aggregator trimmed_mean: fraction beta cut at EACH end, in [0, 0.5)")
+    ap.add_argument("--screen", choices=["none", "multi_krum"], default="none",
+                    help="client screening in front of the aggregator: multi_krum (Blanchard et al. 2017) keeps the "
+                         "clients whose whole models lie closest to their neighbours; --aggregator mean then averages "
+                         "the kept ones unweighted (not with --wide, --secagg, --dp-clip or --gather-plane xgmi)")
+    ap.add_argument("--screen-byzantine", type=int, default=0,
+                    help="--screen: Byzantine clients assumed, f (every round needs 2 f + 3 sampled clients)")
+    ap.add_argument("--screen-keep", type=int, default=None,
+                    help="--screen: clients kept per round, m (default: sampled clients - f; 1 = Krum)")
     ap.add_argument("--compress", choices=["none", "topk", "sign"], default="none",
                     help="compress every client's round update with error feedback: topk = the largest "
                          "--compress-ratio of its entries, sign = one bit per entry and a scale (a simulated uplink: "
@@ -194,6 +202,10 @@ def _aggregator_fields(a) -> dict:
     return dict(aggregator=a.aggregator, trim_ratio=a.trim_ratio)
 
 
+def _screen_fields(a) -> dict:
+    return dict(screen=a.screen, screen_byzantine=a.screen_byzantine, screen_keep=a.screen_keep)
+
+
 def _compress_fields(a) -> dict:
     return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback)
 
@@ -228,7 +240,7 @@ def main_clients(a, comm):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
                        **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a),
-                       **_secagg_fields(a), **_gather_fields(a))
+                       **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -275,6 +287,13 @@ def main(argv=None):
         aggregator_id(EngineConfig(**_dp_fields(a), **_aggregator_fields(a)))
     except ValueError as e:
         raise SystemExit(f"--aggregator / --trim-ratio: {e}")
+    if a.wide and a.screen != "none":
+        raise SystemExit("--screen is not supported with --wide")
+    try:
+        from fedmi.fl.engine import screen_id
+        screen_id(EngineConfig(**_dp_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a)))
+    except ValueError as e:
+        raise SystemExit(f"--screen / --screen-byzantine / --screen-keep: {e}")
     if a.wide and a.compress != "none":
         raise SystemExit("--compress is not supported with --wide")
     try:
@@ -310,7 +329,7 @@ def main(argv=None):
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
                        debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
-                       **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a))
+                       **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

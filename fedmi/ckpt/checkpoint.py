@@ -211,6 +211,8 @@ def resume(path: str, trainer) -> int:
           "history": {"rounds_run": h["rounds_run"], "stop_round": h["stop_round"],
                       "stop_trigger": h["stop_trigger"], "global": np.asarray(h["global"]),
                       "per_rank": np.asarray(h["per_rank"]), "loss": np.asarray(h["loss"])}}
+    if "screen_kept" in h:   # client screening: the kept masks are the same on every rank (config only, no state)
+        st["history"]["screen_kept"] = np.asarray(h["screen_kept"], np.uint64)
     if "opt_steps" in c:
         st["opt_steps"] = int(np.asarray(c["opt_steps"]).reshape(-1)[0])
     if "dp_seed" in c:

@@ -15,16 +15,40 @@ The aggregate is unweighted: sample sizes are self-reported, and a weighted medi
 paper analyses.  :func:`robust_aggregate_torch` is that rule in the tensors' dtype: in fp32 a
 bit-exact model of the HIP kernel (``fedmi/ops/csrc/fl_robust.hip``), in float64 the oracle's
 arithmetic.
+
+Multi-Krum screening (Blanchard et al. 2017, "Machine Learning with Adversaries: Byzantine Tolerant
+Gradient Descent"; ``EngineConfig.screen``) runs in front of any of the three rules and judges whole
+models, where the rules above judge every coordinate on its own.  With ``f`` Byzantine clients
+assumed and ``m`` clients to keep, per round:
+
+* ``d(i, j)`` = the sum over the real parameters of ``(v_i - v_j)^2`` for sampled ``i != j``, a sum
+  that is not ``< +inf`` (NaN, inf, overflow) counting as ``+inf``; ``d(i, i) = 0``;
+* ``K_r < 2 f + 3`` keeps every sampled client; otherwise ``score(i)`` = the sum, in client order, of
+  the ``K_r - f - 2`` smallest ``d(i, j)`` (ties by client index);
+* the ``min(m, K_r - f)`` clients of smallest score are kept (ties to the lower client index), and the
+  coordinate rule runs over them: ``K_r`` becomes the number kept.  ``aggregator="mean"`` is then the
+  UNWEIGHTED mean of the kept clients (the trimmed mean with ``beta = 0``) -- the paper's multi-Krum;
+  ``m = 1`` is Krum.
+
+:func:`pair_distances_model` is the bit-exact fp32 model of the distance kernel
+(``fedmi/ops/csrc/fl_screen.hip``) over parameter images, :func:`screen_select` the selection rule on
+a distance matrix (the select kernel's model, and what the torch engines run).  The torch engines
+compute their distances with :func:`pair_distances_torch`, fp32 in torch's own summation order: their
+kept set can differ from the HIP engines' only where two scores lie within fp32 summation error of
+each other.
 """
 from __future__ import annotations
 
 import math
-from typing import Sequence
+from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 AGGREGATORS = ("mean", "median", "trimmed_mean")
 MAX_ROBUST_CLIENTS = 64   # width of the per-round sampled-client mask (fl_common.h FL_ROBUST_MAX_K)
+SCREENS = ("none", "multi_krum")
+_SCREEN_THREADS = 256     # workgroup of the distance kernel (fl_screen.hip FL_SCREEN_THREADS)
 
 
 def trim_count(kind: str, beta: float, k_r: int) -> int:
@@ -52,6 +76,8 @@ class _AggLaunch:
     ``first_client ..`` with the clamp histories ``clamps``.  Owns the device pointer tables."""
 
     def __init__(self, lead, src, dst, clamps=(), first_client: int = 0):
+        """With a screen (``lead.screen``) the launcher also owns the K x K distance scratch and the
+        kept-mask word of each parity; the kept-mask history is the lead engine's ``screen_hist``."""
         def table(ts):
             return torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=lead.device)
         self._lead, self._bufs = lead, (src, dst, clamps)   # (the tables hold addresses: keep the buffers)
@@ -59,16 +85,30 @@ class _AggLaunch:
         self._src = [table(s) for s in src]
         self._dst = self._src if dst is src else [table(s) for s in dst]
         self._clamp = table(clamps)
+        self._dist = self._keep = None
+        if getattr(lead, "screen", 0):
+            self._dist = torch.zeros(self._k * self._k, dtype=torch.float32, device=lead.device)
+            self._keep = torch.zeros(2, dtype=torch.int64, device=lead.device)
 
     def _round(self, par: int):
         e = self._lead
         return e.state[par].data_ptr(), e.rtab.data_ptr()
 
     def robust(self, par: int, stream: int) -> None:
+        """The aggregate launch; with a screen the distance and select launches run in front of it and
+        the rule takes the kept clients."""
         e = self._lead
-        e.m.robust_aggregate(e.dims, e.robust, float(e.cfg.trim_ratio), self._src[par].data_ptr(), self._k,
+        keep = ()   # (no screen: the call is the one it was before screening existed, argument for argument)
+        if self._keep is not None:
+            word = self._keep.data_ptr() + 8 * par
+            keep = (word,)
+            e.m.screen_dist(e.dims, self._src[par].data_ptr(), self._k, self._dist.data_ptr(), *self._round(par),
+                            int(e.cfg.max_rounds), stream)
+            e.m.screen_select(self._dist.data_ptr(), self._k, int(e.cfg.screen_byzantine), int(e.cfg.screen_keep or 0),
+                              word, e.screen_hist.data_ptr(), *self._round(par), int(e.cfg.max_rounds), stream)
+        e.m.robust_aggregate(e.dims, e.robust, float(e.robust_beta), self._src[par].data_ptr(), self._k,
                              self._dst[par].data_ptr(), self._n, *self._round(par), self._k * e.tail_stride,
-                             int(e.cfg.max_rounds), stream)
+                             int(e.cfg.max_rounds), stream, *keep)
 
     def mask(self, par: int, stream: int) -> None:
         e = self._lead
@@ -118,3 +158,119 @@ def robust_aggregate_torch(stack: torch.Tensor, active_mask: Sequence[bool], kin
             keep = (rank[i] >= t) & (rank[i] < k_r - t)
             acc = torch.where(keep, acc + stack[i], acc)
     return acc / torch.tensor(float(k_r - 2 * t), dtype=stack.dtype, device=stack.device)
+
+
+def _key32(x: np.ndarray) -> np.ndarray:
+    """The sortable uint32 image of fp32 values (fl_robust_select.h robust_key): NaN above +inf, -0 == +0."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    k = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    k = np.where(u == np.uint32(0x80000000), np.uint32(0x80000000), k)
+    return np.where((u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000), np.uint32(0xFFFFFFFE), k).astype(np.uint32)
+
+
+def pair_distances_model(stack, active: Sequence[bool], real) -> np.ndarray:
+    """The K x K fp32 matrix ``fl_screen_dist_kernel`` writes for the parameter images ``stack``
+    [K, Pimg] (Pimg a multiple of 4), bit for bit: thread t of 256 owns the float4s t, t + 256, ... in
+    increasing order and adds, lane by lane, ``(a - b) * (a - b)`` -- one rounding per operation, ``+0``
+    for a position that is image padding (``real`` [Pimg] false) -- into its accumulator; an xor tree
+    (offsets 32, 16, ... 1) sums each 64-lane wave, the four wave sums are added in wave order; a sum
+    that is not ``< +inf`` becomes ``+inf``; the diagonal is 0.  Rows and columns of clients that are
+    not ``active`` are left 0 (the kernel leaves them unspecified)."""
+    a = np.ascontiguousarray(np.asarray(stack, np.float32))
+    real = np.asarray(real, bool).reshape(-1)
+    K, n = a.shape
+    if n % 4 or real.shape[0] != n:
+        raise ValueError("pair_distances_model: needs [K, Pimg] images, Pimg a multiple of 4, and Pimg flags")
+    act = [bool(x) for x in active]
+    if len(act) != K:
+        raise ValueError(f"pair_distances_model: {len(act)} mask entries for {K} clients")
+    T = _SCREEN_THREADS
+    per = (n // 4 + T - 1) // T
+    pad = np.zeros((K, per * T * 4), np.float32)
+    pad[:, :n] = a
+    keep = np.zeros(per * T * 4, bool)
+    keep[:n] = real
+    keep = keep.reshape(per, T, 4)
+    out = np.zeros((K, K), np.float32)
+    idx = np.arange(64)
+    with np.errstate(all="ignore"):
+        for i in range(K):
+            js = [j for j in range(i + 1, K) if act[i] and act[j]]
+            if not js:
+                continue
+            df = pad[js] - pad[i][None]          # (a - b and b - a square to the same float)
+            sq = np.where(keep[None], (df * df).reshape(len(js), per, T, 4), np.float32(0.0))
+            acc = np.zeros((len(js), T), np.float32)
+            for q in range(per):
+                for e in range(4):
+                    acc = acc + sq[:, q, :, e]
+            lanes = acc.reshape(len(js), T // 64, 64)
+            off = 32
+            while off:
+                lanes = lanes + lanes[:, :, idx ^ off]
+                off >>= 1
+            ss = np.zeros(len(js), np.float32)
+            for w in range(T // 64):
+                ss = ss + lanes[:, w, 0]
+            ss = np.where(ss < np.float32(np.inf), ss, np.float32(np.inf)).astype(np.float32)
+            out[i, js] = ss
+            out[js, i] = ss
+    return out
+
+
+def pair_distances_torch(stack: torch.Tensor, active: Sequence[bool]) -> np.ndarray:
+    """Squared distances between the rows of ``stack`` [K, P] in fp32, torch's own summation order (the
+    torch engines' distances; canonicalised like the kernel's: not ``< +inf`` is ``+inf``, zero diagonal)."""
+    a = stack.to(torch.float32)
+    d = ((a[:, None, :] - a[None, :, :]) ** 2).sum(-1)
+    d = torch.where(d < math.inf, d, torch.full_like(d, math.inf))
+    d.fill_diagonal_(0.0)
+    act = torch.as_tensor([bool(x) for x in active])
+    return torch.where(act[:, None] & act[None, :], d, torch.zeros_like(d)).numpy()
+
+
+def screen_keep_count(k_r: int, f: int, m: Optional[int]) -> int:
+    """Clients a round of ``k_r`` sampled clients keeps: all of them when ``k_r < 2 f + 3`` (the rule
+    is undefined there), else ``min(m, k_r - f)``, ``m = None`` meaning ``k_r - f``."""
+    k_r, f = int(k_r), int(f)
+    if k_r < 2 * f + 3:
+        return k_r
+    return k_r - f if not m else min(int(m), k_r - f)
+
+
+def screen_select(dist, active: Sequence[bool], f: int, m: Optional[int] = None) -> list:
+    """The multi-Krum kept mask (a list of K bools) from the K x K fp32 distance matrix ``dist``, by the
+    rule of the module docstring -- pure rule code, the model of ``fl_screen_select_kernel``: rows and
+    columns of clients that are not ``active`` are ignored whatever they hold; scores are added in fp32
+    in client order; scores and distances compare on the sortable key, ties to the lower index."""
+    d = np.ascontiguousarray(np.asarray(dist, np.float32))
+    act = [bool(x) for x in active]
+    K = len(act)
+    if d.shape != (K, K):
+        raise ValueError(f"screen_select: a {d.shape} matrix for {K} clients")
+    f = int(f)
+    if f < 0 or (m is not None and int(m) < 1):
+        raise ValueError(f"screen_select: needs f >= 0 and m >= 1, got f={f}, m={m}")
+    S = [i for i in range(K) if act[i]]
+    k_r = len(S)
+    if k_r < 2 * f + 3:
+        return act
+    nb, want = k_r - f - 2, screen_keep_count(k_r, f, m)
+    key = _key32(d)
+    scores = {}
+    with np.errstate(all="ignore"):
+        for i in S:
+            others = [j for j in S if j != i]
+            near = sorted(others, key=lambda j: (int(key[i, j]), j))[:nb]
+            s = np.float32(0.0)
+            for j in sorted(near):
+                s = np.float32(s + d[i, j])
+            scores[i] = s
+    skey = {i: int(_key32(np.array([scores[i]], np.float32))[0]) for i in S}
+    kept = set(sorted(S, key=lambda i: (skey[i], i))[:want])
+    return [i in kept for i in range(K)]
+
+
+def mask_bits(mask: Sequence[bool]) -> int:
+    """A client mask as the integer the kernels hold (bit k = client k)."""
+    return sum(1 << k for k, on in enumerate(mask) if on)

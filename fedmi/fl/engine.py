@@ -30,7 +30,8 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
-from .aggregate import AGGREGATORS, MAX_ROBUST_CLIENTS, _AggLaunch, robust_aggregate_torch
+from .aggregate import (AGGREGATORS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch, mask_bits, pair_distances_torch,
+                        robust_aggregate_torch, screen_select)
 from .compress import COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
@@ -182,6 +183,21 @@ class EngineConfig:
     # warn and continue on the host gather.  A run-time choice, not state: results are bitwise equal on both
     # planes.  Ignored by every other engine kind (one client, the weighted mean, ClientGroup, torch).
     gather_plane: str = "host"
+    # Client screening in front of the aggregator (fedmi/fl/aggregate.py): "multi_krum" (Blanchard et al.
+    # 2017) keeps, per round, the screen_keep sampled clients whose WHOLE models lie closest to their
+    # K_r - screen_byzantine - 2 nearest neighbours (squared distance), and the aggregator runs over the
+    # kept clients only.  screen_byzantine = f, the Byzantine clients assumed: every round needs
+    # K_r >= 2 f + 3 sampled clients.  screen_keep = m in [1, min_r K_r - f]; None = K_r - f; 1 = Krum.
+    # Screening turns the unweighted (robust) mode on: with aggregator="mean" the kept clients' models
+    # are averaged UNWEIGHTED (the paper's multi-Krum; sample sizes are self-reported), "median" /
+    # "trimmed_mean" run over the kept set with K_r replaced by the number kept.  Metric tails, history
+    # and the early-stop rule see every sampled client: rejecting a model does not drop its metrics.
+    # history()["screen_kept"] holds each round's kept mask (bit k = client k).  "none": off (nothing of a
+    # round changes); one client: off.  Not with secagg, dp_clip > 0, gather_plane="xgmi", more than 64
+    # clients, trial batches (comm_buffers), fed_sweep or WideClient.
+    screen: str = "none"
+    screen_byzantine: int = 0
+    screen_keep: Optional[int] = None
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -259,6 +275,34 @@ def aggregator_id(cfg: EngineConfig) -> int:
     return kind
 
 
+def screen_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
+    """Validate the screening fields and what a screen does not combine with; the screen's index in
+    ``SCREENS`` (0 = off).  ``world``: the federation's size when the caller knows it -- one client
+    switches the screen off, so nothing is refused there; None (the entry point, before the
+    communicator exists) checks the combinations as for several clients.  The per-round bounds
+    (``K_r >= 2 f + 3``, ``screen_keep <= K_r - f``) need the sampled counts: the engines check them."""
+    if not isinstance(cfg.screen, str) or cfg.screen not in SCREENS:
+        raise ValueError(f"screen must be one of {SCREENS}, got {cfg.screen!r}")
+    f, m = cfg.screen_byzantine, cfg.screen_keep
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or int(f) < 0:
+        raise ValueError(f"screen_byzantine must be an integer >= 0, got {f!r}")
+    if m is not None and (isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1):
+        raise ValueError(f"screen_keep must be None or an integer >= 1, got {m!r}")
+    kind = SCREENS.index(cfg.screen)
+    if not kind or (world is not None and int(world) <= 1):
+        return 0
+    if bool(cfg.secagg):
+        raise ValueError(f"screen={cfg.screen!r} does not combine with secagg: screening needs the individual "
+                         "models, secure aggregation opens only their sum")
+    if float(cfg.dp_clip) > 0.0:
+        raise ValueError(f"screen={cfg.screen!r} does not combine with differential privacy (dp_clip > 0): "
+                         "the noise calibration assumes a weighted sum")
+    if cfg.gather_plane == "xgmi":
+        raise ValueError(f"screen={cfg.screen!r} does not run on gather_plane='xgmi': the one-shot select kernel "
+                         "never holds the stack of client models the pairwise distances need; use gather_plane='host'")
+    return kind
+
+
 GATHER_PLANES = ("host", "xgmi")
 
 
@@ -296,7 +340,9 @@ def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, 
 
 class _History:
     def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False,
-                 secagg: bool = False):
+                 secagg: bool = False, screen: bool = False):
+        # screening engines: the round's kept-client mask, bit k = client k (0: the round did not run)
+        self.screen = np.zeros(max_rounds, dtype=np.uint64) if screen else None
         # secure aggregation: this client's clamped / NaN coordinates per round (0: not sampled)
         self.clamped = np.zeros(max_rounds, dtype=np.int64) if secagg else None
         # DP engines: this client's pre-clip update norm per round (0: not sampled)
@@ -326,6 +372,8 @@ class _History:
             out["compress_stat"] = self.cstat[:n].copy()
         if self.clamped is not None:
             out["secagg_clamped"] = self.clamped[:n].copy()
+        if self.screen is not None:
+            out["screen_kept"] = self.screen[:n].copy()
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -351,6 +399,24 @@ class RoundEngineBase:
         if self.robust and self.world > MAX_ROBUST_CLIENTS:
             raise ValueError(f"aggregator={cfg.aggregator!r} takes at most {MAX_ROBUST_CLIENTS} clients "
                              f"(the width of the sampled-client mask), got {self.world}")
+        # index in SCREENS, 0 = no screening; one client: off.  A screen turns the unweighted mode on
+        # whatever the aggregator: "mean" over the kept clients is the trimmed-mean kind with beta = 0
+        self.screen = screen_id(cfg, self.world)
+        self.robust_beta = float(cfg.trim_ratio)
+        if self.screen:
+            if self.world > MAX_ROBUST_CLIENTS:
+                raise ValueError(f"screen={cfg.screen!r} takes at most {MAX_ROBUST_CLIENTS} clients "
+                                 f"(the width of the sampled-client mask), got {self.world}")
+            if not self.robust:
+                self.robust, self.robust_beta = AGGREGATORS.index("trimmed_mean"), 0.0
+            f = int(cfg.screen_byzantine)
+            k_min = self.sampled_count()   # every round samples that many: no round needs a look
+            if k_min < 2 * f + 3:
+                raise ValueError(f"screen={cfg.screen!r} with screen_byzantine={f} needs at least 2 f + 3 = {2 * f + 3} "
+                                 f"sampled clients in every round, a round has {k_min}")
+            if cfg.screen_keep is not None and not 1 <= int(cfg.screen_keep) <= k_min - f:
+                raise ValueError(f"screen_keep must be in [1, {k_min - f}] (the fewest sampled clients of a round "
+                                 f"minus screen_byzantine), got {cfg.screen_keep!r}")
         # secure aggregation: 1 = masked fixed-point contributions; one client is the identity
         on = secagg_id(cfg)
         if on and kind:
@@ -373,7 +439,7 @@ class RoundEngineBase:
         self.agg_scale = 1.0 if self.robust else float(self.n_local) / float(self.n_total)
         self.tail_stride = self.n_classes * self.n_classes + 1
         self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress),
-                             secagg=bool(self.secagg))
+                             secagg=bool(self.secagg), screen=bool(self.screen))
         self.compress_k = compress_k(cfg, self.P)   # entries a contribution transmits (sign, dense: P)
         assert init_flat.shape == (self.P,)
         if self.dp:
@@ -438,9 +504,14 @@ class RoundEngineBase:
         frac = float(self.cfg.participation)
         if frac >= 1.0 or self.world == 1:
             return np.arange(self.world)
-        k = max(1, int(round(frac * self.world)))
+        k = self.sampled_count()
         rng = np.random.default_rng([int(self.cfg.seed), int(r)])
         return np.sort(rng.choice(self.world, size=k, replace=False))
+
+    def sampled_count(self) -> int:
+        """Clients sampled in every round (:meth:`participants` draws that many each time)."""
+        frac = float(self.cfg.participation)
+        return self.world if frac >= 1.0 or self.world == 1 else max(1, int(round(frac * self.world)))
 
     def own_steps(self, rounds: int) -> int:
         """Adam steps this client took in rounds [0, rounds) (it only steps when sampled)."""
@@ -508,6 +579,8 @@ class RoundEngineBase:
             self.hist.cstat[:n] = np.asarray(h["compress_stat"], dtype=np.float32).reshape(n)
         if self.hist.clamped is not None and n and "secagg_clamped" in h:
             self.hist.clamped[:n] = np.asarray(h["secagg_clamped"], dtype=np.int64).reshape(n)
+        if self.hist.screen is not None and n and "screen_kept" in h:
+            self.hist.screen[:n] = np.asarray(h["screen_kept"], dtype=np.uint64).reshape(n)
 
     def _load_dp_seed(self, st: dict) -> None:
         """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
@@ -787,8 +860,13 @@ class TorchRoundEngine(RoundEngineBase):
         out = bufs[0][:-1].clone()
         for b in bufs[1:]:
             out += b[:-1]
-        out[:self.P] = robust_aggregate_torch(stack, [float(b[-1]) != 0.0 for b in bufs], self.cfg.aggregator,
-                                              float(self.cfg.trim_ratio))
+        active = [float(b[-1]) != 0.0 for b in bufs]
+        if self.screen:
+            # multi-Krum: the rule runs over the clients the screen keeps (fp32 distances in torch's order)
+            active = screen_select(pair_distances_torch(stack, active), active, int(self.cfg.screen_byzantine),
+                                   self.cfg.screen_keep)
+            self.hist.screen[self.rounds_issued] = mask_bits(active)
+        out[:self.P] = robust_aggregate_torch(stack, active, AGGREGATORS[self.robust], self.robust_beta)
         return out
 
     def step_aggregate(self) -> None:
@@ -982,6 +1060,8 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"HipRoundEngine: at most {MAX_LOCAL_STEPS} local steps per round (got {cfg.local_steps})")
         if cfg.compress != "none" and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run compression (compress={cfg.compress!r})")
+        if screen_id(cfg, comm.size if comm is not None else 1) and comm_buffers is not None:
+            raise ValueError(f"trial packing (comm_buffers) does not run client screening (screen={cfg.screen!r})")
         if cfg.aggregator != "mean" and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
         if bool(cfg.secagg) and comm_buffers is not None:
@@ -1124,6 +1204,9 @@ class HipRoundEngine(RoundEngineBase):
         if self.secagg:
             # this client's clamped / NaN coordinates per round (uint32 words; integer atomics of fl_secagg.hip)
             self.sa_clamp = torch.zeros(mr, dtype=torch.int32, device=dev)
+        if self.screen:
+            # the round's kept-client mask (uint64 words; written by fl_screen.hip's select launch)
+            self.screen_hist = torch.zeros(mr, dtype=torch.int64, device=dev)
         # gather_plane="xgmi": the native engine aggregates with the peer kernel's select / open call once the
         # peer plane is attached below (it needs the rule's parameters; the host plane launches from Python)
         want_select = xgmi_select and bool(self.robust or self.secagg) and comm_buffers is None
@@ -1148,7 +1231,10 @@ class HipRoundEngine(RoundEngineBase):
                     raise
         self.R = R
         self.layout = self.engine.layout()
-        self.layout["aggregator"] = AGGREGATORS[self.robust]   # the rule that runs (one client: the identity)
+        # the configured rule (one client: the identity -- "mean"); a screen runs "mean" as the unweighted
+        # mean of the kept clients
+        self.layout["aggregator"] = cfg.aggregator if self.robust else AGGREGATORS[0]
+        self.layout["screen"] = SCREENS[self.screen]
         if self.secagg:
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
         self.slab_f16 = bool(self.layout["slab_f16"])
@@ -1336,6 +1422,9 @@ class HipRoundEngine(RoundEngineBase):
         """The gathered stack of every rank's buffer and the launcher of the aggregation kernels over it
         (sources: its rows; destination and masked buffer: this rank's ``params[par]``), built on first use."""
         if self._agg is None:
+            # (a row is Pimg + tails floats, so rows past the first are float-aligned only when the tails are
+            # no multiple of 4: the kernels' float4 loads of the rows rely on gfx950's global dwordx4 loads
+            # taking dword-aligned addresses, as fl_robust's always have)
             stack = torch.empty((self.world, self.params[0].numel()), dtype=torch.float32, device=self.device)
             rows = [stack[k] for k in range(self.world)]
             self._agg = (stack, _AggLaunch(self, [rows, rows], [[p] for p in self.params],
@@ -1604,6 +1693,8 @@ class HipRoundEngine(RoundEngineBase):
                         m["cstat"].copy_(self.cp_stat, non_blocking=True)
                     if self.secagg:
                         m["clamp"].copy_(self.sa_clamp, non_blocking=True)
+                    if self.screen:
+                        m["screen"].copy_(self.screen_hist, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -1639,7 +1730,8 @@ class HipRoundEngine(RoundEngineBase):
             self._mirror = [{"state": mk(self.state[0]), "glob": mk(self.h_global), "rank": mk(self.h_rank),
                              "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {}),
                              **({"cstat": mk(self.cp_stat)} if self.compress else {}),
-                             **({"clamp": mk(self.sa_clamp)} if self.secagg else {})}
+                             **({"clamp": mk(self.sa_clamp)} if self.secagg else {}),
+                             **({"screen": mk(self.screen_hist)} if self.screen else {})}
                             for _ in range(2)]
         return self._mirror
 
@@ -1657,6 +1749,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.cstat[:n] = m["cstat"][:n].numpy()
             if self.secagg:
                 self.hist.clamped[:n] = m["clamp"][:n].numpy().view(np.uint32)
+            if self.screen:
+                self.hist.screen[:n] = m["screen"][:n].numpy().view(np.uint64)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1689,6 +1783,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.cstat[:n] = self.cp_stat[:n].cpu().numpy()
             if self.secagg:
                 self.hist.clamped[:n] = self.sa_clamp[:n].cpu().numpy().view(np.uint32)
+            if self.screen:
+                self.hist.screen[:n] = self.screen_hist[:n].cpu().numpy().view(np.uint64)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1809,6 +1905,8 @@ class HipRoundEngine(RoundEngineBase):
                 if self.secagg:
                     self.sa_clamp[:n].copy_(torch.as_tensor(self.hist.clamped[:n].astype(np.uint32).view(np.int32),
                                                             device=dev))
+                if self.screen:
+                    self.screen_hist[:n].copy_(torch.as_tensor(self.hist.screen[:n].view(np.int64), device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
         self.engine.invalidate()

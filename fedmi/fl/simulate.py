@@ -21,6 +21,11 @@ With a robust aggregator (``EngineConfig.aggregator``) the in-process sum is rep
 coordinate-wise median / trimmed mean of the sampled clients' buffers: one ``fl_robust`` launch,
 in place over the k buffers, on the device; ``robust_aggregate_torch`` on the CPU.
 
+With a client screen (``EngineConfig.screen``, multi-Krum) two more launches run in front of that one
+-- the pairwise distances of the sampled clients' images and the selection of the kept clients
+(``fl_screen.hip``) -- and the rule takes the kept clients; ``pair_distances_torch`` and
+``screen_select`` on the CPU.
+
 With secure aggregation (``EngineConfig.secagg``, ``fedmi/fl/secagg.py``) the k buffers are
 quantised and pair-masked before they are summed: one ``fl_secagg_mask`` launch over the k buffers
 and one ``fl_secagg_open`` launch in place on the device, the host model on the CPU.  The ``wire``
@@ -110,6 +115,14 @@ class ClientGroup:
             self.clients.append(e)
         self.tamper = tamper
         self.wire = wire
+        if self.clients[0].screen:
+            # one kept-mask history for the group (the lead's launches / rule write it): every client reports it
+            lead = self.clients[0]
+            for e in self.clients[1:]:
+                if backend == "hip":
+                    e.screen_hist = lead.screen_hist
+                else:
+                    e.hist.screen = lead.hist.screen
         if backend == "hip":
             lead = self.clients[0]
             if lead.robust or lead.secagg:   # in place over the k clients' buffers, client r = buffer r

@@ -43,7 +43,11 @@ class WideClient:
                  step_size: int = 30, gamma: float = 0.5, seed: int = 0, dtype: str = "bf16",
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
                  fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
-                 compress: str = "none", secagg: bool = False):
+                 compress: str = "none", secagg: bool = False, screen: str = "none"):
+        if screen != "none":
+            # the wide path all-reduces its buckets; nothing gathers the clients' models
+            raise ValueError(f"WideClient does not run client screening (screen={screen!r}); "
+                             "use the round engines (EngineConfig.screen)")
         if secagg:
             # the wide path all-reduces its buckets as floats; nothing quantises or masks them
             raise ValueError("WideClient does not run secure aggregation (secagg=True); "

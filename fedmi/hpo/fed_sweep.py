@@ -97,6 +97,9 @@ class FedTrialGroup:
         if base.aggregator != "mean":
             # the trials share one SUM all-reduce; a gather and a selection per trial is not batched
             raise ValueError("fed_sweep does not run robust-aggregator trials (aggregator)")
+        if getattr(base, "screen", "none") != "none":
+            # the trials share one SUM all-reduce; pairwise distances and a selection per trial are not batched
+            raise ValueError("fed_sweep does not run client-screening trials (screen)")
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         rank = comm.rank if comm is not None else 0

@@ -357,6 +357,23 @@ __host__ __device__ inline int fl_robust_trim(int kind, double beta, int kr) {
     return t < med ? t : med;
 }
 
+// Multi-Krum screening (fl_screen.hip; Blanchard et al. 2017): parameters of the per-round pairwise
+// distance and select launches, passed to those kernels alone.  Of the round's K_r sampled clients
+// (rtab mask) the min(m, K_r - f) with the smallest sum of their K_r - f - 2 nearest squared
+// whole-model distances are kept; fl_robust then aggregates over the kept set (its `keep` argument).
+#define FL_SCREEN_MAX_K 64           // width of the rtab mask; one lane per client in the select kernel
+// client pairs per workgroup of the distance kernel, tile x tile (the matrix is the same bits at every
+// size).  Measured on the 14-50-200-2 image (profiles/screen_trace.jsonl): 1 / 2 / 4 take 10.1 / 11.9 /
+// 22.2 us at K = 4, 10.4 / 12.0 / 22.6 us at K = 8 and 26.0 / 19.4-19.8 / 26.0 us at K = 64
+__host__ __device__ constexpr int fl_screen_tile(int K) { return K <= 8 ? 1 : 2; }
+struct FLScreen {
+    int K;               // sources, 1 .. FL_SCREEN_MAX_K (source k is client k)
+    int f;               // Byzantine clients assumed, >= 0
+    int m;               // clients kept, >= 1; 0: K_r - f
+    int max_rounds;      // rounds of rtab / entries of the kept-mask history; rounds past it are not live
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+};
+
 // Secure aggregation (fl_secagg.hip; Bonawitz et al. 2017, the arithmetic only): parameters of the
 // per-round mask and open launches, passed to those kernels alone.  A sampled client's contribution c
 // becomes q = clamp(rint(c 2^bits), -L, L), L = (2^31 - 1) / K_r, plus / minus the pair masks
@@ -467,9 +484,22 @@ hipError_t fl_launch_server(const MLPDesc& d, const FLServer& p, const float* x,
 // `tails_len` floats named by the device pointer table `src`, written to the `n_dst` buffers named by
 // the device pointer table `dst` (destinations may be sources).  Image: median / trimmed mean of the
 // round's sampled clients, padding exact 0; tails, and the whole buffer of a round that is not live:
-// the left fold in source order.  No per-round host argument: the launch is replayable.
+// the left fold in source order.  No per-round host argument: the launch is replayable.  `keep` (may
+// be null): the kept-client mask of the round's screening (fl_screen.hip), ANDed into the sampled mask
+// of a live round -- the rule then runs over the kept clients.
 hipError_t fl_launch_robust(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
-                            const FLState* st, int tails_len, hipStream_t s);
+                            const FLState* st, int tails_len, hipStream_t s,
+                            const unsigned long long* keep = nullptr);
+// (fl_screen.hip) multi-Krum screening of the round whose state is `st`, over the K images named by the
+// device pointer table `src`.  Dist: the K x K fp32 matrix of squared distances between the round's
+// sampled clients into the caller-owned `dist` (both triangles, zero diagonal; entries of unsampled
+// clients are unspecified); `tile` = client pairs per workgroup, tile x tile (1, 2, 4; 0: fl_screen_tile(K))
+// -- the matrix does not depend on it.  Select: from `dist`, the kept-client mask into `*keep` and
+// `hist[round]`.  A round that is not live writes nothing.  Both replayable.
+hipError_t fl_launch_screen_dist(const MLPDesc& d, const FLScreen& p, const float* const* src, float* dist,
+                                 const FLState* st, hipStream_t s, int tile = 0);
+hipError_t fl_launch_screen_select(const FLScreen& p, const float* dist, unsigned long long* keep,
+                                   unsigned long long* hist, const FLState* st, hipStream_t s);
 // (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
 // place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
 // first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);

@@ -1301,7 +1301,7 @@ static MLPDesc desc_of(const std::vector<int>& dims, const char* who) {
 // state and per-round table.  Works across engines' buffers, so it is not an FLEngine phase.
 static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintptr_t src, int K, uintptr_t dst,
                              int n_dst, uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds,
-                             uintptr_t stream) {
+                             uintptr_t stream, uintptr_t keep) {
     const MLPDesc d = desc_of(dims, "robust_aggregate");
     if (K < 1 || K > FL_ROBUST_MAX_K)
         throw std::runtime_error("robust_aggregate: 1.." + std::to_string(FL_ROBUST_MAX_K) +
@@ -1319,7 +1319,46 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
     p.beta = beta;
     p.rtab = as_ptr<const float>(rtab);
     HIP_CHECK(fl_launch_robust(d, p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
-                               as_ptr<const FLState>(state), tails_len, as_stream(stream)));
+                               as_ptr<const FLState>(state), tails_len, as_stream(stream),
+                               as_ptr<const unsigned long long>(keep)));
+}
+
+// Multi-Krum screening (fl_screen.hip) across engines' buffers, as robust_aggregate is.  `src`: device table
+// of K buffer addresses (int64); `dist`: K x K floats; `keep`: one uint64; `hist`: max_rounds uint64, all
+// caller-owned; `f` / `m`: Byzantine clients assumed and clients kept (0: K_r - f).
+static FLScreen screen_args(const char* who, int K, int f, int m, uintptr_t rtab, int max_rounds) {
+    if (K < 1 || K > FL_SCREEN_MAX_K)
+        throw std::runtime_error(std::string(who) + ": 1.." + std::to_string(FL_SCREEN_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (f < 0 || m < 0) throw std::runtime_error(std::string(who) + ": f and m must be >= 0");
+    if (max_rounds < 1 || !rtab) throw std::runtime_error(std::string(who) + ": bad arguments");
+    FLScreen p;
+    std::memset(&p, 0, sizeof(p));
+    p.K = K;
+    p.f = f;
+    p.m = m;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    return p;
+}
+
+static void screen_dist(std::vector<int> dims, uintptr_t src, int K, uintptr_t dist, uintptr_t state, uintptr_t rtab,
+                        int max_rounds, uintptr_t stream, int tile) {
+    const MLPDesc d = desc_of(dims, "screen_dist");
+    const FLScreen p = screen_args("screen_dist", K, 0, 0, rtab, max_rounds);
+    if (!src || !dist || !state) throw std::runtime_error("screen_dist: bad arguments");
+    if (tile != 0 && tile != 1 && tile != 2 && tile != 4) throw std::runtime_error("screen_dist: tile must be 1, 2 or 4");
+    HIP_CHECK(fl_launch_screen_dist(d, p, as_ptr<const float* const>(src), as_ptr<float>(dist),
+                                    as_ptr<const FLState>(state), as_stream(stream), tile));
+}
+
+static void screen_select(uintptr_t dist, int K, int f, int m, uintptr_t keep, uintptr_t hist, uintptr_t state,
+                          uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    const FLScreen p = screen_args("screen_select", K, f, m, rtab, max_rounds);
+    if (!dist || !keep || !hist || !state) throw std::runtime_error("screen_select: bad arguments");
+    HIP_CHECK(fl_launch_screen_select(p, as_ptr<const float>(dist), as_ptr<unsigned long long>(keep),
+                                      as_ptr<unsigned long long>(hist), as_ptr<const FLState>(state),
+                                      as_stream(stream)));
 }
 
 // Secure aggregation (fl_secagg.hip) across engines' buffers, as robust_aggregate is.  `bufs` / `clamp`:
@@ -1475,7 +1514,11 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("w1"), py::arg("w2"), py::arg("H"), py::arg("stream"), py::arg("label_noise") = 0.f);
     m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
-          py::arg("max_rounds"), py::arg("stream"));
+          py::arg("max_rounds"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);
+    m.def("screen_dist", &screen_dist, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("dist"), py::arg("state"),
+          py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("tile") = 0);
+    m.def("screen_select", &screen_select, py::arg("dist"), py::arg("K"), py::arg("f"), py::arg("m"), py::arg("keep"),
+          py::arg("hist"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
     m.def("compress_launch", &compress_launch, py::arg("dims"), py::arg("kind"), py::arg("k"),
           py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
           py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));

@@ -36,6 +36,11 @@
 // the others zeros) folds the whole buffer that way, padding included: it stays the exact no-op
 // it is under the weighted sum.
 //
+// Behind a client screen (fl_screen.hip, multi-Krum) the launch gets the round's kept-client mask
+// (`keep`, one device word; null without a screen): a live round ANDs it into the sampled mask, so the
+// rule above runs over the kept clients and K_r is their number.  The tails and a round that is not
+// live never read it.
+//
 // Launch- and latency-bound like fl_server: 64-thread workgroups, so the waves land on CUs of
 // their own; the tails run in workgroups of their own (no wave mixes the two paths).  Plain vector
 // stores only.
@@ -51,7 +56,8 @@
 template <int KB, int VEC>
 __global__ void __launch_bounds__(FL_ROBUST_THREADS)
 fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, float* const* __restrict__ dst, int n_dst,
-                 const FLState* __restrict__ st, int tails_len, int img_blocks) {
+                 const FLState* __restrict__ st, int tails_len, int img_blocks,
+                 const unsigned long long* __restrict__ keep) {
     if ((int)blockIdx.x >= img_blocks) {
         // metric tails: one float per thread
         const int j = ((int)blockIdx.x - img_blocks) * FL_ROBUST_THREADS + threadIdx.x;
@@ -65,9 +71,10 @@ fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, fl
     if (idx >= d.Pimg) return;
     float v[KB][VEC];
     fl_src_load<KB, VEC>(src, p.K, 0, idx, v);
-    // the round's sampled clients
+    // the round's sampled clients, cut to the ones the round's screening kept (fl_screen.hip) if any
     int r;
-    const uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r, p.K) : 0;
+    uint64_t mask = fl_round_gate(st, p.max_rounds, r) ? fl_round_mask(p.rtab, r, p.K) : 0;
+    if (keep != nullptr && mask != 0) mask &= *keep;
     float out[VEC];
     robust_apply<KB, VEC>(d, p, v, p.K, idx, mask, out);
     for (int q = 0; q < n_dst; ++q) {
@@ -79,24 +86,24 @@ fl_robust_kernel(MLPDesc d, FLRobust p, const float* const* __restrict__ src, fl
 
 template <int KB, int VEC>
 static void robust_launch(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
-                          const FLState* st, int tails_len, hipStream_t s) {
+                          const FLState* st, int tails_len, hipStream_t s, const unsigned long long* keep) {
     const int units = d.Pimg / VEC;
     const int img_blocks = (units + FL_ROBUST_THREADS - 1) / FL_ROBUST_THREADS;
     const int tail_blocks = (tails_len + FL_ROBUST_THREADS - 1) / FL_ROBUST_THREADS;
     hipLaunchKernelGGL((fl_robust_kernel<KB, VEC>), dim3(img_blocks + tail_blocks), dim3(FL_ROBUST_THREADS), 0, s, d, p,
-                       src, dst, n_dst, st, tails_len, img_blocks);
+                       src, dst, n_dst, st, tails_len, img_blocks, keep);
 }
 
 hipError_t fl_launch_robust(const MLPDesc& d, const FLRobust& p, const float* const* src, float* const* dst, int n_dst,
-                            const FLState* st, int tails_len, hipStream_t s) {
+                            const FLState* st, int tails_len, hipStream_t s, const unsigned long long* keep) {
     if ((d.Pimg & 3) != 0 || d.Pimg < 4 || src == nullptr || dst == nullptr || st == nullptr || p.rtab == nullptr ||
         p.K < 1 || p.K > FL_ROBUST_MAX_K || n_dst < 1 || tails_len < 0 || p.max_rounds < 1 ||
         (p.kind != FL_ROBUST_MEDIAN && p.kind != FL_ROBUST_TRIMMED) || !(p.beta >= 0.0 && p.beta < 0.5))
         return hipErrorInvalidValue;
-    if (p.K <= 4) robust_launch<4, 4>(d, p, src, dst, n_dst, st, tails_len, s);
-    else if (p.K <= 8) robust_launch<8, 4>(d, p, src, dst, n_dst, st, tails_len, s);
-    else if (p.K <= 16) robust_launch<16, 1>(d, p, src, dst, n_dst, st, tails_len, s);
-    else if (p.K <= 32) robust_launch<32, 1>(d, p, src, dst, n_dst, st, tails_len, s);
-    else robust_launch<64, 1>(d, p, src, dst, n_dst, st, tails_len, s);
+    if (p.K <= 4) robust_launch<4, 4>(d, p, src, dst, n_dst, st, tails_len, s, keep);
+    else if (p.K <= 8) robust_launch<8, 4>(d, p, src, dst, n_dst, st, tails_len, s, keep);
+    else if (p.K <= 16) robust_launch<16, 1>(d, p, src, dst, n_dst, st, tails_len, s, keep);
+    else if (p.K <= 32) robust_launch<32, 1>(d, p, src, dst, n_dst, st, tails_len, s, keep);
+    else robust_launch<64, 1>(d, p, src, dst, n_dst, st, tails_len, s, keep);
     return hipGetLastError();
 }
