@@ -100,6 +100,16 @@ def parse_args(argv=None):
                     help="robust --aggregator / --secagg on several ranks: host = every rank's buffer gathered over the "
                          "host plane; xgmi = the rule runs inside the one-shot xGMI peer kernel (at most 8 ranks; rounds "
                          "are graph-captured; falls back to host when the peer plane is unavailable). Same results")
+    ap.add_argument("--heldout", action="store_true",
+                    help="score the round's GLOBAL model on the 20 %% test split at the end of every round (in the "
+                         "round's graph on the HIP engine); --jsonl rows gain heldout_accuracy|precision|recall|f1|loss "
+                         "and the run ends with one line naming the best held-out round (not with --wide)")
+    ap.add_argument("--keep-best", action="store_true",
+                    help="--heldout: keep the model of the round with the smallest held-out loss (--predict-out then "
+                         "writes its probabilities)")
+    ap.add_argument("--predict-out", default=None, metavar="FILE.npy",
+                    help="write the test split's class probabilities [n, C] (float32) of the final global model, or of "
+                         "the best round's with --keep-best (rank 0)")
     ap.add_argument("--patience", type=int, default=10)
     ap.add_argument("--tolerance", type=float, default=1e-4)
     ap.add_argument("--no-early-stop", action="store_true")
@@ -225,6 +235,26 @@ def _print_privacy(a, rounds: int) -> None:
         print(privacy_statement(a.dp_noise, rounds, a.dp_delta), flush=True)
 
 
+def _print_heldout(a, h: dict) -> None:
+    """--heldout: the best held-out round on one line."""
+    if a.heldout:
+        from fedmi.fl.engine import heldout_metrics
+        b = int(h["heldout_best_round"])
+        if b < 0:
+            print("Held-out: no round scored a finite loss", flush=True)
+        else:
+            print(f"Best held-out round: {b + 1} (loss {float(h['heldout_loss'][b]):.4f}, accuracy "
+                  f"{float(heldout_metrics(h)[b, 0]):.4f})", flush=True)
+
+
+def _write_predictions(a, eng, X_test) -> None:
+    """--predict-out: the test split's probabilities of the final global model, or (--keep-best) of the
+    best held-out round's."""
+    if not a.predict_out:
+        return
+    np.save(a.predict_out, eng.predict_proba(X_test, which="best" if a.keep_best else "global"))
+
+
 def main_clients(a, comm):
     """--clients K: K clients of one federation in this process (reference semantics client for
     client: own shard, local step, local evaluation, sample-weighted FedAvg, early stop on the
@@ -244,7 +274,8 @@ def main_clients(a, comm):
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
-                    alpha=a.alpha, device=comm.device if backend == "hip" else None)
+                    alpha=a.alpha, device=comm.device if backend == "hip" else None,
+                    heldout=(ds.X_test, ds.y_test) if a.heldout else None, keep_best=a.keep_best)
     t0 = time.perf_counter()
     g.run(a.rounds)
     wall = time.perf_counter() - t0
@@ -253,6 +284,8 @@ def main_clients(a, comm):
         print_history(h, a.patience)
     print(f"{a.clients} simulated clients ({backend}): {h['rounds_run']} rounds in {wall:.2f} s", flush=True)
     _print_privacy(a, int(h["rounds_run"]))
+    _print_heldout(a, h)
+    _write_predictions(a, g.clients[0], ds.X_test)
     if a.jsonl:
         w = JsonlWriter(a.jsonl)
         w.history(h, clients=a.clients, script="C-clients", aggregation="in-process", wall_s=wall,
@@ -309,6 +342,10 @@ def main(argv=None):
             raise ValueError(f"secagg does not combine with aggregator={a.aggregator!r}")
     except ValueError as e:
         raise SystemExit(f"--secagg / --secagg-bits / --secagg-seed: {e}")
+    if a.wide and (a.heldout or a.keep_best or a.predict_out):
+        raise SystemExit("--heldout / --keep-best / --predict-out is not supported with --wide")
+    if a.keep_best and not a.heldout:
+        raise SystemExit("--keep-best needs --heldout")
     if a.wide and a.participation < 1.0:
         raise SystemExit("--participation < 1 is not supported with --wide (every wide client trains every round)")
     # RCCL protocol pinned per workload: LL for the fused engine's small FedAvg images, Simple
@@ -335,6 +372,8 @@ def main(argv=None):
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,
                                    output_size=2 if a.synthetic else None,
                                    n_total=a.synthetic_rows * size if a.synthetic else None)
+    if a.heldout:
+        trainer.set_heldout(ds.X_test, ds.y_test, keep_best=a.keep_best)   # before --resume: the rows continue
     t_setup = time.perf_counter()
     done = 0   # rounds restored from a checkpoint (not run by this process)
     if a.resume:
@@ -373,6 +412,8 @@ def main(argv=None):
         w.close()
     if rank == 0:
         _print_privacy(a, int(trainer.history()["rounds_run"]))   # resumed rounds count too
+        _print_heldout(a, trainer.history())
+        _write_predictions(a, trainer.engine, ds.X_test)
     if a.save:
         save_checkpoint(a.save, trainer)   # collective: every client writes its optimizer state
     if a.timing and rank == 0:

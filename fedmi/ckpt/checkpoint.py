@@ -144,11 +144,20 @@ def save_checkpoint(path: str, trainer) -> None:
     # the client's own per-round clamp counts stay in its file, as its update norms do
     sa = {} if "secagg_clamped" not in st["history"] else {
         "secagg_clamped": np.asarray(st["history"]["secagg_clamped"], np.int64)}
+    # held-out scoring: every rank scores the set it was given; its rows (counts, fp32 loss sums), the best
+    # round so far and, with keep_best, that round's dense weights stay in the client's file
+    ho = {} if "heldout" not in st else {
+        "heldout_cm": np.asarray(st["history"]["heldout_cm"], np.int64),
+        "heldout_loss_sum": np.asarray(st["history"]["heldout_loss_sum"], np.float32),
+        "heldout_best": np.asarray([st["heldout"]["best_loss_sum"]], np.float32),
+        "heldout_best_round": np.asarray([int(st["heldout"]["best_round"])], np.int64),
+        **({} if st["heldout"].get("best_flat") is None else
+           {"heldout_best_flat": np.asarray(st["heldout"]["best_flat"], np.float32)})}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
         {"local": np.asarray(st["local"], np.float32), "exp_avg": np.asarray(st["exp_avg"], np.float32),
          "exp_avg_sq": np.asarray(st["exp_avg_sq"], np.float32),
          # this client's own Adam step count (differs from rounds x local_steps when clients are sampled)
-         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv, **cp, **sa}, tmp,
+         "opt_steps": np.asarray([int(st.get("opt_steps", 0))], np.int64), **dp, **sv, **cp, **sa, **ho}, tmp,
         metadata={"round": str(R)}))
     gflat = flat_to_dict(st["global"], eng.dims)
     if eng.rank == 0:
@@ -164,7 +173,9 @@ def save_checkpoint(path: str, trainer) -> None:
             "config": eng.cfg.to_dict(),
             "world": eng.world,
             "early_stop": st["es"],
-            "history": {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in hist.items()},
+            # (held-out rows stay in the client files: every rank scores its own set, and a NaN loss has no JSON word)
+            "history": {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in hist.items()
+                        if not k.startswith("heldout_")},
         })
     _barrier(eng)   # meta.json names round R: older sets may go
     _prune(path, cname, R)
@@ -226,6 +237,13 @@ def resume(path: str, trainer) -> int:
         st["history"]["compress_stat"] = np.asarray(c["compress_stat"], np.float32)
     if "secagg_clamped" in c:
         st["history"]["secagg_clamped"] = np.asarray(c["secagg_clamped"], np.int64)
+    if "heldout_cm" in c:
+        st["history"].update(heldout_cm=np.asarray(c["heldout_cm"], np.int64),
+                             heldout_loss_sum=np.asarray(c["heldout_loss_sum"], np.float32),
+                             heldout_best_round=int(np.asarray(c["heldout_best_round"]).reshape(-1)[0]))
+        st["heldout"] = {"best_round": st["history"]["heldout_best_round"],
+                         "best_loss_sum": float(np.asarray(c["heldout_best"], np.float32).reshape(-1)[0]),
+                         "best_flat": np.asarray(c["heldout_best_flat"], np.float32) if "heldout_best_flat" in c else None}
     eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer / compression
     return st["rounds"]
 

@@ -338,7 +338,41 @@ def server_step(kind: int, cfg: EngineConfig, x: torch.Tensor, a: torch.Tensor, 
     return x + lr * (m / (v.sqrt() + tau))
 
 
+# Held-out rows an engine scores per round (fedmi/ops/csrc/fl_common.h FL_HELDOUT_MAX_ROWS).
+HELDOUT_MAX_ROWS = 1 << 24
+
+
+def heldout_metrics(history: dict) -> np.ndarray:
+    """``[rounds_run, 4]`` accuracy / precision / recall / F1 (``metrics_from_confusion``) of the global
+    model on the held-out set, round by round, from ``history()["heldout_cm"]``."""
+    if "heldout_cm" not in history:
+        raise KeyError("history has no held-out rows: call set_heldout(X, y) before the rounds")
+    cm = np.asarray(history["heldout_cm"])
+    if len(cm) == 0:
+        return np.zeros((0, 4))
+    return np.stack([metric_vector(metrics_from_confusion(c)) for c in cm])
+
+
+def _softmax_ce_rows(z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Per-row softmax cross-entropy lse(z) - z[y] in the logits' dtype."""
+    return torch.logsumexp(z, 1) - z.gather(1, y.view(-1, 1)).squeeze(1)
+
+
 class _History:
+    # held-out scoring (set_heldout): per round the global model's confusion counts and fp32 loss SUM on
+    # the n held-out rows, and the round with the smallest sum (-1: none yet); None: off
+    ho_cm = None
+    ho_loss = None
+    ho_best_round = -1
+    ho_n = 0
+
+    def enable_heldout(self, n_classes: int, n_rows: int) -> None:
+        if self.ho_cm is None:
+            mr = len(self.loss)
+            self.ho_cm = np.zeros((mr, n_classes, n_classes), dtype=np.int64)
+            self.ho_loss = np.zeros(mr, dtype=np.float32)
+        self.ho_n = int(n_rows)
+
     def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False,
                  secagg: bool = False, screen: bool = False):
         # screening engines: the round's kept-client mask, bit k = client k (0: the round did not run)
@@ -374,6 +408,11 @@ class _History:
             out["secagg_clamped"] = self.clamped[:n].copy()
         if self.screen is not None:
             out["screen_kept"] = self.screen[:n].copy()
+        if self.ho_cm is not None:
+            out["heldout_cm"] = self.ho_cm[:n].copy()
+            out["heldout_loss_sum"] = self.ho_loss[:n].copy()
+            out["heldout_loss"] = self.ho_loss[:n].astype(np.float64) / float(max(self.ho_n, 1))
+            out["heldout_best_round"] = int(self.ho_best_round)
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -441,6 +480,8 @@ class RoundEngineBase:
         self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress),
                              secagg=bool(self.secagg), screen=bool(self.screen))
         self.compress_k = compress_k(cfg, self.P)   # entries a contribution transmits (sign, dense: P)
+        self.heldout = False     # set_heldout: the global model is scored on a held-out set every round
+        self.keep_best = False   # ... and the model of the round with the smallest held-out loss is kept
         assert init_flat.shape == (self.P,)
         if self.dp:
             if self.world > 1 and client_sizes is None:
@@ -531,6 +572,77 @@ class RoundEngineBase:
     def _apply_early_stop(self) -> None:
         raise NotImplementedError
 
+    # -- held-out scoring of the global model, inference --
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        """Score the round's GLOBAL (aggregated, post-server-step) model on the held-out rows ``(X, y)``
+        at the end of every live round: ``history()`` gains ``heldout_cm`` ``[rounds_run, C, C]`` (int64),
+        ``heldout_loss`` ``[rounds_run]`` (mean softmax cross-entropy: the fp32 sum / n in float64; the
+        sums themselves under ``heldout_loss_sum``) and ``heldout_best_round`` (first round with the
+        smallest loss sum under a plain ``<``: NaN never wins, ties keep the earlier round; -1: none).
+        ``keep_best``: that round's model is kept (:meth:`best_flat`).  Call it before the first round or
+        between ``run()`` calls (rounds run before it have all-zero rows).  The local metrics, the
+        early-stop rule and every weight are untouched.  The data is not config: it is not saved, a
+        resumed engine is given its set again before the state is loaded."""
+        raise NotImplementedError
+
+    def _check_heldout(self, X, y):
+        X = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
+        y = np.asarray(y)
+        if X.ndim != 2 or X.shape[1] != self.dims[0]:
+            raise ValueError(f"held-out X must be [n, {self.dims[0]}], got {tuple(X.shape)}")
+        n = int(X.shape[0])
+        if y.shape != (n,):
+            raise ValueError(f"held-out y must be [{n}], got {tuple(y.shape)}")
+        if not 1 <= n <= HELDOUT_MAX_ROWS:
+            raise ValueError(f"held-out set: 1 .. {HELDOUT_MAX_ROWS} rows, got {n}")
+        if not np.issubdtype(y.dtype, np.integer):
+            raise ValueError(f"held-out labels must be integers, got dtype {y.dtype}")
+        if int(y.min()) < 0 or int(y.max()) >= self.n_classes:
+            raise ValueError(f"held-out labels must be in [0, {self.n_classes}), got [{int(y.min())}, {int(y.max())}]")
+        return X, y.astype(np.int64)
+
+    def _check_rows(self, X) -> np.ndarray:
+        X = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.dims[0]:
+            raise ValueError(f"X must be [n, {self.dims[0]}], got {tuple(X.shape)}")
+        return X
+
+    def heldout_step(self, r: int) -> None:
+        """Held-out row of round ``r`` on the aggregated image a caller produced (host gather,
+        :class:`~fedmi.fl.simulate.ClientGroup`), after :meth:`server_step`; nothing without a set."""
+        raise NotImplementedError
+
+    def best_flat(self) -> np.ndarray:
+        """Dense weights of the round with the smallest held-out loss (``set_heldout(keep_best=True)``)."""
+        raise NotImplementedError
+
+    def predict_proba(self, X, which: str = "global") -> np.ndarray:
+        """``[n, C]`` float32 softmax probabilities of the global (``which="global"``) or this client's
+        local (``"local"``) model, or of the best held-out round's (``"best"``, with
+        ``set_heldout(keep_best=True)``), from its fp32 weights."""
+        raise NotImplementedError
+
+    def predict(self, X, which: str = "global") -> np.ndarray:
+        """``[n]`` int64 classes: the first-maximum argmax of the LOGITS, the confusion kernels' rule."""
+        raise NotImplementedError
+
+    def _heldout_state_out(self, best_flat) -> dict:
+        """The held-out part of a portable state (the rows travel in the history)."""
+        if not self.heldout:
+            return {}
+        return {"heldout": {"best_round": int(self.hist.ho_best_round), "best_loss_sum": float(self._ho_best_sum()),
+                            "best_flat": best_flat}}
+
+    def _heldout_state_in(self, st: dict):
+        """The held-out part of a portable state for this engine, or None without held-out scoring; a
+        state and an engine that disagree on having rows do not match."""
+        has = st.get("heldout") is not None
+        if has != bool(self.heldout):
+            raise ValueError("checkpoint and engine disagree on held-out scoring: the state "
+                             + ("carries" if has else "has no") + " held-out rows, the engine "
+                             + ("scores a held-out set" if self.heldout else "has none (set_heldout)"))
+        return st["heldout"] if has else None
+
     def _allreduce_scalar(self, x: float) -> float:
         if self.world == 1:
             return x
@@ -581,6 +693,12 @@ class RoundEngineBase:
             self.hist.clamped[:n] = np.asarray(h["secagg_clamped"], dtype=np.int64).reshape(n)
         if self.hist.screen is not None and n and "screen_kept" in h:
             self.hist.screen[:n] = np.asarray(h["screen_kept"], dtype=np.uint64).reshape(n)
+        if self.hist.ho_cm is not None:
+            C = self.n_classes
+            if n and "heldout_cm" in h:
+                self.hist.ho_cm[:n] = np.asarray(h["heldout_cm"], dtype=np.int64).reshape(n, C, C)
+                self.hist.ho_loss[:n] = np.asarray(h["heldout_loss_sum"], dtype=np.float32).reshape(n)
+            self.hist.ho_best_round = int(h.get("heldout_best_round", -1))
 
     def _load_dp_seed(self, st: dict) -> None:
         """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
@@ -701,6 +819,65 @@ class TorchRoundEngine(RoundEngineBase):
     def _apply_early_stop(self) -> None:
         cfg = self.cfg
         self.stopper = EarlyStopper(cfg.patience, cfg.tolerance, cfg.rtol, enabled=cfg.early_stop)
+
+    # -- held-out scoring (the HIP engine's definitions in torch fp32: its own oracle, not bit-equal) --
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        X, y = self._check_heldout(X, y)
+        self.ho_X = torch.as_tensor(X, device=self.device)
+        self.ho_y = torch.as_tensor(y, dtype=torch.long, device=self.device)
+        self.hist.enable_heldout(self.n_classes, len(X))
+        if not self.heldout:
+            self._ho_best = np.float32(np.inf)
+            self._ho_best_flat = None
+        self.heldout, self.keep_best = True, bool(keep_best)
+
+    def _ho_best_sum(self) -> float:
+        return float(self._ho_best)
+
+    def heldout_step(self, r: int) -> None:
+        if not self.heldout:
+            return
+        self.model.eval()
+        with torch.no_grad():
+            z = self.model(self.ho_X).to(torch.float32)
+            _, pred = torch.max(z, 1)
+            loss = np.float32(_softmax_ce_rows(z, self.ho_y).sum().item())
+        self.hist.ho_cm[r] = confusion_matrix(self.ho_y.cpu().numpy(), pred.cpu().numpy(), self.n_classes)
+        self.hist.ho_loss[r] = loss
+        if loss < self._ho_best:    # plain <: NaN never wins, ties keep the earlier round
+            self._ho_best = loss
+            self.hist.ho_best_round = int(r)
+            if self.keep_best:
+                self._ho_best_flat = self.model.flat.detach().cpu().numpy().copy()
+
+    def best_flat(self) -> np.ndarray:
+        if not (self.heldout and self.keep_best):
+            raise RuntimeError("best_flat: needs set_heldout(X, y, keep_best=True)")
+        if self._ho_best_flat is None:
+            raise RuntimeError("best_flat: no round has won yet")
+        return self._ho_best_flat.copy()
+
+    def _logits(self, X, which: str) -> torch.Tensor:
+        if which not in ("global", "local", "best"):
+            raise ValueError(f"which must be 'global', 'local' or 'best', got {which!r}")
+        Xt = torch.as_tensor(self._check_rows(X), device=self.device)
+        model = self.model
+        if which != "local":
+            model = MLPModel(self.dims[0], self.dims[1:-1], self.dims[-1], device=self.device)
+            with torch.no_grad():
+                model.flat.copy_(self.global_params if which == "global" else torch.as_tensor(self.best_flat()))
+        model.eval()
+        with torch.no_grad():
+            return model(Xt).to(torch.float32)
+
+    def predict_proba(self, X, which: str = "global") -> np.ndarray:
+        return torch.softmax(self._logits(X, which), 1).cpu().numpy().astype(np.float32).reshape(-1, self.n_classes)
+
+    def predict(self, X, which: str = "global") -> np.ndarray:
+        z = self._logits(X, which)
+        if z.shape[0] == 0:
+            return np.zeros(0, np.int64)
+        return torch.max(z, 1)[1].cpu().numpy().astype(np.int64)
 
     # -- step-by-step API (reference train_one_epoch / evaluate_local / federated_averaging)
     def step_train(self) -> None:
@@ -898,6 +1075,7 @@ class TorchRoundEngine(RoundEngineBase):
         with torch.no_grad():
             self.model.flat.copy_(new.to(self.device))
         self.global_params = self.model.flat.detach().clone()
+        self.heldout_step(r)
         self._finalize(r, buf[self.P:].numpy())
         self.rounds_issued += 1
 
@@ -990,6 +1168,8 @@ class TorchRoundEngine(RoundEngineBase):
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
             **({"compress_residual": self.compress_residual.numpy().copy()} if self.compress else {}),
+            **self._heldout_state_out(None if not self.heldout or self._ho_best_flat is None
+                                      else self._ho_best_flat.copy()),
         }
 
     def load_portable_state(self, st: dict) -> None:
@@ -997,6 +1177,11 @@ class TorchRoundEngine(RoundEngineBase):
         cfg = self.cfg
         sv = self._server_state_in(st)
         ce = self._compress_state_in(st)
+        ho = self._heldout_state_in(st)
+        if ho is not None:
+            self._ho_best = np.float32(ho["best_loss_sum"])
+            self._ho_best_flat = (None if ho.get("best_flat") is None or not self.keep_best
+                                  else np.asarray(ho["best_flat"], np.float32).copy())
         if sv is not None:
             self.server_m = torch.as_tensor(sv[0].copy())
             self.server_v = torch.as_tensor(sv[1].copy())
@@ -1074,6 +1259,7 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"gather_plane='xgmi' takes at most {PEER_MAX_WORLD} ranks (the peers of one node), "
                              f"got {int(comm.size)}; use gather_plane='host'")
         self.m = native()
+        self._packed = comm_buffers is not None   # an engine of a trial batch (shared FedAvg buffers)
         if device is None:
             device = comm.device if comm is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -1393,8 +1579,8 @@ class HipRoundEngine(RoundEngineBase):
 
     def _phase_allreduce(self, r: int) -> None:
         if self.world == 1:
-            if self.server:   # FedAvg of one client is the identity; the server step still runs
-                self.engine.phase(r, 2, self._stream(), None)
+            if self.server or self.heldout:   # FedAvg of one client is the identity; the server step and
+                self.engine.phase(r, 2, self._stream(), None)   # the held-out record still run
             return
         if self._engine_reduces():
             self.engine.phase(r, 2, self._stream(), self._native_comm)
@@ -1402,6 +1588,7 @@ class HipRoundEngine(RoundEngineBase):
             with torch.cuda.stream(self.stream):
                 self._aggregate(r)
             self.server_step(r)
+            self.heldout_step(r)
 
     def _aggregate(self, r: int) -> None:
         """Aggregation of round ``r`` from Python, on the current stream, in place in the round's
@@ -1448,6 +1635,91 @@ class HipRoundEngine(RoundEngineBase):
         nothing without a server optimizer."""
         if self.server:
             self.engine.phase(r, 3, self._stream(), None)
+
+    # -- held-out scoring of the global model (fedmi/ops/csrc/fl_heldout.hip), inference --
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        if self._packed:
+            raise ValueError("trial packing (comm_buffers) does not run held-out scoring (set_heldout)")
+        X, y = self._check_heldout(X, y)
+        self.stream.synchronize()
+        dev, C, mr = self.device, self.n_classes, int(self.cfg.max_rounds)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.ho_X = torch.as_tensor(X, device=dev)
+        self.ho_y = torch.as_tensor(y.astype(np.int32), device=dev)
+        nblk = -(-len(X) // int(self.engine.heldout_rows_per_block))
+        self.ho_scratch = torch.zeros(nblk * (C * C + 1), **i32)   # one partial per workgroup of the row launch
+        if not self.heldout:
+            self.ho_cm = torch.zeros(mr * C * C, **i32)
+            self.ho_loss = torch.zeros(mr, dtype=torch.float32, device=dev)
+            # {best loss sum (+inf), best round (-1)} as two words, and the best round's image
+            self.ho_best = torch.as_tensor(np.array([0x7F800000, -1], np.int32), device=dev)
+            self.ho_best_image = torch.zeros(self.Pimg, dtype=torch.float32, device=dev)
+        self.hist.enable_heldout(C, len(X))
+        torch.cuda.current_stream(dev).synchronize()
+        # (the fold tracks the best round whether or not its image is kept: history()["heldout_best_round"])
+        self.engine.set_heldout(self.ho_X.data_ptr(), self.ho_y.data_ptr(), len(X), self.ho_scratch.data_ptr(),
+                                self.ho_cm.data_ptr(), self.ho_loss.data_ptr(), self.ho_best_image.data_ptr(),
+                                self.ho_best.data_ptr(), True)
+        self.heldout, self.keep_best = True, bool(keep_best)
+        self._graph_ready = False   # the native engine dropped its graphs, as for set_debug
+        self._mirror = None         # the streaming mirror gains the held-out buffers
+
+    def heldout_step(self, r: int) -> None:
+        if self.heldout:
+            self.engine.phase(r, 4, self._stream(), None)
+
+    def _ho_best_words(self):
+        w = self.ho_best.cpu().numpy()
+        return float(w.view(np.float32)[0]), int(w[1])
+
+    def _ho_best_sum(self) -> float:
+        self.stream.synchronize()
+        return self._ho_best_words()[0]
+
+    def _read_heldout(self, n: int, cm, loss, best) -> None:
+        """Rows [0, n) and the best round from (device or pinned-host) copies of the held-out buffers."""
+        C = self.n_classes
+        if n:
+            self.hist.ho_cm[:n] = cm[:n * C * C].cpu().numpy().reshape(n, C, C)
+            self.hist.ho_loss[:n] = loss[:n].cpu().numpy()
+        self.hist.ho_best_round = int(best.cpu().numpy()[1])
+
+    def best_flat(self) -> np.ndarray:
+        if not (self.heldout and self.keep_best):
+            raise RuntimeError("best_flat: needs set_heldout(X, y, keep_best=True)")
+        self.stream.synchronize()
+        if self._ho_best_words()[1] < 0:
+            raise RuntimeError("best_flat: no round has won yet")
+        return image_to_dense(self.ho_best_image.cpu().numpy(), self.dims)
+
+    def _predict(self, X, which: str, proba: bool):
+        if which not in ("global", "local", "best"):
+            raise ValueError(f"which must be 'global', 'local' or 'best', got {which!r}")
+        X = self._check_rows(X)
+        n, C, dev = int(X.shape[0]), self.n_classes, self.device
+        out = np.zeros((n, C), np.float32) if proba else np.zeros(n, np.int64)
+        if which == "best":
+            self.best_flat()   # raises without keep_best or before a first win
+        p = {"local": self.local, "best": getattr(self, "ho_best_image", None),
+             "global": self.params[self.rounds_issued & 1][:self.Pimg]}[which]
+        chunk = 1 << 20   # rows per launch (the kernel takes up to 2^24)
+        for i0 in range(0, n, chunk):
+            Xt = torch.as_tensor(X[i0:i0 + chunk], device=dev)
+            m = int(Xt.shape[0])
+            o = torch.empty((m, C), dtype=torch.float32, device=dev) if proba else \
+                torch.empty(m, dtype=torch.int32, device=dev)
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+            self.engine.predict(Xt.data_ptr(), m, p.data_ptr(), o.data_ptr() if proba else 0,
+                                0 if proba else o.data_ptr(), self._stream())
+            self.stream.synchronize()
+            out[i0:i0 + m] = o.cpu().numpy()
+        return out
+
+    def predict_proba(self, X, which: str = "global") -> np.ndarray:
+        return self._predict(X, which, True)
+
+    def predict(self, X, which: str = "global") -> np.ndarray:
+        return self._predict(X, which, False)
 
     def _issue_debug(self, n: int) -> None:
         """Debug mode: every phase launched eagerly and synchronised, so a
@@ -1497,7 +1769,7 @@ class HipRoundEngine(RoundEngineBase):
         :meth:`profile`, which runs classic phases): the native engine issues them eagerly with
         a hipEvent after every launch behind a gate kernel (FLEngine::trace), so the kernels
         run back to back.  Returns mean us per round by kernel kind (``train``, ``adam``,
-        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``compress``, ``server``), ``round`` and launch counts.  Each
+        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``compress``, ``server``, ``heldout``), ``round`` and launch counts.  Each
         interval carries the eager launch + event marker cost: measured on MI355X (bench N = 1,
         profiles/kernel_trace_r5.log) ~1.5 us per kernel over the rocprofv3 kernel durations
         (markers without the system-scope fence; ~3.2 us with it).
@@ -1534,6 +1806,7 @@ class HipRoundEngine(RoundEngineBase):
                     self.engine.run_local(r, s)
                     self._aggregate(r)
                     self.server_step(r)
+                    self.heldout_step(r)
             self.rounds_issued += n
             return
         # lagged engines: graphs hold lagged rounds only, the last round of the call is eager and
@@ -1695,6 +1968,10 @@ class HipRoundEngine(RoundEngineBase):
                         m["clamp"].copy_(self.sa_clamp, non_blocking=True)
                     if self.screen:
                         m["screen"].copy_(self.screen_hist, non_blocking=True)
+                    if self.heldout:
+                        m["ho_cm"].copy_(self.ho_cm, non_blocking=True)
+                        m["ho_loss"].copy_(self.ho_loss, non_blocking=True)
+                        m["ho_best"].copy_(self.ho_best, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -1731,7 +2008,9 @@ class HipRoundEngine(RoundEngineBase):
                              "loss": mk(self.h_loss), **({"norm": mk(self.dp_norm)} if self.dp else {}),
                              **({"cstat": mk(self.cp_stat)} if self.compress else {}),
                              **({"clamp": mk(self.sa_clamp)} if self.secagg else {}),
-                             **({"screen": mk(self.screen_hist)} if self.screen else {})}
+                             **({"screen": mk(self.screen_hist)} if self.screen else {}),
+                             **({"ho_cm": mk(self.ho_cm), "ho_loss": mk(self.ho_loss), "ho_best": mk(self.ho_best)}
+                                if self.heldout else {})}
                             for _ in range(2)]
         return self._mirror
 
@@ -1751,6 +2030,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.clamped[:n] = m["clamp"][:n].numpy().view(np.uint32)
             if self.screen:
                 self.hist.screen[:n] = m["screen"][:n].numpy().view(np.uint64)
+        if self.heldout:
+            self._read_heldout(n, m["ho_cm"], m["ho_loss"], m["ho_best"])
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1785,6 +2066,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.clamped[:n] = self.sa_clamp[:n].cpu().numpy().view(np.uint32)
             if self.screen:
                 self.hist.screen[:n] = self.screen_hist[:n].cpu().numpy().view(np.uint64)
+        if self.heldout:
+            self._read_heldout(n, self.ho_cm, self.ho_loss, self.ho_best)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -1853,6 +2136,8 @@ class HipRoundEngine(RoundEngineBase):
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
             **({"compress_residual": self.compress_residual} if self.compress else {}),
+            **self._heldout_state_out(None if not (self.heldout and self.keep_best and self._ho_best_words()[1] >= 0)
+                                      else self.best_flat()),
         }
 
     def load_portable_state(self, st: dict) -> None:
@@ -1861,6 +2146,7 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"checkpoint has {r} rounds > max_rounds {self.cfg.max_rounds}")
         sv = self._server_state_in(st)
         ce = self._compress_state_in(st)
+        ho = self._heldout_state_in(st)
         self.stream.synchronize()
         dev = self.device
         img = lambda a: torch.as_tensor(dense_to_image(np.asarray(a, np.float32), self.dims), device=dev)
@@ -1907,6 +2193,24 @@ class HipRoundEngine(RoundEngineBase):
                                                             device=dev))
                 if self.screen:
                     self.screen_hist[:n].copy_(torch.as_tensor(self.hist.screen[:n].view(np.int64), device=dev))
+            if ho is not None:
+                # the rows continue behind the checkpoint's, the best so far stays the round to beat
+                C = self.n_classes
+                self.ho_cm.zero_()
+                self.ho_loss.zero_()
+                if n:
+                    self.ho_cm[:n * C * C].copy_(torch.as_tensor(self.hist.ho_cm[:n].reshape(-1).astype(np.int32),
+                                                                 device=dev))
+                    self.ho_loss[:n].copy_(torch.as_tensor(self.hist.ho_loss[:n], device=dev))
+                words = np.array([np.float32(ho["best_loss_sum"]).view(np.int32), int(self.hist.ho_best_round)], np.int32)
+                if ho.get("best_flat") is not None:
+                    self.ho_best_image.copy_(img(ho["best_flat"]))
+                elif self.keep_best:
+                    # a state saved without keep_best has no image of its best round: the next round to
+                    # score starts the search again, so best_flat() never returns an image nobody wrote
+                    words = np.array([0x7F800000, -1], np.int32)
+                    self.hist.ho_best_round = -1
+                self.ho_best.copy_(torch.as_tensor(words, device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
         self.engine.invalidate()

@@ -43,7 +43,7 @@ import torch
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
 from .aggregate import _AggLaunch
-from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, gather_plane_id
+from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, gather_plane_id, heldout_metrics
 
 
 class SimRank:
@@ -66,8 +66,12 @@ class ClientGroup:
     def __init__(self, X, y, k: int, cfg: EngineConfig, backend: str = "hip", shard_mode: str = "compat",
                  seed: int = 0, alpha: float = 0.5, device=None, n_classes: Optional[int] = None,
                  tamper: Optional[Callable[[int, List[torch.Tensor]], None]] = None,
-                 wire: Optional[Callable[[int, List[torch.Tensor]], None]] = None):
-        """``tamper(r, bufs)``: optional hook for Byzantine-client studies, called every round after the
+                 wire: Optional[Callable[[int, List[torch.Tensor]], None]] = None,
+                 heldout=None, keep_best: bool = False):
+        """``heldout=(X, y)``: the lead client scores the round's global model on these rows after the
+        aggregation and the server steps of every round (``set_heldout``): :meth:`history` carries the
+        held-out keys, ``keep_best`` keeps the best round's model for :meth:`best_flat`.
+        ``tamper(r, bufs)``: optional hook for Byzantine-client studies, called every round after the
         local steps and before the aggregation with the round index and the k clients' contribution
         buffers in client order (hip: the device FedAvg buffers, on the group's stream, the padded
         parameter image first; torch: the ``fedavg_contribution`` rows, the dense parameters first);
@@ -132,6 +136,9 @@ class ClientGroup:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             for e in self.clients:
                 e.stream = self.stream   # one stream: every client's kernels and the sums in order
+        if heldout is not None:
+            Xv, yv = heldout
+            self.clients[0].set_heldout(Xv, yv, keep_best=keep_best)   # only the lead holds the set
         self.rounds = 0
 
     # ---- rounds ----
@@ -161,6 +168,7 @@ class ClientGroup:
         for e in self.clients:
             e.server_step(r)              # server optimizer: every client steps its replica of the sum
             e.rounds_issued = r + 1
+        lead.heldout_step(r)              # held-out row of the round's finished global image (lead only)
 
     def _sum_hip(self, bufs) -> None:
         with torch.cuda.stream(self.stream):
@@ -232,15 +240,22 @@ class ClientGroup:
     def global_flat(self) -> np.ndarray:
         return self.clients[0].global_flat()
 
+    def best_flat(self) -> np.ndarray:
+        """Dense weights of the round with the smallest held-out loss (``heldout=..., keep_best=True``)."""
+        return self.clients[0].best_flat()
+
 
 def rounds_to_target(X, y, k: int, cfg: EngineConfig, backend: str = "hip", seed: int = 0,
-                     targets=(0.80, 0.83), shard_mode: str = "compat") -> dict:
+                     targets=(0.80, 0.83), shard_mode: str = "compat", heldout=None) -> dict:
     """Reference-compat convergence of k clients: first round reaching each global-accuracy
-    target, the early-stop round and the final accuracy."""
-    g = ClientGroup(X, y, k, cfg, backend=backend, shard_mode=shard_mode, seed=seed)
+    target, the early-stop round and the final accuracy.  ``heldout=(X, y)``: the
+    targets and ``final_acc`` are read from the global model's accuracy on these rows instead of the
+    mean of the clients' local training accuracies, and the result's ``"metric"`` says so
+    (``"heldout_accuracy"``); without it the result is what it always was."""
+    g = ClientGroup(X, y, k, cfg, backend=backend, shard_mode=shard_mode, seed=seed, heldout=heldout)
     g.run(cfg.max_rounds)
     h = g.history()
-    acc = h["global"][:, 0]
+    acc = h["global"][:, 0] if heldout is None else heldout_metrics(h)[:, 0]
     out = {}
     for t in targets:
         hit = np.flatnonzero(acc >= t)
@@ -248,4 +263,6 @@ def rounds_to_target(X, y, k: int, cfg: EngineConfig, backend: str = "hip", seed
     out["early_stop_round"] = int(h["stop_round"]) if h["stop_round"] >= 0 else None
     out["final_acc"] = float(acc[-1]) if len(acc) else None
     out["rounds_run"] = int(h["rounds_run"])
+    if heldout is not None:
+        out["metric"] = "heldout_accuracy"
     return out

@@ -181,6 +181,26 @@ class FederatedMLPLearning:
             cm = t.numpy()
         return metrics_from_confusion(cm)
 
+    # ---- held-out scoring of the global model, inference (fedmi/fl/engine.py set_heldout) ----
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        """Score the round's global model on the held-out rows ``(X, y)`` at the end of every round
+        (``history()`` gains the ``heldout_*`` keys); ``keep_best`` keeps the best round's model
+        (:meth:`best_weights`).  ``train_and_evaluate``'s return value and console output are unchanged."""
+        self.engine.set_heldout(X, y, keep_best=keep_best)
+
+    def predict_proba(self, X, which: str = "global") -> np.ndarray:
+        """``[n, C]`` float32 class probabilities of the global (or ``which="local"``) model."""
+        return self.engine.predict_proba(X, which=which)
+
+    def predict(self, X, which: str = "global") -> np.ndarray:
+        """``[n]`` int64 classes (first-maximum argmax of the logits)."""
+        return self.engine.predict(X, which=which)
+
+    def best_weights(self) -> Dict[str, np.ndarray]:
+        """Weights of the round with the smallest held-out loss, in the reference key layout
+        (``model.{2i}.weight`` / ``.bias``); needs ``set_heldout(..., keep_best=True)``."""
+        return flat_to_dict(self.engine.best_flat(), self.engine.dims)
+
     def history(self) -> dict:
         return self.engine.history()
 

@@ -509,6 +509,11 @@ class WideClient:
         self.evaluate_shard()
         return float(self.metrics()["accuracy"])
 
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        """Refused: the wide path's layered kernels have no held-out scoring (the round engines do)."""
+        raise ValueError("WideClient does not run held-out scoring (set_heldout): use a round engine "
+                         "(HipRoundEngine / TorchRoundEngine / ClientGroup)")
+
     def run_round(self, evaluate: bool = True) -> None:
         """One federated round as the reference runs it (C:145-198): local step, local evaluation
         of the post-step model on the shard (device-side, no host sync), FedAvg buckets."""

@@ -148,6 +148,11 @@ class FedTrialGroup:
             raise ValueError(f"unknown backend {backend!r}")
         self.rounds_issued = 0
 
+    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+        """Refused: the trials of a group share launches, a held-out record per trial is not batched."""
+        raise ValueError("fed_sweep does not run held-out scoring (set_heldout): score the chosen trial's "
+                         "model afterwards (evaluate_global / predict)")
+
     # ---- HIP rounds ----
     def _issue_group_round(self, r: int) -> None:
         """Round r of every trial on the group stream (fork/join), plus the shared all-reduce."""

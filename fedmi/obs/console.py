@@ -69,6 +69,12 @@ class JsonlWriter:
             # (secure aggregation: this client's clamped / NaN coordinates of the round)
             if "secagg_clamped" in hist:
                 norm["secagg_clamped"] = int(hist["secagg_clamped"][r])
+            # (held-out scoring: the round's global model on the held-out set)
+            if "heldout_cm" in hist:
+                from ..fl.metrics import metrics_from_confusion
+                ho = metrics_from_confusion(hist["heldout_cm"][r])
+                norm.update({f"heldout_{k}": float(ho[k]) for k in METRIC_NAMES})
+                norm["heldout_loss"] = float(hist["heldout_loss"][r])
             self.write(round=r + 1, **{k: float(hist["global"][r][i]) for i, k in enumerate(METRIC_NAMES)},
                        per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **norm, **extra)
 

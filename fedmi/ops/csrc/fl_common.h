@@ -394,6 +394,26 @@ struct FLSecAgg {
     const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
 };
 
+// Held-out scoring of the round's aggregated model (fl_heldout.hip): parameters of the per-round row and
+// fold launches, passed to those kernels alone, as FLDp is.  Every buffer is caller-owned.  A live
+// round r leaves hist_cm[r] = the C x C confusion counts of the round's output image on the n held-out
+// rows (true class major, first-maximum argmax) and hist_loss[r] = the fp32 SUM of the rows' softmax
+// cross-entropies lse(z) - z[y]; the fp32 master image is read whatever the engine's operand type.
+#define FL_HELDOUT_MAX_ROWS (1 << 24)  // counts stay exact where a caller holds them in fp32
+#define FL_HELDOUT_FOLD_THREADS 1024
+struct FLHeldout {
+    const float* X;      // [n, dim0] row-major held-out rows
+    const int* y;        // [n] labels in [0, C)
+    int n;               // 1 .. FL_HELDOUT_MAX_ROWS
+    int max_rounds;      // rows of hist_cm / hist_loss; rounds past it are not live
+    int keep_best;       // 1: the fold keeps the image of the round with the smallest loss sum
+    int* scratch;        // [ceil(n / R)][C * C + 1] per-workgroup partials: counts, then the loss sum's bits
+    int* hist_cm;        // [max_rounds][C * C]
+    float* hist_loss;    // [max_rounds] fp32 loss SUMS
+    float* best_image;   // keep_best: [Pimg]
+    float* best;         // keep_best: {best loss sum (starts at +inf), best round's index as int bits (starts at -1)}
+};
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -511,6 +531,18 @@ hipError_t fl_launch_secagg_mask(const MLPDesc& d, const FLSecAgg& p, float* con
                                  uint32_t* const* clamp, const FLState* st, hipStream_t s);
 hipError_t fl_launch_secagg_open(const MLPDesc& d, const FLSecAgg& p, const float* const* src, float* const* dst,
                                  int n_dst, const FLState* st, int tails_len, hipStream_t s);
+// (fl_heldout.hip) held-out scoring of the round whose state is `st` and whose output image is `image`:
+// the row launch (one workgroup per R = 16 or 32 held-out rows, partials into p.scratch) and the fold
+// launch (one workgroup: round r's row of p.hist_cm / p.hist_loss, and with p.keep_best the best image).
+// `d`: the model's descriptor built for R rows.  A round that is not live writes nothing.  No per-round
+// host argument: both launches are replayable.  fl_set_lds_limit_heldout: once per model (dynamic LDS).
+hipError_t fl_set_lds_limit_heldout(size_t bytes);
+hipError_t fl_launch_heldout(const MLPDesc& d, int R, const FLHeldout& p, const float* image, const FLState* st,
+                             hipStream_t s);
+// ... and its row mode: the fp32 softmax of `params`' logits on rows [0, n) of X into proba[n][C] and / or
+// their first-maximum argmax into pred[n] (either may be null, not both); ungated.
+hipError_t fl_launch_heldout_predict(const MLPDesc& d, int R, const float* X, int n, const float* params,
+                                     float* proba, int* pred, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

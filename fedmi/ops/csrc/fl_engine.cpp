@@ -725,6 +725,47 @@ class FLEngine {
         drop_graph();
     }
 
+    // Held-out scoring (fl_heldout.hip): every round the engine aggregates then ends with the row and
+    // fold launches on its output image; `X` = 0 turns it off.  All buffers are caller-owned device
+    // memory (fl_common.h FLHeldout).  Kernel arguments and the round kind change (no lagged rounds
+    // while it is on), so captured graphs are dropped, as by set_debug.
+    void set_heldout(uintptr_t X, uintptr_t y, int n, uintptr_t scratch, uintptr_t hist_cm, uintptr_t hist_loss,
+                     uintptr_t best_image, uintptr_t best, bool keep_best) {
+        FLHeldout h;
+        std::memset(&h, 0, sizeof(h));
+        if (X != 0) {
+            if (n < 1 || n > FL_HELDOUT_MAX_ROWS)
+                throw std::runtime_error("set_heldout: 1 .. 2^24 held-out rows, got " + std::to_string(n));
+            if (!y || !scratch || !hist_cm || !hist_loss || (keep_best && (!best_image || !best)))
+                throw std::runtime_error("set_heldout: missing buffers");
+            h.X = as_ptr<const float>(X);
+            h.y = as_ptr<const int>(y);
+            h.n = n;
+            h.max_rounds = c_.max_rounds;
+            h.keep_best = keep_best ? 1 : 0;
+            h.scratch = as_ptr<int>(scratch);
+            h.hist_cm = as_ptr<int>(hist_cm);
+            h.hist_loss = as_ptr<float>(hist_loss);
+            h.best_image = keep_best ? as_ptr<float>(best_image) : nullptr;
+            h.best = keep_best ? as_ptr<float>(best) : nullptr;
+            prepare_heldout();
+        }
+        ho_ = h;
+        tr_.heldout_on = X != 0;
+        refresh_undo();
+        drop_graph();
+    }
+    bool heldout() const { return tr_.heldout_on; }
+    int heldout_rows_per_block() const { return ho_R(); }
+
+    // Row mode of the held-out kernel: softmax probabilities [n][C] and / or the logits' first-maximum
+    // argmax [n] of the fp32 image `params` on rows [0, n) of X (either output may be 0).
+    void predict(uintptr_t X, int n, uintptr_t params, uintptr_t proba, uintptr_t pred, uintptr_t stream) {
+        prepare_heldout();
+        HIP_CHECK(fl_launch_heldout_predict(dh_, ho_R(), as_ptr<const float>(X), n, as_ptr<const float>(params),
+                                            as_ptr<float>(proba), as_ptr<int>(pred), as_stream(stream)));
+    }
+
     // Launch one kernel of round r on its live state (0 = train, 1 = adam, 2 = eval).
     void launch_one(int r, int which, uintptr_t stream) {
         issue([&](RoundPlan& p) { plan_relaunch(p, "launch_one", r, which); }, as_stream(stream), nullptr);
@@ -788,7 +829,7 @@ class FLEngine {
         HIP_CHECK(hipStreamSynchronize(s));
         constexpr int TR_N = FLLaunchRec::N_KINDS;  // events are tagged with the launch kind
         static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
-                                          "server", "finalize", "compress"};
+                                          "server", "finalize", "compress", "heldout"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -1005,6 +1046,9 @@ class FLEngine {
             case FLLaunchRec::SERVER:
                 HIP_CHECK(fl_launch_server(d_, sv_, F(0), F(1), S(2), eb, dtype_ == 1 ? b_.pk_global : nullptr, s));
                 break;
+            case FLLaunchRec::HELDOUT:  // the row launch, then the fold launch
+                HIP_CHECK(fl_launch_heldout(dh_, ho_R(), ho_, F(0), S(1), s));
+                break;
             case FLLaunchRec::FINALIZE:
                 HIP_CHECK(fl_launch_finalize(d_, c_, b_, F(0), S(1), S(2), s, i[0],
                                              late_fold() ? pbuf_[m.par] : nullptr));
@@ -1072,6 +1116,19 @@ class FLEngine {
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
+    FLHeldout ho_ = {};        // held-out scoring: fl_heldout row + fold launches at the end of every round
+    MLPDesc dh_ = {};          // ... the fp32 forward layout at its rows per workgroup (prepare_heldout)
+    // rows per workgroup of the held-out kernels: the engine's, at most 32 (the fp32 forward's tiles)
+    int ho_R() const { return c_.R > 32 ? 32 : c_.R; }
+    void prepare_heldout() {
+        if (dh_.L != 0) return;
+        MLPDesc d;
+        fl_build_fp32_layout(d_.dim, d_.L, ho_R(), &d);
+        if ((size_t)d.lds_floats * 4 > FL_LDS_DYNAMIC_MAX)
+            throw std::runtime_error("FLEngine: the fp32 forward pass of the held-out kernels exceeds LDS");
+        HIP_CHECK(fl_set_lds_limit_heldout((size_t)d.lds_floats * 4));
+        dh_ = d;
+    }
     FLConfig c_;
     FLBuffers b_;
     float* pbuf_[2];
@@ -1117,6 +1174,7 @@ class TrialBatch {
             if (e.peer_ != nullptr) throw std::runtime_error("TrialBatch: engines must not use the peer all-reduce");
             if (e.tr_.server_on) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
             if (e.tr_.compress_on) throw std::runtime_error("TrialBatch: no compression (compress)");
+            if (e.tr_.heldout_on) throw std::runtime_error("TrialBatch: no held-out scoring (set_heldout)");
             // the batch kernels write and read dense slab rows: from here on the engine's own launches do
             // too (the row stride stays; train / Adam pairs are issued together, so no pair is split)
             engs_[k]->slab_blocked_ = false;
@@ -1196,6 +1254,7 @@ class TrialBatch {
         if (m.kind == FLLaunchRec::DP) throw std::runtime_error("trial batch: no DP");
         if (m.kind == FLLaunchRec::COMPRESS) throw std::runtime_error("trial batch: no compression");
         if (m.kind == FLLaunchRec::SERVER) throw std::runtime_error("trial batch: no server optimizer");
+        if (m.kind == FLLaunchRec::HELDOUT) throw std::runtime_error("trial batch: no held-out scoring");
         if (m.kind == FLLaunchRec::ALLREDUCE || m.kind == FLLaunchRec::EVAL_FEDAVG)
             throw std::runtime_error("trial batch: no peer all-reduce");
         if (m.kind == FLLaunchRec::ADAM && m.peer) throw std::runtime_error("trial batch: no in-kernel exchange");
@@ -1486,6 +1545,12 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def("trace", &FLEngine::trace, py::arg("r0"), py::arg("n"), py::arg("stream"), py::arg("comm") = nullptr,
              py::arg("close") = true, py::arg("gate_us") = 5000.0, py::arg("warm") = 0)
         .def("set_debug", &FLEngine::set_debug)
+        .def("set_heldout", &FLEngine::set_heldout, py::arg("X"), py::arg("y"), py::arg("n"), py::arg("scratch"),
+             py::arg("hist_cm"), py::arg("hist_loss"), py::arg("best_image"), py::arg("best"), py::arg("keep_best"))
+        .def_property_readonly("heldout", &FLEngine::heldout)
+        .def_property_readonly("heldout_rows_per_block", &FLEngine::heldout_rows_per_block)
+        .def("predict", &FLEngine::predict, py::arg("X"), py::arg("n"), py::arg("params"), py::arg("proba"),
+             py::arg("pred"), py::arg("stream"))
         .def("invalidate", &FLEngine::invalidate)
         .def("set_dp_seed", &FLEngine::set_dp_seed)
         .def("packed_global", &FLEngine::packed_global)
@@ -1530,6 +1595,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("stream"));
     m.attr("SECAGG_STREAM") = (unsigned)FL_SECAGG_STREAM;
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
+    m.attr("HELDOUT_MAX_ROWS") = (int)FL_HELDOUT_MAX_ROWS;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);
     // floats per slab row an engine of this model may need at R rows per workgroup: the dense row, or the

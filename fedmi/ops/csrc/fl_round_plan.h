@@ -50,7 +50,7 @@ inline bool operator==(const FLSel& a, const FLSel& b) { return a.base == b.base
 
 // One launch of a round.  The kinds double as trace tags (FLEngine::trace).
 struct FLLaunchRec {
-    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, COMPRESS, N_KINDS };
+    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, COMPRESS, HELDOUT, N_KINDS };
     int kind;
     int i[4];     // TRAIN: ls, stage_local, mode, fold_mask | ADAM: ls, fold, tail_a, fold_mask |
                   // FINALIZE: mask | others: 0
@@ -72,8 +72,8 @@ inline bool same_buffers(const FLLaunchRec& a, const FLLaunchRec& b) {
 }
 
 // Launches of one planning call: fixed capacity, nothing allocated per round.  A round holds at
-// most 2 * local_steps + 5 records (flush, pack, the train/Adam pairs, DP or compression, eval, all-reduce,
-// server), so engines take at most FL_PLAN_MAX_LOCAL_STEPS = 61 local steps
+// most 2 * local_steps + 6 records (flush, pack, the train/Adam pairs, DP or compression, eval, all-reduce,
+// server, held-out), so engines take at most FL_PLAN_MAX_LOCAL_STEPS = 61 local steps
 // (fedmi/fl/engine.py MAX_LOCAL_STEPS states the same number).
 #define FL_PLAN_CAP 128
 #define FL_PLAN_MAX_LOCAL_STEPS ((FL_PLAN_CAP - 5) / 2)
@@ -106,6 +106,10 @@ struct RoundTraits {
     bool server_on = false;
     bool eval_fedavg_fits = false;
     bool identity = false;  // FedAvg is the identity: world == 1 && agg_scale == 1
+    // Held-out scoring (fl_heldout.hip): every round the engine aggregates ends with a HELDOUT record on
+    // its output image.  A round that a late fold may still discard must not leave a history row (or
+    // take the best image) behind, so no rounds are lagged while it is on -- as with a foreign output.
+    bool heldout_on = false;
 
     // Lagged rounds: allowed by the layout, and either no early stopping (metrics may be
     // folded one round late), the Adam-fused exchange (which folds them in time) or an
@@ -113,7 +117,7 @@ struct RoundTraits {
     // bit-exactly -- late_fold()).  A peer all-reduce kernel without the in-kernel exchange
     // (several local steps) keeps classic rounds with early stopping: its send buffer is not the
     // output buffer a late stop republishes from.
-    bool lagged() const { return lag_ok && (!es_enabled || xchg || !has_peer); }
+    bool lagged() const { return lag_ok && !heldout_on && (!es_enabled || xchg || !has_peer); }
     bool late_fold() const { return lagged() && es_enabled && !xchg; }
     // The engine produces round outputs itself: one client, its peer all-reduce, or RCCL.
     bool aggregates(bool comm_present) const { return world < 2 || has_peer || comm_present; }
@@ -291,10 +295,20 @@ inline void plan_server(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int
     c.srv_packed = t.dtype == 1;
 }
 
+// Held-out record of round r (fl_heldout.hip): scores the round's finished output image -- aggregated,
+// after any server step -- under the round's state (live flag and index), both of the output parity.
+inline void plan_heldout(const RoundTraits& t, RoundPlan& out, int r) {
+    if (!t.heldout_on) return;
+    const int par = (r + 1) & 1;
+    out.push(FLLaunchRec::HELDOUT, 0, 0, 0, 0, par, fl_at(FL_TB_PBUF0 + par), fl_at(FL_TB_ST0 + par));
+}
+
 // `lag`: a lagged round -- no evaluation; the next round's train kernel scores it.
-// `server`: the round ends with the server-optimizer step (not when the caller aggregates).
+// `server`: the round ends with the engine's own steps on the aggregated image -- the server-optimizer
+// step, then the held-out record (neither when the caller aggregates).
 inline void plan_round(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int r, bool allow_fused, bool lag,
                        bool server, bool comm_present) {
+    const bool held = server && t.heldout_on && t.aggregates(comm_present);
     server = server && t.server_on && t.aggregates(comm_present);
     const bool fused = t.fused && allow_fused;
     lag = lag && t.lagged() && !fused;
@@ -304,7 +318,7 @@ inline void plan_round(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
     c.prev_lagged = lag;
     if (lag) {
         if (!xchg) plan_allreduce(t, out, r, comm_present);
-        return;
+        return;  // (never with held-out scoring: lagged() is false then)
     }
     if (!fused && t.has_peer && t.eval_fedavg_fits) {
         // evaluation and the one-shot all-reduce in one kernel (peer_device.h)
@@ -313,6 +327,7 @@ inline void plan_round(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
                  fl_at(FL_TB_ST0 + par));
         c.cm_in_tail = true;
         if (server) plan_server(t, c, out, r);
+        if (held) plan_heldout(t, out, r);
         return;
     }
     if (!fused) {
@@ -321,12 +336,13 @@ inline void plan_round(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
     }
     plan_allreduce(t, out, r, comm_present);
     if (server) plan_server(t, c, out, r);
+    if (held) plan_heldout(t, out, r);
 }
 
 // One phase of round r: 0 = local training (all local steps), 1 = local evaluation,
-// 2 = FedAvg all-reduce (+ the server-optimizer step when the engine aggregates itself),
-// 3 = the server-optimizer step alone (the caller aggregated the round's buffer).  Always
-// classic rounds.
+// 2 = FedAvg all-reduce (+ the server-optimizer step and the held-out record when the engine
+// aggregates itself), 3 = the server-optimizer step alone, 4 = the held-out record alone (the caller
+// aggregated the round's buffer; 4 after 3).  Always classic rounds.
 inline void plan_phase(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int r, int which, bool comm_present) {
     if (which == 0) {
         plan_flush_pending_eval(t, c, out, r);
@@ -337,12 +353,18 @@ inline void plan_phase(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
         c.cm_in_tail = true;
     } else if (which == 2) {
         plan_allreduce(t, out, r, comm_present);
-        if (t.aggregates(comm_present)) plan_server(t, c, out, r);
+        if (t.aggregates(comm_present)) {
+            plan_server(t, c, out, r);
+            plan_heldout(t, out, r);
+        }
     } else if (which == 3) {
         if (!t.server_on) throw std::runtime_error("phase 3: no server optimizer");
         plan_server(t, c, out, r);
+    } else if (which == 4) {
+        if (!t.heldout_on) throw std::runtime_error("phase 4: no held-out set");
+        plan_heldout(t, out, r);
     } else {
-        throw std::runtime_error("phase: 0, 1, 2 or 3");
+        throw std::runtime_error("phase: 0, 1, 2, 3 or 4");
     }
 }
 
