@@ -1497,6 +1497,21 @@ class HipRoundEngine(RoundEngineBase):
             return rows[:, :P].clone()
         return self.slab[:ns * stride].view(ns, stride)[:, :P].clone()
 
+    def slab_losses(self) -> torch.Tensor:
+        """The last train kernel's per-workgroup loss slots as fp32 [n_slabs]: slab row b holds the sum
+        of its rows' cross-entropies divided by the shard's n (the Adam kernel sums the slots into the
+        round's history loss).  The slot is the float at index P of a row -- of fp32 and of dense fp16
+        rows alike (fl_train_body.inc, fl_train_bf16_body.inc) -- and in a blocked fp16 row the float at
+        the index that is the row's count of gradient halves, pads included (fl_layout.h FlSlabBlk::P):
+        one past the last bias gradient, the largest position of ``slab_map()``."""
+        lay = self.engine.layout()
+        ns, stride, slot = int(lay["n_slabs"]), int(lay["slab_stride"]), self.P
+        if self.slab_f16 and lay.get("slab_blocked"):
+            slot = max(self.engine.slab_map()) + 1
+        if not slot < stride:
+            raise RuntimeError(f"slab row of {stride} floats has no loss slot at {slot}")
+        return self.slab[:ns * stride].view(ns, stride)[:, slot].clone()
+
     def _pick_slab_f16(self, cfg) -> bool:
         if cfg.grad_slab not in ("auto", "fp16", "fp32"):
             raise ValueError(f"grad_slab must be 'auto', 'fp16' or 'fp32', got {cfg.grad_slab!r}")

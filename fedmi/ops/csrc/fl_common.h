@@ -215,7 +215,8 @@ struct FLBuffers {
     const float* X;     // [n_rows, dim0] row-major, device resident
     const int* y;       // [n_rows]
     float* slab;        // [n_slabs, slab_stride] dense gradient partials (fp32; slab_f16: fp16 in the
-                        // first P halves of each row, the loss partial stays the fp32 at [P]; the
+                        // first P halves of each row, zeros up to the next multiple of 8 halves -- the Adam
+                        // kernel reads 16-byte chunks --, the loss partial stays the fp32 at [P]; the
                         // reference shape's specialised train / Adam pair keeps the fp16 row blocked
                         // instead, fl_layout.h FlSlabBlk)
     float* local;       // [Pimg] post-step local weights (evaluated, C:148)

@@ -211,6 +211,11 @@
             if ((int)threadIdx.x < sb.Pz - sb.P) slab_store_h(reinterpret_cast<uint16_t*>(slab) + sb.P + threadIdx.x, 0.f);
         } else {
             if (threadIdx.x == 0) slab[d.P] = lossv;
+            // dense fp16 row: its last 16-byte chunk is completed with zeros as well (the Adam kernel reads
+            // whole chunks and checks every half it reads for saturation); halves [P, roundup8(P)) end at or
+            // before half 2 P, where the fp32 loss slot starts (P >= 4)
+            if (c.slab_f16 && (int)threadIdx.x < ((-d.P) & 7))
+                slab_store_h(reinterpret_cast<uint16_t*>(slab) + d.P + threadIdx.x, 0.f);
         }
     }
     lds_barrier();

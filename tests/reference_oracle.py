@@ -199,12 +199,13 @@ def _bf(x):
     return x.to(torch.bfloat16).to(torch.float64)
 
 
-def _bf16_forward(flat, X, dims, plain=False):
+def _bf16_forward(flat, X, dims, plain=False, pre_out=None):
     """Forward pass of the bf16 kernels (fl_kernels_bf16.hip) in float64: every layer multiplies the
     bf16 parts of its input and weights, x_hi = bf16(x), x_lo = bf16(x - x_hi) -- split-bf16
     hi.hi + (lo.hi + hi.lo), or with ``plain`` hi.hi alone (FLConfig::plain_fwd) -- and adds the
     fp32 bias; hidden outputs are rounded to fp32 after ReLU and split again.  Returns (Ws, the hi
-    part of every layer's input, the logits)."""
+    part of every layer's input, the logits).  ``pre_out``: a list that receives every hidden layer's
+    pre-activations (tests/train_stage_oracle.py: the model's ReLU margin)."""
     from fedmi.models.mlp import flat_to_dict
     d = flat_to_dict(flat, dims)
     L = len(dims) - 1
@@ -220,15 +221,19 @@ def _bf16_forward(flat, X, dims, plain=False):
             al, wl = _bf(a - ah), _bf(Ws[l] - wh)
             z = ah @ wh.T + (al @ wh.T + ah @ wl.T) + bs[l]
         his.append(ah)
+        if pre_out is not None and l + 1 < L:
+            pre_out.append(z)
         a = torch.relu(z).to(torch.float32).to(torch.float64)
     return Ws, his, z
 
 
-def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False, plain=False):
+def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False, plain=False, n_div=None):
     """Host model of the bf16 train kernel's arithmetic (fl_kernels_bf16.hip), in float64:
     split-bf16 forward (hi.hi + lo.hi + hi.lo, hidden outputs split into hi/lo after ReLU; with
     ``plain`` the hi.hi forward of several clients' training pass), softmax-CE deltas rounded to
-    bf16, backward on the hi parts with bf16 deltas."""
+    bf16, backward on the hi parts with bf16 deltas.  ``n_div``: the mean's divisor (default: the
+    rows given) -- one workgroup's rows with the whole shard's n give that workgroup's slab row
+    (tests/train_stage_oracle.py), and n_div = 1 without ``scaled_delta`` the fp16 slab's unscaled sums."""
     L = len(dims) - 1
     Ws, his, z = _bf16_forward(flat, X, dims, plain)
     yt = torch.as_tensor(y, dtype=torch.long)
@@ -238,8 +243,9 @@ def _split_bf16_reference_grad(flat, X, y, dims, scaled_delta=False, plain=False
     dz[torch.arange(n), yt] -= 1.0
     # fp16 slab: the kernels back-propagate the unscaled delta (Adam applies the 1/n); fp32
     # slab: the delta of the mean loss
-    sc = 1.0 if scaled_delta else float(n)
-    dz = _bf(dz / n) if scaled_delta else _bf(dz)
+    div = float(n if n_div is None else n_div)
+    sc = 1.0 if scaled_delta else div
+    dz = _bf(dz / div) if scaled_delta else _bf(dz)
     gW, gb = [None] * L, [None] * L
     for l in range(L - 1, -1, -1):
         gW[l] = dz.T @ his[l] / sc

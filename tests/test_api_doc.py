@@ -30,6 +30,20 @@ def test_c_trainer_example():
         assert callable(getattr(fl, name))
 
 
+def test_slab_accessors_are_documented():
+    """The train launch's read-back accessors of the HIP engine (tests/test_train_stage.py) exist with the
+    documented names and docs/API.md says what they return."""
+    import os
+
+    from fedmi.fl.engine import HipRoundEngine
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "docs", "API.md")) as f:
+        doc = f.read()
+    for name in ("slab_partials", "slab_losses"):
+        assert callable(getattr(HipRoundEngine, name)) and getattr(HipRoundEngine, name).__doc__
+        assert f"`{name}()`" in doc, name
+    assert "`[n_slabs]`" in doc and "`[n_slabs, P]`" in doc
+
+
 def test_sklearn_examples():
     warnings.filterwarnings("ignore")
     ds = load_tabular(with_mean=False)
