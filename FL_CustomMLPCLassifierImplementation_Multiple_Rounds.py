@@ -82,11 +82,16 @@ def parse_args(argv=None):
                     help="--screen: Byzantine clients assumed, f (every round needs 2 f + 3 sampled clients)")
     ap.add_argument("--screen-keep", type=int, default=None,
                     help="--screen: clients kept per round, m (default: sampled clients - f; 1 = Krum)")
-    ap.add_argument("--compress", choices=["none", "topk", "sign"], default="none",
+    ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk"], default="none",
                     help="compress every client's round update with error feedback: topk = the largest "
-                         "--compress-ratio of its entries, sign = one bit per entry and a scale (a simulated uplink: "
-                         "the exchange stays dense; --jsonl rows carry uplink_bytes)")
-    ap.add_argument("--compress-ratio", type=float, default=0.1, help="--compress topk: fraction of entries kept, in (0, 1]")
+                         "--compress-ratio of its entries, sign = one bit per entry and a scale, qsgd = stochastic "
+                         "quantisation to --compress-levels levels, randk = a random --compress-ratio of its entries "
+                         "(a simulated uplink: the exchange stays dense; --jsonl rows carry uplink_bytes)")
+    ap.add_argument("--compress-ratio", type=float, default=0.1,
+                    help="--compress topk / randk: fraction of entries kept, in (0, 1]")
+    ap.add_argument("--compress-levels", type=int, default=127, help="--compress qsgd: quantisation levels s, in [1, 32767]")
+    ap.add_argument("--compress-seed", type=int, default=None,
+                    help="--compress qsgd / randk: seed of the random stream (default: a private draw per client)")
     ap.add_argument("--no-error-feedback", action="store_true",
                     help="--compress: discard what the compressor drops instead of carrying it to the next round")
     ap.add_argument("--secagg", action="store_true",
@@ -217,7 +222,8 @@ def _screen_fields(a) -> dict:
 
 
 def _compress_fields(a) -> dict:
-    return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback)
+    return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback,
+                compress_levels=a.compress_levels, compress_seed=a.compress_seed)
 
 
 def _secagg_fields(a) -> dict:
@@ -333,7 +339,7 @@ def main(argv=None):
         from fedmi.fl.compress import compress_id
         compress_id(EngineConfig(**_dp_fields(a), **_compress_fields(a)))
     except ValueError as e:
-        raise SystemExit(f"--compress / --compress-ratio: {e}")
+        raise SystemExit(f"--compress / --compress-ratio / --compress-levels / --compress-seed: {e}")
     if a.wide and a.secagg:
         raise SystemExit("--secagg is not supported with --wide")
     try:

@@ -139,7 +139,10 @@ def save_checkpoint(path: str, trainer) -> None:
     # compression: the client's own residual (dense order) and its per-round statistic
     cp = {} if "compress_residual" not in st else {
         "compress_residual": np.asarray(st["compress_residual"], np.float32),
-        "compress_stat": np.asarray(st["history"]["compress_stat"], np.float32)}
+        "compress_stat": np.asarray(st["history"]["compress_stat"], np.float32),
+        # the stochastic kinds: the client's seed (two 32-bit words, as dp_seed)
+        **({} if "compress_seed" not in st else {"compress_seed": np.asarray(
+            [int(st["compress_seed"]) & 0xFFFFFFFF, int(st["compress_seed"]) >> 32], np.int64)})}
     # secure aggregation: the config's three fields are all a resume needs (the mask seed is no state);
     # the client's own per-round clamp counts stay in its file, as its update norms do
     sa = {} if "secagg_clamped" not in st["history"] else {
@@ -235,6 +238,9 @@ def resume(path: str, trainer) -> int:
     if "compress_residual" in c:
         st["compress_residual"] = np.asarray(c["compress_residual"], np.float32)
         st["history"]["compress_stat"] = np.asarray(c["compress_stat"], np.float32)
+    if "compress_seed" in c:
+        lo, hi = (int(x) for x in np.asarray(c["compress_seed"]).reshape(-1)[:2])
+        st["compress_seed"] = lo | (hi << 32)
     if "secagg_clamped" in c:
         st["history"]["secagg_clamped"] = np.asarray(c["secagg_clamped"], np.int64)
     if "heldout_cm" in c:

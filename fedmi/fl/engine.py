@@ -32,7 +32,7 @@ from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, 
                           param_count)
 from .aggregate import (AGGREGATORS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch, mask_bits, pair_distances_torch,
                         robust_aggregate_torch, screen_select)
-from .compress import COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
+from .compress import COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
 from .secagg import (MAX_SECAGG_CLIENTS, SECAGG_STREAM, secagg_id, secagg_mask, secagg_open,
@@ -156,10 +156,19 @@ class EngineConfig:
     # compress.uplink_bytes report what a real uplink would carry.  "none": off (nothing of a round
     # changes).  The local model, Adam moments, FedProx anchor and local metrics are untouched; rounds
     # are classic; history()["compress_stat"] holds the k-th kept magnitude (top-k) / the scale (sign).
+    # Two stochastic compressors draw Philox words of (compress_seed, round, client): "qsgd" quantises
+    # |u| / ||u||_2 to compress_levels = s levels with stochastic rounding (Alistarh et al. 2017, one
+    # bucket; unbiased; compress_stat = the norm), "randk" keeps k random entries (k as for top-k; the
+    # indices follow from the seed, so only the values travel; with error_feedback the memory variant,
+    # without it the kept entries are scaled by P / k, the unbiased variant; compress_stat = the
+    # selection's quantile).  compress_seed: None = a private 64-bit draw per client (kept in the portable
+    # state, so a resume continues the stream), an int in [0, 2**64) = reproducible runs.
     # Not with dp_clip > 0, trial batches (comm_buffers), fed_sweep or WideClient.
     compress: str = "none"
     compress_ratio: float = 0.1
     error_feedback: bool = True
+    compress_levels: int = 127
+    compress_seed: Optional[int] = None
     # Secure aggregation (fedmi/fl/secagg.py; Bonawitz et al. 2017): every sampled client quantises its
     # weighted contribution to fixed point with secagg_bits fractional bits and adds / subtracts one
     # Philox mask per pair of the round's sampled clients (mod 2^32) before the exchange; the masks
@@ -381,7 +390,7 @@ class _History:
         self.clamped = np.zeros(max_rounds, dtype=np.int64) if secagg else None
         # DP engines: this client's pre-clip update norm per round (0: not sampled)
         self.norm = np.zeros(max_rounds, dtype=np.float32) if dp else None
-        # compressing engines: the round's statistic (top-k: k-th kept magnitude; sign: scale; 0: not sampled)
+        # compressing engines: the round's statistic (top-k: k-th kept magnitude; sign: scale; qsgd: norm; rand-k: the selection's quantile; 0: not sampled)
         self.cstat = np.zeros(max_rounds, dtype=np.float32) if compress else None
         self.glob = np.zeros((max_rounds, 4))
         self.rank = np.zeros((max_rounds, world, 4))
@@ -427,7 +436,12 @@ class RoundEngineBase:
         self.cfg = cfg
         self.dp = dp_enabled(cfg)
         self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
-        self.compress = compress_id(cfg)   # index in COMPRESSORS; 0 = dense contributions
+        self.compress = compress_id(cfg)   # index in ALL_COMPRESSORS; 0 = dense contributions
+        # the stochastic kinds carry one more piece of state: the client's seed (config, or a private draw)
+        self.compress_random = cfg.compress in RANDOM_COMPRESSORS
+        if self.compress_random:
+            self.compress_seed = (int.from_bytes(os.urandom(8), "little") if cfg.compress_seed is None
+                                  else int(cfg.compress_seed))
         gather_plane_id(cfg)               # validated by every engine; only a multi-rank HIP engine reads it
         self.comm = comm
         self.world = comm.size if comm is not None else 1
@@ -709,10 +723,26 @@ class RoundEngineBase:
     def _set_dp_seed(self, seed: int) -> None:
         self.dp_seed = int(seed)
 
+    def _load_compress_seed(self, st: dict) -> None:
+        """A resumed engine with a stochastic compressor continues the checkpoint's stream (a private
+        seed drawn at construction is replaced by the saved one)."""
+        if self.compress_random and st.get("compress_seed") is not None:
+            self._set_compress_seed(int(st["compress_seed"]))
+
+    def _set_compress_seed(self, seed: int) -> None:
+        self.compress_seed = int(seed)
+
+    def _compress_state_out(self, residual) -> dict:
+        """The compression entries of a portable state: the dense residual and, stochastic kinds, the seed."""
+        if not self.compress:
+            return {}
+        return {"compress_residual": residual,
+                **({"compress_seed": int(self.compress_seed)} if self.compress_random else {})}
+
     def uplink_bytes(self) -> int:
         """Bytes per round a real uplink would carry for this client's contribution (the exchange
         itself stays dense: compression is simulated)."""
-        return uplink_bytes(self.cfg.compress, self.compress_k, self.P)
+        return uplink_bytes(self.cfg.compress, self.compress_k, self.P, int(self.cfg.compress_levels))
 
     def _compress_state_in(self, st: dict):
         """The dense compression residual of a portable state for this engine, or None without
@@ -724,6 +754,10 @@ class RoundEngineBase:
                              + repr(self.cfg.compress))
         if not self.compress:
             return None
+        if (st.get("compress_seed") is not None) != self.compress_random:
+            raise ValueError("checkpoint and engine disagree on compression: the state "
+                             + ("carries" if not self.compress_random else "has no")
+                             + " compress_seed, the engine has compress=" + repr(self.cfg.compress))
         e = np.asarray(st["compress_residual"], np.float32).reshape(-1)
         if e.shape != (self.P,):
             raise ValueError(f"compression residual has {e.shape[0]} entries, the model {self.P}")
@@ -958,8 +992,10 @@ class TorchRoundEngine(RoundEngineBase):
         if active:
             x = self._dp_input.to(torch.float32)
             u = (local.to(torch.float32) - x) + self.compress_residual
+            rnd = (dict(levels=int(self.cfg.compress_levels), seed=self.compress_seed, round=r, client=self.rank)
+                   if self.compress_random else {})
             c, self.compress_residual, stat = compress_torch(u, self.cfg.compress, self.compress_k,
-                                                             bool(self.cfg.error_feedback))
+                                                             bool(self.cfg.error_feedback), **rnd)
             self.hist.cstat[r] = stat
             out = x + c
         self._compressed = (r, out)
@@ -1167,7 +1203,7 @@ class TorchRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
-            **({"compress_residual": self.compress_residual.numpy().copy()} if self.compress else {}),
+            **self._compress_state_out(self.compress_residual.numpy().copy() if self.compress else None),
             **self._heldout_state_out(None if not self.heldout or self._ho_best_flat is None
                                       else self._ho_best_flat.copy()),
         }
@@ -1215,6 +1251,7 @@ class TorchRoundEngine(RoundEngineBase):
         self.rounds_issued = r
         self._load_history(st["history"])
         self._load_dp_seed(st)
+        self._load_compress_seed(st)
 
 
 # ---------------------------------------------------------------------------------------
@@ -1376,6 +1413,8 @@ class HipRoundEngine(RoundEngineBase):
             self.cp_stat = torch.zeros(mr, dtype=torch.float32, device=dev)
             ecfg.update({"compress": int(self.compress), "compress_k": int(self.compress_k),
                          "error_feedback": bool(cfg.error_feedback)})
+            if self.compress_random:
+                ecfg.update({"compress_levels": int(cfg.compress_levels), "compress_seed": int(self.compress_seed)})
             bufs.update({"compress_residual": self.cp_res.data_ptr(), "compress_stat": self.cp_stat.data_ptr()})
         if self.server:
             # server optimizer state: image-shaped fp32 (m = 0; v = tau^2 everywhere, padding included)
@@ -2150,7 +2189,7 @@ class HipRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
-            **({"compress_residual": self.compress_residual} if self.compress else {}),
+            **self._compress_state_out(self.compress_residual if self.compress else None),
             **self._heldout_state_out(None if not (self.heldout and self.keep_best and self._ho_best_words()[1] >= 0)
                                       else self.best_flat()),
         }
@@ -2228,6 +2267,7 @@ class HipRoundEngine(RoundEngineBase):
                 self.ho_best.copy_(torch.as_tensor(words, device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
+        self._load_compress_seed(st)
         self.engine.invalidate()
         self.engine.reset_pending()
         self.rounds_issued = r
@@ -2236,6 +2276,11 @@ class HipRoundEngine(RoundEngineBase):
     def _set_dp_seed(self, seed: int) -> None:
         self.dp_seed = int(seed)
         self.engine.set_dp_seed(int(seed))   # a kernel argument: the native engine drops its graphs
+        self._graph_ready = False
+
+    def _set_compress_seed(self, seed: int) -> None:
+        self.compress_seed = int(seed)
+        self.engine.set_compress_seed(int(seed))   # a kernel argument: the native engine drops its graphs
         self._graph_ready = False
 
     def state_dict(self) -> dict:

@@ -63,7 +63,7 @@ class JsonlWriter:
         for r in range(hist["rounds_run"]):
             # (DP engines: this client's pre-clip update norm of the round, 0 when not sampled)
             norm = {"update_norm": float(hist["update_norm"][r])} if "update_norm" in hist else {}
-            # (compressing engines: the round's statistic -- k-th kept magnitude / sign scale)
+            # (compressing engines: the round's statistic -- k-th kept magnitude / sign scale / qsgd norm / rand-k quantile)
             if "compress_stat" in hist:
                 norm["compress_stat"] = float(hist["compress_stat"][r])
             # (secure aggregation: this client's clamped / NaN coordinates of the round)

@@ -321,9 +321,22 @@ struct FLServer {
 //   FL_COMPRESS_TOPK : C keeps the k entries of largest |u| (ties: lower dense index first), e' = u elsewhere
 //   FL_COMPRESS_SIGN : C(u) = copysign(s, u), s = sum|u| / P;                              e' = u - C(u)
 // (Stich et al. 2018; Karimireddy et al. 2019).  The exchange still carries the dense image.
+// The two stochastic kinds draw, for dense parameter p, word p % 4 of Philox4x32-10 at counter
+// (p / 4, round, client, FL_QSGD_STREAM / FL_RANDK_STREAM) under (key0, key1); the round comes from the
+// device state, so a replayed graph draws fresh words:
+//   FL_COMPRESS_QSGD  : norm = sqrt(sum u^2); level = floor(a) + ((word >> 8) < frac(a) 2^24), a = min(|u| / norm * levels,
+//                       levels); C(u) = copysign(norm * level / levels, u), e' = u - C(u); norm 0 or not finite: C(u) = u
+//   FL_COMPRESS_RANDK : C keeps the k entries of largest word >> 1 (ties: lower dense index first); with error
+//                       feedback C(u) = u there and e' = u elsewhere, without it C(u) = u * (P / k) there (unbiased)
+// (Alistarh et al. 2017; Stich et al. 2018).
 #define FL_COMPRESS_NONE 0
 #define FL_COMPRESS_TOPK 1
 #define FL_COMPRESS_SIGN 2
+#define FL_COMPRESS_QSGD 3
+#define FL_COMPRESS_RANDK 4
+#define FL_COMPRESS_MAX_LEVELS 32767
+#define FL_QSGD_STREAM 0x44475351u   // distinct from each other, the DP noise stream 0x46454450 (fl_dp.hip)
+#define FL_RANDK_STREAM 0x4B444E52u  // and FL_SECAGG_STREAM
 struct FLCompress {
     int kind;            // FL_COMPRESS_*
     int k;               // top-k: entries kept, 1 .. P
@@ -332,7 +345,11 @@ struct FLCompress {
     int max_rounds;      // entries of stat_hist; rounds past it are not live
     float* residual;     // [2][Pimg] fp32, caller-owned, zero at start: round r reads half r & 1 and writes
                          // half (r + 1) & 1 (every workgroup reads the whole old residual, fl_compress.hip)
-    float* stat_hist;    // [max_rounds] top-k: magnitude of the k-th kept entry; sign: s (0: not sampled)
+    float* stat_hist;    // [max_rounds] top-k: magnitude of the k-th kept entry; sign: s; qsgd: the norm; randk:
+                         // (word >> 1) 2^-31 of the k-th kept entry (0: not sampled)
+    int levels;          // qsgd: quantisation levels s, 1 .. FL_COMPRESS_MAX_LEVELS
+    int client;          // stochastic kinds: third word of the counter (the rank / client index, as FLDp::rank)
+    uint32_t key0, key1; // stochastic kinds: Philox key, the client's 64-bit compress seed, low and high word
 };
 
 // Robust aggregation (fl_robust.hip; Yin et al. 2018): parameters of the per-round coordinate-wise
@@ -492,7 +509,7 @@ hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, con
 // (fl_compress.hip) compression of the round whose last Adam kernel wrote state `st`: rewrites the
 // real parameters of the first Pimg floats of `comm` from `local`, the round's input image `pg` and
 // the residual.  fl_set_lds_limit_compress: once per model before the first launch (dynamic LDS).
-hipError_t fl_set_lds_limit_compress(const MLPDesc& d);
+hipError_t fl_set_lds_limit_compress(const MLPDesc& d, int kind = FL_COMPRESS_TOPK);
 hipError_t fl_launch_compress(const MLPDesc& d, const FLCompress& p, const float* local, const float* pg, float* comm,
                               const FLState* st, const float* rtab, hipStream_t s);
 // (fl_server.hip) server-optimizer step of the round whose state is `st`: `x` = the image the round

@@ -301,10 +301,20 @@ class FLEngine {
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
         }
         if (tr_.compress_on) {
-            if (cp_.kind != FL_COMPRESS_TOPK && cp_.kind != FL_COMPRESS_SIGN)
+            if (cp_.kind < FL_COMPRESS_TOPK || cp_.kind > FL_COMPRESS_RANDK)
                 throw std::runtime_error("FLEngine: unknown compressor");
             cp_.P = d_.P;
-            cp_.k = cp_.kind == FL_COMPRESS_TOPK ? cfg["compress_k"].cast<int>() : d_.P;
+            cp_.k = cp_.kind == FL_COMPRESS_TOPK || cp_.kind == FL_COMPRESS_RANDK ? cfg["compress_k"].cast<int>() : d_.P;
+            if (compress_random()) {
+                // the stochastic kinds: words of (compress_seed, round, this client), fl_compress.hip
+                const unsigned long long seed = cfg["compress_seed"].cast<unsigned long long>();
+                cp_.levels = cp_.kind == FL_COMPRESS_QSGD ? cfg["compress_levels"].cast<int>() : 0;
+                cp_.client = c_.rank;
+                cp_.key0 = (uint32_t)seed;
+                cp_.key1 = (uint32_t)(seed >> 32);
+                if (cp_.kind == FL_COMPRESS_QSGD && (cp_.levels < 1 || cp_.levels > FL_COMPRESS_MAX_LEVELS))
+                    throw std::runtime_error("FLEngine: compress_levels must be in 1 .. 32767");
+            }
             cp_.error_feedback = cfg["error_feedback"].cast<bool>() ? 1 : 0;
             cp_.max_rounds = c_.max_rounds;
             cp_.residual = as_ptr<float>(bufs["compress_residual"].cast<uintptr_t>());
@@ -312,7 +322,7 @@ class FLEngine {
             if (cp_.k < 1 || cp_.k > d_.P) throw std::runtime_error("FLEngine: compress_k must be in 1 .. P");
             if (cp_.residual == nullptr || cp_.stat_hist == nullptr)
                 throw std::runtime_error("FLEngine: compression needs the residual and the statistic history");
-            HIP_CHECK(fl_set_lds_limit_compress(d_));
+            HIP_CHECK(fl_set_lds_limit_compress(d_, cp_.kind));
         }
         if (tr_.server_on) {
             if (sv_.kind < FL_SERVER_SGD || sv_.kind > FL_SERVER_YOGI)
@@ -631,6 +641,15 @@ class FLEngine {
         drop_graph();
     }
 
+    // Philox key of a stochastic compressor (resume: the checkpoint's stream continues); a kernel
+    // argument, so captured graphs are dropped.
+    void set_compress_seed(unsigned long long seed) {
+        if (!compress_random()) throw std::runtime_error("set_compress_seed: no stochastic compressor (qsgd, randk)");
+        cp_.key0 = (uint32_t)seed;
+        cp_.key1 = (uint32_t)(seed >> 32);
+        drop_graph();
+    }
+
     // bf16 engines: the packed split-bf16 image of the round's input weights as the train kernel
     // stages it (param_bytes; tests compare the server step's pack with the stand-alone one)
     py::bytes packed_global(uintptr_t stream) const {
@@ -910,13 +929,20 @@ class FLEngine {
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
         {
             // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
-            static const char* compress_names[] = {"none", "topk", "sign"};
+            static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk"};
             const long long P = d_.P, k = tr_.compress_on ? cp_.k : P;
+            long long code_bits = 0;  // qsgd: ceil(log2(2 s + 1)), a fixed-width sign-and-level code
+            while ((1ll << code_bits) < 2ll * cp_.levels + 1) ++code_bits;
             py::dict c;
             c["kind"] = std::string(compress_names[cp_.kind]);
             c["k"] = (int)k;
             c["dense_bytes"] = 4 * P;
-            c["uplink_bytes"] = cp_.kind == FL_COMPRESS_TOPK ? 8 * k : cp_.kind == FL_COMPRESS_SIGN ? 4 + (P + 7) / 8 : 4 * P;
+            c["uplink_bytes"] = cp_.kind == FL_COMPRESS_TOPK   ? 8 * k
+                                : cp_.kind == FL_COMPRESS_SIGN ? 4 + (P + 7) / 8
+                                : cp_.kind == FL_COMPRESS_QSGD ? 4 + (P * code_bits + 7) / 8
+                                : cp_.kind == FL_COMPRESS_RANDK ? 4 * k
+                                                               : 4 * P;
+            if (cp_.kind == FL_COMPRESS_QSGD) c["levels"] = cp_.levels;
             o["compress"] = c;
         }
         static const char* server_names[] = {"none", "sgd", "adagrad", "adam", "yogi"};
@@ -1115,6 +1141,7 @@ class FLEngine {
     void** sa_tab_ = nullptr;        // ... device pointer tables of the mask launch: {send 0, send 1, clamp history}
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
+    bool compress_random() const { return cp_.kind == FL_COMPRESS_QSGD || cp_.kind == FL_COMPRESS_RANDK; }
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLHeldout ho_ = {};        // held-out scoring: fl_heldout row + fold launches at the end of every round
     MLPDesc dh_ = {};          // ... the fp32 forward layout at its rows per workgroup (prepare_heldout)
@@ -1471,13 +1498,15 @@ static void secagg_open(std::vector<int> dims, int bits, uintptr_t src, int K, u
 // round state and per-round table.
 static void compress_launch(std::vector<int> dims, int kind, int k, bool error_feedback, uintptr_t local, uintptr_t x,
                             uintptr_t comm, uintptr_t residual, uintptr_t stat, uintptr_t state, uintptr_t rtab,
-                            int max_rounds, uintptr_t stream) {
+                            int max_rounds, uintptr_t stream, int levels, int client, unsigned long long seed) {
     const MLPDesc d = desc_of(dims, "compress_launch");
-    if (kind != FL_COMPRESS_TOPK && kind != FL_COMPRESS_SIGN)
-        throw std::runtime_error("compress_launch: kind must be 1 (topk) or 2 (sign)");
+    if (kind < FL_COMPRESS_TOPK || kind > FL_COMPRESS_RANDK)
+        throw std::runtime_error("compress_launch: kind must be 1 (topk), 2 (sign), 3 (qsgd) or 4 (randk)");
+    if (kind == FL_COMPRESS_QSGD && (levels < 1 || levels > FL_COMPRESS_MAX_LEVELS))
+        throw std::runtime_error("compress_launch: levels must be in 1 .. 32767");
     if (max_rounds < 1 || !local || !x || !comm || !residual || !stat || !state || !rtab)
         throw std::runtime_error("compress_launch: bad arguments");
-    if (kind == FL_COMPRESS_SIGN) k = d.P;
+    if (kind == FL_COMPRESS_SIGN || kind == FL_COMPRESS_QSGD) k = d.P;
     if (k < 1 || k > d.P) throw std::runtime_error("compress_launch: k must be in 1 .. P");
     FLCompress p;
     std::memset(&p, 0, sizeof(p));
@@ -1488,7 +1517,11 @@ static void compress_launch(std::vector<int> dims, int kind, int k, bool error_f
     p.max_rounds = max_rounds;
     p.residual = as_ptr<float>(residual);
     p.stat_hist = as_ptr<float>(stat);
-    HIP_CHECK(fl_set_lds_limit_compress(d));
+    p.levels = levels;
+    p.client = client;
+    p.key0 = (uint32_t)seed;
+    p.key1 = (uint32_t)(seed >> 32);
+    HIP_CHECK(fl_set_lds_limit_compress(d, kind));
     HIP_CHECK(fl_launch_compress(d, p, as_ptr<const float>(local), as_ptr<const float>(x), as_ptr<float>(comm),
                                  as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
 }
@@ -1553,6 +1586,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
              py::arg("pred"), py::arg("stream"))
         .def("invalidate", &FLEngine::invalidate)
         .def("set_dp_seed", &FLEngine::set_dp_seed)
+        .def("set_compress_seed", &FLEngine::set_compress_seed)
         .def("packed_global", &FLEngine::packed_global)
         .def("packed_local", &FLEngine::packed_local)
         .def("set_early_stop", &FLEngine::set_early_stop)
@@ -1586,7 +1620,8 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("hist"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
     m.def("compress_launch", &compress_launch, py::arg("dims"), py::arg("kind"), py::arg("k"),
           py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
-          py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+          py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"),
+          py::arg("levels") = 127, py::arg("client") = 0, py::arg("seed") = 0ull);
     m.def("secagg_mask", &secagg_mask, py::arg("dims"), py::arg("bits"), py::arg("seed"), py::arg("bufs"), py::arg("n"),
           py::arg("first_client"), py::arg("state"), py::arg("rtab"), py::arg("clamp"), py::arg("max_rounds"),
           py::arg("stream"));
@@ -1594,6 +1629,8 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"), py::arg("max_rounds"),
           py::arg("stream"));
     m.attr("SECAGG_STREAM") = (unsigned)FL_SECAGG_STREAM;
+    m.attr("QSGD_STREAM") = (unsigned)FL_QSGD_STREAM;
+    m.attr("RANDK_STREAM") = (unsigned)FL_RANDK_STREAM;
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.attr("HELDOUT_MAX_ROWS") = (int)FL_HELDOUT_MAX_ROWS;
     m.def("device_info", &device_info);

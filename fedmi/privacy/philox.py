@@ -14,6 +14,10 @@ from __future__ import annotations
 import numpy as np
 
 DP_STREAM = 0x46454450
+# Streams of the stochastic update compressors (fedmi/fl/compress.py; FL_QSGD_STREAM / FL_RANDK_STREAM of
+# fedmi/ops/csrc/fl_common.h): same counter layout, the words used as they come (param_words)
+QSGD_STREAM = 0x44475351
+RANDK_STREAM = 0x4B444E52
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9
@@ -60,6 +64,20 @@ def box_muller(o: np.ndarray) -> np.ndarray:
 def seed_key(seed: int):
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     return seed & 0xFFFFFFFF, seed >> 32
+
+
+def param_words(n_params: int, round_index: int, rank: int, seed: int, stream: int) -> np.ndarray:
+    """The 32-bit word of dense parameters ``0 .. n_params - 1`` for (round, rank) on ``stream``:
+    parameter ``p`` takes word ``p % 4`` of the block at counter ``(p // 4, round, rank, stream)``
+    under ``seed_key(seed)``; uint32."""
+    n_params = int(n_params)
+    nq = (n_params + 3) // 4
+    ctr = np.empty((nq, 4), np.uint64)
+    ctr[:, 0] = np.arange(nq, dtype=np.uint64)
+    ctr[:, 1] = int(round_index) & 0xFFFFFFFF
+    ctr[:, 2] = int(rank) & 0xFFFFFFFF
+    ctr[:, 3] = int(stream) & 0xFFFFFFFF
+    return philox4x32_10(ctr, seed_key(seed)).reshape(-1)[:n_params]
 
 
 def dp_normals(n_params: int, round_index: int, rank: int, seed: int) -> np.ndarray:
