@@ -69,11 +69,17 @@ def parse_args(argv=None):
     ap.add_argument("--server-momentum", type=float, default=0.9, help="server momentum b1")
     ap.add_argument("--server-beta2", type=float, default=0.99, help="server second-moment decay b2 (adam, yogi)")
     ap.add_argument("--server-tau", type=float, default=1e-3, help="server adaptivity tau (adagrad, adam, yogi)")
-    ap.add_argument("--aggregator", choices=["mean", "median", "trimmed_mean"], default="mean",
+    ap.add_argument("--aggregator", choices=["mean", "median", "trimmed_mean", "geomed"], default="mean",
                     help="aggregation rule: mean = sample-weighted FedAvg (the reference); median / trimmed_mean = "
-                         "coordinate-wise, unweighted, Byzantine-robust (Yin et al. 2018)")
+                         "coordinate-wise, unweighted, Byzantine-robust (Yin et al. 2018); geomed = the geometric "
+                         "median of the whole models by smoothed Weiszfeld iterations (Pillutla et al. 2022, RFA; "
+                         "not with --wide or --gather-plane xgmi)")
     ap.add_argument("--trim-ratio", type=float, default=0.1,
                     help="--aggregator trimmed_mean: fraction beta cut at EACH end, in [0, 0.5)")
+    ap.add_argument("--geomed-iters", type=int, default=3,
+                    help="--aggregator geomed: Weiszfeld iterations from the coordinate-wise median, 1 .. 32")
+    ap.add_argument("--geomed-nu", type=float, default=1e-6,
+                    help="--aggregator geomed: smoothing, the lower bound of a distance in a weight, > 0")
     ap.add_argument("--screen", choices=["none", "multi_krum"], default="none",
                     help="client screening in front of the aggregator: multi_krum (Blanchard et al. 2017) keeps the "
                          "clients whose whole models lie closest to their neighbours; --aggregator mean then averages "
@@ -214,7 +220,7 @@ def _server_fields(a) -> dict:
 
 
 def _aggregator_fields(a) -> dict:
-    return dict(aggregator=a.aggregator, trim_ratio=a.trim_ratio)
+    return dict(aggregator=a.aggregator, trim_ratio=a.trim_ratio, geomed_iters=a.geomed_iters, geomed_nu=a.geomed_nu)
 
 
 def _screen_fields(a) -> dict:
@@ -323,9 +329,9 @@ def main(argv=None):
         raise SystemExit("--aggregator is not supported with --wide")
     try:
         from fedmi.fl.engine import aggregator_id
-        aggregator_id(EngineConfig(**_dp_fields(a), **_aggregator_fields(a)))
+        aggregator_id(EngineConfig(**_dp_fields(a), **_aggregator_fields(a), **_gather_fields(a)))
     except ValueError as e:
-        raise SystemExit(f"--aggregator / --trim-ratio: {e}")
+        raise SystemExit(f"--aggregator / --trim-ratio / --geomed-iters / --geomed-nu: {e}")
     if a.wide and a.screen != "none":
         raise SystemExit("--screen is not supported with --wide")
     try:

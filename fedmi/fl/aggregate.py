@@ -36,6 +36,24 @@ a distance matrix (the select kernel's model, and what the torch engines run).  
 compute their distances with :func:`pair_distances_torch`, fp32 in torch's own summation order: their
 kept set can differ from the HIP engines' only where two scores lie within fp32 summation error of
 each other.
+
+The geometric median (``aggregator="geomed"``; Pillutla, Kakade, Harchaoui 2022, "Robust Aggregation for
+Federated Learning", RFA) sits between the two: a whole-vector rule that needs no ``f``, with breakdown
+point 1/2, every client pulling with at most unit force.  It iterates, so it is no ``AGGREGATORS``
+entry (those are one-launch rules) but the ``ITERATIVE_AGGREGATORS`` one, id 3 in ``ALL_AGGREGATORS``.
+With ``T = geomed_iters`` and ``nu = float32(geomed_nu)``, over the sampled (and, behind a screen, kept)
+clients ``S``:
+
+* ``z_0`` = the coordinate-wise median of ``S``, exactly the rule above;
+* ``T`` times: ``d_i = sum (v_i - z_t)^2`` over the real parameters; the clients with ``d_i < +inf`` are
+  included (NaN, inf and overflow exclude a client for that iteration -- selected out, never multiplied
+  by 0); ``b_i = 1 / max(nu, sqrt(d_i))``; ``z_{t+1} = (sum b_i v_i) / (sum b_i)``, both sums in client
+  order from ``+0``, one division; nobody included: ``z_{t+1} = z_t``.
+
+:func:`geomed_model` is the bit-exact fp32 model of the launches (``fedmi/ops/csrc/fl_geomed.hip``) over
+parameter images, with the distances added in the kernel's one order (:func:`geomed_block_sums`);
+:func:`geomed_torch` is the rule in the tensor's dtype with torch's own summation order: what the torch
+engines run in fp32, and the float64 oracle in float64.
 """
 from __future__ import annotations
 
@@ -46,9 +64,21 @@ import numpy as np
 import torch
 
 AGGREGATORS = ("mean", "median", "trimmed_mean")
+# rules that iterate over whole models (several launches, scratch of their own); ids follow AGGREGATORS'
+ITERATIVE_AGGREGATORS = ("geomed",)
+ALL_AGGREGATORS = AGGREGATORS + ITERATIVE_AGGREGATORS
 MAX_ROBUST_CLIENTS = 64   # width of the per-round sampled-client mask (fl_common.h FL_ROBUST_MAX_K)
 SCREENS = ("none", "multi_krum")
 _SCREEN_THREADS = 256     # workgroup of the distance kernel (fl_screen.hip FL_SCREEN_THREADS)
+GEOMED_MAX_ITERS = 32     # fl_common.h FL_GEOMED_MAX_ITERS
+GEOMED_BLOCK = 256        # floats of the image per block of a distance sum (fl_common.h FL_GEOMED_THREADS)
+GEOMED_SLOT = 192         # floats of one iteration's record in the scratch (fl_common.h FL_GEOMED_SLOT)
+
+
+def geomed_scratch_floats(pimg: int, iters: int) -> int:
+    """Floats of scratch the geomed launches need for an image of ``pimg`` floats (fl_common.h
+    fl_geomed_scratch_floats): two sets of 64 distance partials per block, then ``iters`` records."""
+    return 2 * ((int(pimg) + GEOMED_BLOCK - 1) // GEOMED_BLOCK) * MAX_ROBUST_CLIENTS + int(iters) * GEOMED_SLOT
 
 
 def trim_count(kind: str, beta: float, k_r: int) -> int:
@@ -85,7 +115,11 @@ class _AggLaunch:
         self._src = [table(s) for s in src]
         self._dst = self._src if dst is src else [table(s) for s in dst]
         self._clamp = table(clamps)
-        self._dist = self._keep = None
+        self._dist = self._keep = self._geomed = None
+        if ALL_AGGREGATORS[getattr(lead, "robust", 0)] == "geomed":
+            # distance partials and the iterations' records (weights, distances, combined mask) of the geomed launches
+            self._geomed = torch.zeros(geomed_scratch_floats(lead.Pimg, int(lead.cfg.geomed_iters)),
+                                       dtype=torch.float32, device=lead.device)
         if getattr(lead, "screen", 0):
             self._dist = torch.zeros(self._k * self._k, dtype=torch.float32, device=lead.device)
             self._keep = torch.zeros(2, dtype=torch.int64, device=lead.device)
@@ -106,6 +140,12 @@ class _AggLaunch:
                             int(e.cfg.max_rounds), stream)
             e.m.screen_select(self._dist.data_ptr(), self._k, int(e.cfg.screen_byzantine), int(e.cfg.screen_keep or 0),
                               word, e.screen_hist.data_ptr(), *self._round(par), int(e.cfg.max_rounds), stream)
+        if self._geomed is not None:
+            # the geometric median: geomed_iters + 1 launches (fl_geomed.hip) in the place of the one
+            e.m.geomed_aggregate(e.dims, int(e.cfg.geomed_iters), float(e.cfg.geomed_nu), self._src[par].data_ptr(),
+                                 self._k, self._dst[par].data_ptr(), self._n, *self._round(par),
+                                 self._k * e.tail_stride, int(e.cfg.max_rounds), self._geomed.data_ptr(), stream, *keep)
+            return
         e.m.robust_aggregate(e.dims, e.robust, float(e.robust_beta), self._src[par].data_ptr(), self._k,
                              self._dst[par].data_ptr(), self._n, *self._round(par), self._k * e.tail_stride,
                              int(e.cfg.max_rounds), stream, *keep)
@@ -158,6 +198,123 @@ def robust_aggregate_torch(stack: torch.Tensor, active_mask: Sequence[bool], kin
             keep = (rank[i] >= t) & (rank[i] < k_r - t)
             acc = torch.where(keep, acc + stack[i], acc)
     return acc / torch.tensor(float(k_r - 2 * t), dtype=stack.dtype, device=stack.device)
+
+
+def _check_geomed(who: str, K: int, active: Sequence[bool], iters: int, nu: float):
+    act = [bool(a) for a in active]
+    if len(act) != K:
+        raise ValueError(f"{who}: {len(act)} mask entries for {K} clients")
+    if not any(act):
+        raise ValueError(f"{who}: needs at least one sampled client")
+    if not 1 <= int(iters) <= GEOMED_MAX_ITERS:
+        raise ValueError(f"{who}: iters must be in [1, {GEOMED_MAX_ITERS}], got {iters!r}")
+    nu32 = np.float32(nu)   # the kernels' smoothing constant is (float)geomed_nu
+    if not (np.isfinite(nu32) and nu32 > 0):
+        raise ValueError(f"{who}: nu must be finite and > 0 in fp32, got {nu!r}")
+    return act, nu32
+
+
+def geomed_torch(stack: torch.Tensor, active: Sequence[bool], iters: int, nu: float,
+                 trace: Optional[list] = None) -> torch.Tensor:
+    """The smoothed-Weiszfeld geometric median (Pillutla et al. 2022, RFA) of the rows of ``stack`` [K, P]
+    whose ``active`` entry is true, in ``stack``'s dtype (float32: what the torch engines run; float64:
+    the oracle): from the coordinate-wise median, ``iters`` times ``d_i = sum (v_i - z)^2`` in torch's own
+    summation order, the clients with ``d_i < +inf`` combined with weights ``1 / max(nu, sqrt(d_i))``
+    (added in client order, divided once by their sum); nobody at a finite distance: ``z`` stays.
+    ``trace``: a list that receives each iteration's included clients."""
+    if stack.dim() != 2 or stack.dtype not in (torch.float32, torch.float64):
+        raise ValueError("geomed_torch: needs a [K, P] float32 or float64 tensor")
+    act, nu32 = _check_geomed("geomed_torch", int(stack.shape[0]), active, iters, nu)
+    S = [i for i, a in enumerate(act) if a]
+    z = robust_aggregate_torch(stack, act, "median", 0.0)
+    floor = torch.tensor(float(nu32), dtype=stack.dtype, device=stack.device)
+    for _ in range(int(iters)):
+        d = ((stack[S] - z[None]) ** 2).sum(1)
+        incl = [i for i, ok in zip(S, (d < math.inf).tolist()) if ok]
+        if trace is not None:
+            trace.append(incl)
+        if not incl:
+            continue   # (z stays, and so does every later iteration's distance)
+        b = 1.0 / torch.maximum(floor, torch.sqrt(d))
+        acc = torch.zeros_like(z)
+        tot = torch.zeros((), dtype=stack.dtype, device=stack.device)
+        for j, i in enumerate(S):
+            if i in incl:   # selected, never multiplied by 0: an excluded row may hold NaN
+                acc = acc + b[j] * stack[i]
+                tot = tot + b[j]
+        z = acc / tot
+    return z
+
+
+def geomed_block_sums(sq: np.ndarray) -> np.ndarray:
+    """The distance sums of ``fl_geomed_kernel`` for the per-position terms ``sq`` [K, n] (fp32, ``+0`` where
+    the position is image padding): blocks of 256 consecutive positions (the last one filled with ``+0``),
+    each added by the xor tree (offsets 32, 16, ... 1) over its four runs of 64 and the four sums in order
+    from ``+0``; the block sums folded in block order from ``+0``.  One rounding per addition."""
+    sq = np.ascontiguousarray(sq, np.float32)
+    K, n = sq.shape
+    nb = (n + GEOMED_BLOCK - 1) // GEOMED_BLOCK
+    pad = np.zeros((K, nb * GEOMED_BLOCK), np.float32)
+    pad[:, :n] = sq
+    lanes = pad.reshape(K, nb, GEOMED_BLOCK // 64, 64)
+    idx = np.arange(64)
+    with np.errstate(all="ignore"):
+        off = 32
+        while off:
+            lanes = lanes + lanes[..., idx ^ off]
+            off >>= 1
+        blk = np.zeros((K, nb), np.float32)
+        for w in range(GEOMED_BLOCK // 64):
+            blk = blk + lanes[:, :, w, 0]
+        d = np.zeros(K, np.float32)
+        for w in range(nb):
+            d = d + blk[:, w]
+    return d
+
+
+def geomed_model(stack, active: Sequence[bool], real, iters: int, nu: float, trace: Optional[list] = None,
+                 records: Optional[list] = None) -> np.ndarray:
+    """What the ``fl_geomed`` launches write for the parameter images ``stack`` [K, Pimg] (fp32), bit for
+    bit: the image of the geometric median of the ``active`` clients, padding (``real`` [Pimg] false)
+    exact 0.  The rule is :func:`geomed_torch`'s with every operation one fp32 rounding, the median by
+    ``robust_aggregate_torch`` and the distances added in the kernel's order (:func:`geomed_block_sums`;
+    padding adds ``+0`` whatever it holds).  ``trace`` receives each iteration's included clients,
+    ``records`` each iteration's scratch record as the kernel leaves it: ``d`` [K] the distances it measured
+    (``+inf`` for a sum that is not ``< +inf``, 0 for a client that is not active), ``b`` [K] and ``mask`` the
+    weights and clients it combined (an iteration with nobody included repeats the last combine: its
+    record carries that one's; ``mask`` 0: the median was kept)."""
+    a = np.ascontiguousarray(np.asarray(stack, np.float32))
+    real = np.asarray(real, bool).reshape(-1)
+    K, n = a.shape
+    if real.shape[0] != n:
+        raise ValueError("geomed_model: needs [K, Pimg] images and Pimg flags")
+    act, nu32 = _check_geomed("geomed_model", K, active, iters, nu)
+    S = [i for i in range(K) if act[i]]
+    z = robust_aggregate_torch(torch.from_numpy(a), act, "median", 0.0).numpy()
+    eff_b, eff_mask = np.zeros(K, np.float32), 0
+    inf = np.float32(np.inf)
+    with np.errstate(all="ignore"):
+        for _ in range(int(iters)):
+            df = a[S] - z[None]
+            dS = geomed_block_sums(np.where(real[None], df * df, np.float32(0.0)))
+            d = np.zeros(K, np.float32)
+            d[S] = np.where(dS < inf, dS, inf)
+            incl = [i for i in S if d[i] < inf]
+            if trace is not None:
+                trace.append(incl)
+            if incl:
+                eff_b = np.zeros(K, np.float32)
+                eff_b[incl] = np.float32(1.0) / np.maximum(nu32, np.sqrt(d[incl]))
+                eff_mask = mask_bits([i in incl for i in range(K)])
+                acc = np.zeros(n, np.float32)
+                tot = np.float32(0.0)
+                for i in incl:
+                    acc = acc + eff_b[i] * a[i]
+                    tot = np.float32(tot + eff_b[i])
+                z = acc / tot
+            if records is not None:
+                records.append({"d": d, "b": eff_b.copy(), "mask": eff_mask})
+    return np.where(real, z, np.float32(0.0)).astype(np.float32)
 
 
 def _key32(x: np.ndarray) -> np.ndarray:

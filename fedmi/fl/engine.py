@@ -30,8 +30,8 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
-from .aggregate import (AGGREGATORS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch, mask_bits, pair_distances_torch,
-                        robust_aggregate_torch, screen_select)
+from .aggregate import (AGGREGATORS, ALL_AGGREGATORS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch,
+                        geomed_torch, mask_bits, pair_distances_torch, robust_aggregate_torch, screen_select)
 from .compress import COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
@@ -145,8 +145,16 @@ class EngineConfig:
     # the early-stop rule are unchanged; a server optimizer steps from the robust aggregate; rounds are
     # classic.  Not with dp_clip > 0 (the noise calibration assumes a weighted sum), trial batches or
     # WideClient; at most 64 clients.
+    # "geomed" = the geometric median of the sampled clients' unweighted local models (Pillutla et al.
+    # 2022, RFA): a whole-vector rule that needs no Byzantine count, breakdown point 1/2, every client
+    # pulling with at most unit force.  geomed_iters smoothed Weiszfeld iterations from the coordinate-wise
+    # median, weights 1 / max(geomed_nu, distance); geomed_iters + 1 launches per round (fl_geomed.hip).
+    # Composes as the median does; on a multi-rank HipRoundEngine over the host gather only
+    # (gather_plane="xgmi" is refused: the one-shot select kernel cannot iterate).
     aggregator: str = "mean"
     trim_ratio: float = 0.1
+    geomed_iters: int = 3
+    geomed_nu: float = 1e-6
     # Update compression with error feedback (fedmi/fl/compress.py): every sampled client compresses
     # u = (local - x) + e (x: the image the round trained from, e: its residual) before the exchange and
     # contributes w (x + C(u)); what C drops stays in e (error_feedback=False: it is discarded).  "topk"
@@ -267,20 +275,34 @@ def server_opt_id(cfg: EngineConfig) -> int:
     return kind
 
 
-def aggregator_id(cfg: EngineConfig) -> int:
-    """Validate the aggregation fields; the rule's index in ``AGGREGATORS`` (0 = the weighted mean)."""
-    if cfg.aggregator not in AGGREGATORS:
-        raise ValueError(f"aggregator must be one of {AGGREGATORS}, got {cfg.aggregator!r}")
+def aggregator_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
+    """Validate the aggregation fields; the rule's index in ``ALL_AGGREGATORS`` (0 = the weighted mean).
+    ``world``: the federation's size when the caller knows it -- the aggregate of one client is the
+    identity, so no combination is refused there."""
+    if not isinstance(cfg.aggregator, str) or cfg.aggregator not in ALL_AGGREGATORS:
+        raise ValueError(f"aggregator must be one of {ALL_AGGREGATORS}, got {cfg.aggregator!r}")
+    T = cfg.geomed_iters
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 1 <= int(T) <= GEOMED_MAX_ITERS:
+        raise ValueError(f"geomed_iters must be an integer in [1, {GEOMED_MAX_ITERS}], got {T!r}")
+    try:
+        nu = float(np.float32(cfg.geomed_nu)) if not isinstance(cfg.geomed_nu, bool) else math.nan
+    except (TypeError, ValueError):
+        nu = math.nan
+    if not (math.isfinite(nu) and nu > 0.0):
+        raise ValueError(f"geomed_nu must be a finite number > 0 (in fp32), got {cfg.geomed_nu!r}")
     try:
         beta = float(cfg.trim_ratio)
     except (TypeError, ValueError):
         beta = math.nan
     if not (math.isfinite(beta) and 0.0 <= beta < 0.5):
         raise ValueError(f"trim_ratio must be a finite number in [0, 0.5), got {cfg.trim_ratio!r}")
-    kind = AGGREGATORS.index(cfg.aggregator)
+    kind = ALL_AGGREGATORS.index(cfg.aggregator)
     if kind and float(cfg.dp_clip) > 0.0:
         raise ValueError(f"aggregator={cfg.aggregator!r} does not combine with differential privacy (dp_clip > 0): "
                          "the noise calibration assumes a weighted sum")
+    if cfg.aggregator == "geomed" and cfg.gather_plane == "xgmi" and (world is None or int(world) > 1):
+        raise ValueError("aggregator='geomed' does not run on gather_plane='xgmi': the one-shot select kernel "
+                         "cannot iterate; use gather_plane='host'")
     return kind
 
 
@@ -446,8 +468,8 @@ class RoundEngineBase:
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
-        # index in AGGREGATORS, 0 = the weighted mean; the aggregate of one client is the identity
-        kind = aggregator_id(cfg)
+        # index in ALL_AGGREGATORS, 0 = the weighted mean; the aggregate of one client is the identity
+        kind = aggregator_id(cfg, self.world)
         self.robust = kind if self.world > 1 else 0
         if self.robust and self.world > MAX_ROBUST_CLIENTS:
             raise ValueError(f"aggregator={cfg.aggregator!r} takes at most {MAX_ROBUST_CLIENTS} clients "
@@ -1079,7 +1101,10 @@ class TorchRoundEngine(RoundEngineBase):
             active = screen_select(pair_distances_torch(stack, active), active, int(self.cfg.screen_byzantine),
                                    self.cfg.screen_keep)
             self.hist.screen[self.rounds_issued] = mask_bits(active)
-        out[:self.P] = robust_aggregate_torch(stack, active, AGGREGATORS[self.robust], self.robust_beta)
+        if ALL_AGGREGATORS[self.robust] == "geomed":
+            out[:self.P] = geomed_torch(stack, active, int(self.cfg.geomed_iters), float(self.cfg.geomed_nu))
+        else:
+            out[:self.P] = robust_aggregate_torch(stack, active, AGGREGATORS[self.robust], self.robust_beta)
         return out
 
     def step_aggregate(self) -> None:
@@ -1460,6 +1485,9 @@ class HipRoundEngine(RoundEngineBase):
         # mean of the kept clients
         self.layout["aggregator"] = cfg.aggregator if self.robust else AGGREGATORS[0]
         self.layout["screen"] = SCREENS[self.screen]
+        if ALL_AGGREGATORS[self.robust] == "geomed":
+            self.layout["geomed"] = {"iters": int(cfg.geomed_iters), "nu": float(np.float32(cfg.geomed_nu)),
+                                     "launches": int(cfg.geomed_iters) + 1}
         if self.secagg:
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
         self.slab_f16 = bool(self.layout["slab_f16"])

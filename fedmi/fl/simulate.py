@@ -19,7 +19,9 @@ client's tail (C:165-192).
 
 With a robust aggregator (``EngineConfig.aggregator``) the in-process sum is replaced by the
 coordinate-wise median / trimmed mean of the sampled clients' buffers: one ``fl_robust`` launch,
-in place over the k buffers, on the device; ``robust_aggregate_torch`` on the CPU.
+in place over the k buffers, on the device; ``robust_aggregate_torch`` on the CPU.  ``"geomed"``
+takes the same place with its ``geomed_iters + 1`` launches (``fl_geomed.hip``); ``geomed_torch`` on
+the CPU.
 
 With a client screen (``EngineConfig.screen``, multi-Krum) two more launches run in front of that one
 -- the pairwise distances of the sampled clients' images and the selection of the kept clients

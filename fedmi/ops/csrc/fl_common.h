@@ -392,6 +392,33 @@ struct FLScreen {
     const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
 };
 
+// Geometric-median aggregation (fl_geomed.hip; Pillutla et al. 2022, RFA): parameters of the per-round
+// smoothed-Weiszfeld launches, passed to those kernels alone.  From the coordinate-wise median of the
+// round's sampled clients (rtab mask), T times: squared whole-model distances d_i to the estimate,
+// weights 1 / max(nu, sqrt(d_i)) over the clients with d_i < +inf, the weighted combine.
+#define FL_GEOMED_MAX_K 64           // width of the rtab mask
+#define FL_GEOMED_MAX_ITERS 32
+#define FL_GEOMED_THREADS 256        // floats of the image per workgroup: part of d_i's summation order
+// one iteration's record in the caller's scratch, floats: [0, 64) the weights b_i the iteration combined
+// with, [64, 128) the distances d_i it measured, [128, 130) the mask of the clients it combined (two
+// 32-bit halves; 0: it kept the coordinate-wise median)
+#define FL_GEOMED_SLOT 192
+struct FLGeomed {
+    int K;               // sources, 1 .. FL_GEOMED_MAX_K (source k is client k)
+    int max_rounds;      // rounds of rtab; rounds past it are not live
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+    int T;               // Weiszfeld iterations, 1 .. FL_GEOMED_MAX_ITERS
+    float nu;            // smoothing: lower bound of a distance in a weight, > 0
+};
+__host__ __device__ constexpr int fl_geomed_blocks(int Pimg) {
+    return (Pimg + FL_GEOMED_THREADS - 1) / FL_GEOMED_THREADS;
+}
+// floats of scratch the launches need: two sets of per-workgroup distance partials (64 per workgroup),
+// then T iteration records
+__host__ __device__ constexpr long long fl_geomed_scratch_floats(int Pimg, int T) {
+    return 2ll * fl_geomed_blocks(Pimg) * FL_GEOMED_MAX_K + (long long)T * FL_GEOMED_SLOT;
+}
+
 // Secure aggregation (fl_secagg.hip; Bonawitz et al. 2017, the arithmetic only): parameters of the
 // per-round mask and open launches, passed to those kernels alone.  A sampled client's contribution c
 // becomes q = clamp(rint(c 2^bits), -L, L), L = (2^31 - 1) / K_r, plus / minus the pair masks
@@ -538,6 +565,15 @@ hipError_t fl_launch_screen_dist(const MLPDesc& d, const FLScreen& p, const floa
                                  const FLState* st, hipStream_t s, int tile = 0);
 hipError_t fl_launch_screen_select(const FLScreen& p, const float* dist, unsigned long long* keep,
                                    unsigned long long* hist, const FLState* st, hipStream_t s);
+// (fl_geomed.hip) geometric-median aggregate of the round whose state is `st`: the T + 1 launches of the
+// smoothed Weiszfeld iteration over the K buffers of Pimg + tails_len floats named by `src`, the result
+// into the n_dst buffers named by `dst` (they may be the sources).  `scratch`: fl_geomed_scratch_floats
+// caller-owned floats; iteration t's record (FL_GEOMED_SLOT) lies at 2 * blocks * 64 + t * FL_GEOMED_SLOT.
+// A round that is not live is the whole-buffer left fold and writes no scratch.  `keep` as fl_launch_robust's.
+// No per-round host argument: the sequence is replayable.
+hipError_t fl_launch_geomed(const MLPDesc& d, const FLGeomed& p, const float* const* src, float* const* dst, int n_dst,
+                            const FLState* st, int tails_len, float* scratch, hipStream_t s,
+                            const unsigned long long* keep = nullptr);
 // (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
 // place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
 // first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);

@@ -1409,6 +1409,35 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
                                as_ptr<const unsigned long long>(keep)));
 }
 
+// Geometric-median aggregate (fl_geomed.hip) across engines' buffers, as robust_aggregate is: the iters + 1
+// launches of the smoothed Weiszfeld iteration.  `scratch`: geomed_scratch_floats(dims, iters) caller-owned
+// floats (distance partials, then one GEOMED_SLOT record per iteration: weights, distances, combined mask).
+static void geomed_aggregate(std::vector<int> dims, int iters, double nu, uintptr_t src, int K, uintptr_t dst, int n_dst,
+                             uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds, uintptr_t scratch,
+                             uintptr_t stream, uintptr_t keep) {
+    const MLPDesc d = desc_of(dims, "geomed_aggregate");
+    if (K < 1 || K > FL_GEOMED_MAX_K)
+        throw std::runtime_error("geomed_aggregate: 1.." + std::to_string(FL_GEOMED_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (iters < 1 || iters > FL_GEOMED_MAX_ITERS)
+        throw std::runtime_error("geomed_aggregate: iters must be in 1.." + std::to_string(FL_GEOMED_MAX_ITERS));
+    const float nuf = (float)nu;
+    if (!(nuf > 0.f) || !std::isfinite(nuf)) throw std::runtime_error("geomed_aggregate: nu must be finite and > 0 in fp32");
+    if (n_dst < 1 || n_dst > FL_GEOMED_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !dst || !state || !rtab ||
+        !scratch)
+        throw std::runtime_error("geomed_aggregate: bad arguments");
+    FLGeomed p;
+    std::memset(&p, 0, sizeof(p));
+    p.K = K;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    p.T = iters;
+    p.nu = nuf;
+    HIP_CHECK(fl_launch_geomed(d, p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
+                               as_ptr<const FLState>(state), tails_len, as_ptr<float>(scratch), as_stream(stream),
+                               as_ptr<const unsigned long long>(keep)));
+}
+
 // Multi-Krum screening (fl_screen.hip) across engines' buffers, as robust_aggregate is.  `src`: device table
 // of K buffer addresses (int64); `dist`: K x K floats; `keep`: one uint64; `hist`: max_rounds uint64, all
 // caller-owned; `f` / `m`: Byzantine clients assumed and clients kept (0: K_r - f).
@@ -1614,6 +1643,15 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
           py::arg("max_rounds"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);
+    m.def("geomed_aggregate", &geomed_aggregate, py::arg("dims"), py::arg("iters"), py::arg("nu"), py::arg("src"),
+          py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
+          py::arg("max_rounds"), py::arg("scratch"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);
+    m.def("geomed_scratch_floats", [](const std::vector<int>& dims, int iters) {
+        return fl_geomed_scratch_floats(desc_of(dims, "geomed_scratch_floats").Pimg, iters);
+    });
+    m.attr("GEOMED_SLOT") = (int)FL_GEOMED_SLOT;
+    m.attr("GEOMED_THREADS") = (int)FL_GEOMED_THREADS;
+    m.attr("GEOMED_MAX_ITERS") = (int)FL_GEOMED_MAX_ITERS;
     m.def("screen_dist", &screen_dist, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("dist"), py::arg("state"),
           py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("tile") = 0);
     m.def("screen_select", &screen_select, py::arg("dist"), py::arg("K"), py::arg("f"), py::arg("m"), py::arg("keep"),
