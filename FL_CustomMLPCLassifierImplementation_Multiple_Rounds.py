@@ -34,6 +34,14 @@ from fedmi.runtime.fault import parse_fault
 
 
 
+def _index_list(text: str) -> tuple:
+    """--attack-clients: '1,4' -> (1, 4)."""
+    try:
+        return tuple(int(t) for t in text.split(",") if t.strip() != "")
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated client indices, got {text!r}")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", default=DEFAULT_DATASET)
@@ -88,6 +96,20 @@ def parse_args(argv=None):
                     help="--screen: Byzantine clients assumed, f (every round needs 2 f + 3 sampled clients)")
     ap.add_argument("--screen-keep", type=int, default=None,
                     help="--screen: clients kept per round, m (default: sampled clients - f; 1 = Krum)")
+    ap.add_argument("--attack", choices=["none", "sign_flip", "gauss", "alie", "ipm", "label_flip"], default="none",
+                    help="Byzantine attack model of the --attack-clients: sign_flip = own update reversed and scaled; "
+                         "gauss = own model plus Gaussian noise; alie = 'A Little Is Enough' (Baruch et al. 2019); "
+                         "ipm = inner-product manipulation (Xie et al. 2020); label_flip = train on the labels C - 1 - y.  "
+                         "Also with --clients K; on several ranks the launched kinds need a robust --aggregator or a "
+                         "--screen on --gather-plane host; not with --wide")
+    ap.add_argument("--attack-clients", type=_index_list, default=(),
+                    help="--attack: the Byzantine clients / ranks, comma-separated indices, e.g. 1,4")
+    ap.add_argument("--attack-scale", type=float, default=1.0,
+                    help="--attack: s of sign_flip, sigma of gauss, eps of ipm; > 0")
+    ap.add_argument("--attack-z", type=float, default=None,
+                    help="--attack alie: standard deviations below the honest mean (default: the paper's z for the "
+                         "federation's size and the number of --attack-clients)")
+    ap.add_argument("--attack-seed", type=int, default=0, help="--attack gauss: 64-bit Philox seed")
     ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk"], default="none",
                     help="compress every client's round update with error feedback: topk = the largest "
                          "--compress-ratio of its entries, sign = one bit per entry and a scale, qsgd = stochastic "
@@ -227,6 +249,11 @@ def _screen_fields(a) -> dict:
     return dict(screen=a.screen, screen_byzantine=a.screen_byzantine, screen_keep=a.screen_keep)
 
 
+def _attack_fields(a) -> dict:
+    return dict(attack=a.attack, attack_clients=tuple(a.attack_clients), attack_scale=a.attack_scale,
+                attack_z=a.attack_z, attack_seed=a.attack_seed)
+
+
 def _compress_fields(a) -> dict:
     return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback,
                 compress_levels=a.compress_levels, compress_seed=a.compress_seed)
@@ -282,7 +309,7 @@ def main_clients(a, comm):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
                        **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a),
-                       **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a))
+                       **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a), **_attack_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
@@ -339,6 +366,13 @@ def main(argv=None):
         screen_id(EngineConfig(**_dp_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a)))
     except ValueError as e:
         raise SystemExit(f"--screen / --screen-byzantine / --screen-keep: {e}")
+    if a.wide and a.attack != "none":
+        raise SystemExit("--attack is not supported with --wide")
+    try:
+        from fedmi.fl.attack import attack_id
+        attack_id(EngineConfig(**_attack_fields(a)), a.clients if a.clients else None)
+    except ValueError as e:
+        raise SystemExit(f"--attack / --attack-clients / --attack-scale / --attack-z / --attack-seed: {e}")
     if a.wide and a.compress != "none":
         raise SystemExit("--compress is not supported with --wide")
     try:
@@ -378,7 +412,8 @@ def main(argv=None):
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
                        debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
-                       **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a))
+                       **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a),
+                       **_attack_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,
                                    mode=a.mode, backend=a.engine, seed=a.seed, config=cfg,
                                    shard_mode=a.partition, alpha=a.alpha, presharded=a.synthetic,

@@ -63,6 +63,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from .attack import ATTACKS
+
 AGGREGATORS = ("mean", "median", "trimmed_mean")
 # rules that iterate over whole models (several launches, scratch of their own); ids follow AGGREGATORS'
 ITERATIVE_AGGREGATORS = ("geomed",)
@@ -98,8 +100,9 @@ def trim_count(kind: str, beta: float, k_r: int) -> int:
 
 
 class _AggLaunch:
-    """The Python-launched aggregation kernels (``robust_aggregate``, ``secagg_mask``, ``secagg_open``) of
-    one federation, over buffers that keep their addresses.  ``lead``: the engine whose dims, round
+    """The Python-launched aggregation kernels (``robust_aggregate``, ``secagg_mask``, ``secagg_open``) and the
+    attack stage in front of them (``attack_apply``, ``fedmi/fl/attack.py``) of one federation, over buffers
+    that keep their addresses.  ``lead``: the engine whose dims, round
     state, ``rtab`` and config every launch uses (identical on all clients); ``src[par]`` / ``dst[par]``:
     the source and destination buffers of a round of output parity ``par``; :meth:`mask` masks the
     destinations in place -- what a process publishes is where it receives the aggregate -- as clients
@@ -123,6 +126,13 @@ class _AggLaunch:
         if getattr(lead, "screen", 0):
             self._dist = torch.zeros(self._k * self._k, dtype=torch.float32, device=lead.device)
             self._keep = torch.zeros(2, dtype=torch.int64, device=lead.device)
+        self._wtab = None
+        if getattr(lead, "attack_stage", False):
+            # the attack stage's table of the k buffers' FedAvg weights per round (unweighted mode: none, all 1)
+            wtab = lead.attack_weights()
+            if wtab is not None:
+                self._wtab = torch.as_tensor(wtab, device=lead.device).contiguous()
+            self._bad = mask_bits(k in lead.attack_par["clients"] for k in range(self._k))   # a constant of the federation
 
     def _round(self, par: int):
         e = self._lead
@@ -149,6 +159,16 @@ class _AggLaunch:
         e.m.robust_aggregate(e.dims, e.robust, float(e.robust_beta), self._src[par].data_ptr(), self._k,
                              self._dst[par].data_ptr(), self._n, *self._round(par), self._k * e.tail_stride,
                              int(e.cfg.max_rounds), stream, *keep)
+
+    def attack(self, par: int, stream: int) -> None:
+        """The attack stage (fl_attack.hip): one launch rewrites the bad sampled clients' buffers among the
+        sources in place; ``x`` is the lead engine's round-input image, the other parity's buffer."""
+        e = self._lead
+        a = e.attack_par
+        e.m.attack_apply(e.dims, ATTACKS.index(a["kind"]), a["scale"], a["z"], int(e.cfg.attack_seed),
+                         self._src[par].data_ptr(), self._k, e.params[par ^ 1].data_ptr(),
+                         0 if self._wtab is None else self._wtab.data_ptr(), self._bad,
+                         *self._round(par), int(e.cfg.max_rounds), stream)
 
     def mask(self, par: int, stream: int) -> None:
         e = self._lead

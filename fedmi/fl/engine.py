@@ -32,6 +32,8 @@ from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, 
                           param_count)
 from .aggregate import (AGGREGATORS, ALL_AGGREGATORS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch,
                         geomed_torch, mask_bits, pair_distances_torch, robust_aggregate_torch, screen_select)
+from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
+                     attack_torch)
 from .compress import COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
@@ -215,11 +217,36 @@ class EngineConfig:
     screen: str = "none"
     screen_byzantine: int = 0
     screen_keep: Optional[int] = None
+    # Byzantine attack model (fedmi/fl/attack.py, the specification): the clients / ranks attack_clients are
+    # Byzantine and publish, every round they are sampled in, "sign_flip": their own update reversed and scaled
+    # by attack_scale; "gauss": their model plus attack_scale * N(0, I) (Philox words of (attack_seed, round,
+    # client)); "alie": the honest sampled clients' mean minus attack_z of their standard deviations in every
+    # coordinate (Baruch et al. 2019; attack_z None = the paper's z for world clients, computed once); "ipm":
+    # the round's input image minus attack_scale times the honest mean update (Xie et al. 2020).  One launch per
+    # round (fl_attack.hip) after the local steps and any DP / compression kernel, before the screen, the
+    # robust rule, the secure-aggregation mask and the sum -- where ClientGroup(tamper=...) is called.
+    # "label_flip": no launch; a Byzantine client trains on the labels C - 1 - y (ClientGroup and
+    # FederatedMLPLearning flip them when the shards are built).  "none": off (nothing of a round changes); one
+    # client: off.  The launched kinds need the individual contributions: ClientGroup (every rule), or a
+    # multi-rank engine on the host gather (a robust rule or a screen, gather_plane="host"); they make every
+    # client start from one common model, as server_opt does.  Not with more than 64 clients, trial batches
+    # (comm_buffers), fed_sweep or WideClient.  attack_seed is config, not state.
+    attack: str = "none"
+    attack_clients: Sequence[int] = ()
+    attack_scale: float = 1.0
+    attack_z: Optional[float] = None
+    attack_seed: int = 0
 
     def to_dict(self) -> dict:
         d = asdict(self)
         d["hidden"] = list(self.hidden)
         d["betas"] = list(self.betas)
+        if self.attack == "none":
+            # (off: a checkpoint's config record is what it was before the attack fields existed)
+            for k in ("attack", "attack_clients", "attack_scale", "attack_z", "attack_seed"):
+                del d[k]
+        else:
+            d["attack_clients"] = [int(k) for k in self.attack_clients]
         return d
 
 
@@ -332,6 +359,18 @@ def screen_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
         raise ValueError(f"screen={cfg.screen!r} does not run on gather_plane='xgmi': the one-shot select kernel "
                          "never holds the stack of client models the pairwise distances need; use gather_plane='host'")
     return kind
+
+
+def attack_stage(cfg: EngineConfig, world: Optional[int] = None) -> bool:
+    """Validate the attack fields (``attack_id``); True when the attack is a stage of the round (a launch over
+    the clients' contributions: every kind but ``"label_flip"``)."""
+    return ATTACKS[attack_id(cfg, world)] in DEVICE_ATTACKS
+
+
+def common_init(cfg: EngineConfig) -> bool:
+    """Every client starts from one model: a server optimizer and the attack stage both read the image a round
+    trained from, which must be the same on every replica from round 0 on."""
+    return cfg.server_opt != "none" or cfg.attack in DEVICE_ATTACKS
 
 
 GATHER_PLANES = ("host", "xgmi")
@@ -501,6 +540,27 @@ class RoundEngineBase:
         if self.secagg and self.world > MAX_SECAGG_CLIENTS:
             raise ValueError(f"secagg takes at most {MAX_SECAGG_CLIENTS} clients (the width of the sampled-client "
                              f"mask), got {self.world}")
+        # Byzantine attack model: index in ATTACKS, 0 = off; one client: off.  attack_stage: the attack is a
+        # stage over the clients' contributions (every kind but "label_flip", which poisons the shard instead)
+        self.attack = attack_id(cfg, self.world)
+        self.attack_stage = ATTACKS[self.attack] in DEVICE_ATTACKS
+        if self.attack:
+            if self.world > MAX_ATTACK_CLIENTS:
+                raise ValueError(f"attack={cfg.attack!r} takes at most {MAX_ATTACK_CLIENTS} clients "
+                                 f"(the width of the sampled-client mask), got {self.world}")
+            self.attack_par = attack_params(cfg, self.world)
+            self.attack_bad = attack_clients(cfg)
+        if self.attack_stage and not getattr(comm, "in_process", False):
+            # a rank of its own: the stage needs every client's contribution on this rank -- the host gather
+            if self.secagg:
+                raise ValueError(f"attack={cfg.attack!r} does not run with multi-rank secagg: a rank only ever holds "
+                                 "its peers' masked contributions; use ClientGroup")
+            if not self.robust:
+                raise ValueError(f"attack={cfg.attack!r} does not run on a multi-rank engine with the plain mean: the "
+                                 "weighted all-reduce never holds the individual contributions; use a robust rule, "
+                                 "a screen, or ClientGroup")
+        if self.attack_stage and client_sizes is not None:
+            self._client_sizes = [int(n) for n in client_sizes]
         self.n_local = int(len(X))
         if self.n_local == 0:
             raise ValueError("client shard is empty (reference SURVEY Q12 would deadlock)")
@@ -555,6 +615,25 @@ class RoundEngineBase:
         if len(part) == self.world:
             return float(self.n_local) / float(self.n_total)
         return float(self.n_local) / float(sum(int(self._client_sizes[k]) for k in part))
+
+    def attack_weights(self) -> Optional[np.ndarray]:
+        """The [max_rounds, world] fp32 table of every client's FedAvg weight in its buffer, as the clients'
+        per-round device tables hold them (0: not sampled), for the attack stage; None in unweighted (robust)
+        mode, where every weight is 1."""
+        if self.robust:
+            return None
+        sizes = getattr(self, "_client_sizes", None)
+        if sizes is None:
+            raise ValueError(f"attack={self.cfg.attack!r} under the weighted mean needs client_sizes (the contributions "
+                             "carry the weights n_j / N)")
+        mr = max(1, int(self.cfg.max_rounds))
+        tab = np.zeros((mr, self.world), np.float32)
+        for r in range(mr):
+            part = [int(k) for k in self.participants(r)]
+            denom = float(self.n_total) if len(part) == self.world else float(sum(int(sizes[k]) for k in part))
+            for k in part:
+                tab[r, k] = float(sizes[k]) / denom
+        return tab
 
     def _dp_sigma_table(self, client_sizes) -> np.ndarray:
         """Per-round noise std of ONE client's share, sigma_r = z * S * max_{j in P_r} w_j(r) / sqrt(K_r),
@@ -939,7 +1018,7 @@ class TorchRoundEngine(RoundEngineBase):
     def step_train(self) -> None:
         r = self.rounds_issued
         self._active = self.rank in self.participants(r)
-        if self.dp or self.compress:
+        if self.dp or self.compress or self.attack_stage:
             self._dp_input = self.model.flat.detach().cpu().clone()   # the image the round trains from
         if self._active:
             self._loss = self.train_one_epoch()
@@ -986,6 +1065,29 @@ class TorchRoundEngine(RoundEngineBase):
         buf[t0:t0 + self.n_classes ** 2] = torch.as_tensor(self._cm.reshape(-1), dtype=torch.float32)
         buf[t0 + self.n_classes ** 2] = self._loss
         return buf
+
+    def attack_rows(self, bufs: Sequence[torch.Tensor]) -> None:
+        """The attack stage over the clients' :meth:`fedavg_contribution` rows (rank order), in place, in the
+        rows' dtype (``attack_torch``), with the weights those rows carry: 1 in robust mode, the fp32 table
+        weight under secure aggregation, ``n_j / N`` under the mean and ``n_j`` under the mean with client
+        sampling (divided by the sampled total after the sum).  Nothing without a launched attack kind."""
+        if not self.attack_stage:
+            return
+        r = self.rounds_issued
+        part = [int(k) for k in self.participants(r)]
+        if self.robust:
+            w = None
+        elif self.secagg:
+            if getattr(self, "_attack_wtab", None) is None:
+                self._attack_wtab = self.attack_weights()
+            w = [float(v) for v in self._attack_wtab[r]]
+        elif float(self.cfg.participation) < 1.0:
+            w = [float(n) for n in self._client_sizes]
+        else:
+            w = [float(n) / float(self.n_total) for n in self._client_sizes]
+        par = self.attack_par
+        attack_torch(bufs, self._dp_input, [k in part for k in range(self.world)], self.attack_bad, par["kind"],
+                     par["scale"], par["z"], self.P, weights=w, seed=int(self.cfg.attack_seed), round=r)
 
     def _dp_clip_and_noise(self, r: int, local: torch.Tensor):
         """(x + c (local - x), this client's noise vector or None) of round r; records the pre-clip
@@ -1112,7 +1214,9 @@ class TorchRoundEngine(RoundEngineBase):
         buf = self.fedavg_contribution()
         if self.robust:
             # robust aggregators: every client's row is gathered, the rule applied on every rank alike
-            buf = self.robust_combine([torch.as_tensor(b) for b in self.comm.allgather(buf.numpy())])
+            rows = [torch.as_tensor(b) for b in self.comm.allgather(buf.numpy())]
+            self.attack_rows(rows)   # (Byzantine attack model: every rank rewrites its copy of the bad ranks' rows)
+            buf = self.robust_combine(rows)
         elif self.secagg:
             # secure aggregation: every client's MASKED row is gathered, the sum opened on every rank alike
             self.secagg_mask_(buf)
@@ -1313,6 +1417,12 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"trial packing (comm_buffers) does not run a robust aggregator (aggregator={cfg.aggregator!r})")
         if bool(cfg.secagg) and comm_buffers is not None:
             raise ValueError("trial packing (comm_buffers) does not run secure aggregation (secagg)")
+        world = comm.size if comm is not None else 1
+        if attack_stage(cfg, world) and comm_buffers is not None:
+            raise ValueError(f"trial packing (comm_buffers) does not run an attack stage (attack={cfg.attack!r})")
+        if attack_stage(cfg, world) and cfg.gather_plane == "xgmi":
+            raise ValueError(f"attack={cfg.attack!r} does not run on gather_plane='xgmi': the one-shot select kernel never "
+                             "holds the stack of contributions the stage rewrites; use gather_plane='host'")
         # robust rule / secure aggregation over the one-shot xGMI peer kernel: one node's ranks at most
         from ..parallel.peer import PEER_MAX_WORLD
         xgmi_select = (bool(gather_plane_id(cfg)) and comm is not None and int(comm.size) > 1
@@ -1490,6 +1600,8 @@ class HipRoundEngine(RoundEngineBase):
                                      "launches": int(cfg.geomed_iters) + 1}
         if self.secagg:
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
+        if self.attack:
+            self.layout["attack"] = dict(self.attack_par)
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -1685,7 +1797,11 @@ class HipRoundEngine(RoundEngineBase):
             return
         stack, agg = self._gather_launch()
         self.comm.allgather_device(buf, out=stack)
-        agg.robust((r + 1) & 1, torch.cuda.current_stream(self.device).cuda_stream)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        if self.attack_stage:
+            # Byzantine attack model: every rank rewrites its copy of the bad ranks' rows, then screens / aggregates
+            agg.attack((r + 1) & 1, s)
+        agg.robust((r + 1) & 1, s)
 
     def _gather_launch(self):
         """The gathered stack of every rank's buffer and the launcher of the aggregation kernels over it
@@ -1693,7 +1809,10 @@ class HipRoundEngine(RoundEngineBase):
         if self._agg is None:
             # (a row is Pimg + tails floats, so rows past the first are float-aligned only when the tails are
             # no multiple of 4: the kernels' float4 loads of the rows rely on gfx950's global dwordx4 loads
-            # taking dword-aligned addresses, as fl_robust's always have)
+            # taking dword-aligned addresses, as fl_robust's always have; the attack stage's K <= 8 buckets
+            # also STORE float4s into the rows of the bad ranks -- global dwordx4 stores take dword-aligned
+            # addresses in the same way, and tests/test_attack.py's three ranks run that case: rows of
+            # Pimg + 30 floats)
             stack = torch.empty((self.world, self.params[0].numel()), dtype=torch.float32, device=self.device)
             rows = [stack[k] for k in range(self.world)]
             self._agg = (stack, _AggLaunch(self, [rows, rows], [[p] for p in self.params],

@@ -32,6 +32,11 @@ With secure aggregation (``EngineConfig.secagg``, ``fedmi/fl/secagg.py``) the k 
 quantised and pair-masked before they are summed: one ``fl_secagg_mask`` launch over the k buffers
 and one ``fl_secagg_open`` launch in place on the device, the host model on the CPU.  The ``wire``
 hook sees the buffers between the two -- what a peer would receive.
+
+With an attack model (``EngineConfig.attack``, ``fedmi/fl/attack.py``) the Byzantine clients' buffers are
+rewritten after the ``tamper`` hook and before all of the above: one ``fl_attack`` launch in place over the
+k buffers on the device, ``attack_torch`` on the CPU; ``"label_flip"`` flips the bad clients' shard labels
+instead.  The launched kinds make every client start from one common model.
 """
 from __future__ import annotations
 
@@ -45,7 +50,8 @@ import torch
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
 from .aggregate import _AggLaunch
-from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, gather_plane_id, heldout_metrics
+from .attack import attack_id, flip_labels
+from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, common_init, gather_plane_id, heldout_metrics
 
 
 class SimRank:
@@ -54,6 +60,7 @@ class SimRank:
 
     peer_allreduce = False
     native = None
+    in_process = True   # the group holds every client's contribution: the attack stage runs whatever the rule
 
     def __init__(self, size: int, rank: int, device):
         self.size, self.rank, self.device = int(size), int(rank), torch.device(device)
@@ -98,6 +105,8 @@ class ClientGroup:
             # one mask seed for the group (config only: no result depends on it)
             cfg = copy.deepcopy(cfg)
             cfg.secagg_seed = int.from_bytes(os.urandom(8), "little")
+        # Byzantine attack model: validated against the group's size; "label_flip" poisons the bad clients' shards
+        flipped = set(int(b) for b in cfg.attack_clients) if (attack_id(cfg, self.k) and cfg.attack == "label_flip") else ()
         self.clients: List = []
         for r in range(self.k):
             c = copy.deepcopy(cfg)
@@ -108,13 +117,14 @@ class ClientGroup:
                 c.gather_plane = "host"
             comm = SimRank(self.k, r, self.device)
             # FederatedMLPLearning's seeding: one init stream per (seed, rank)
-            # (server optimizer: one common starting model, see FederatedMLPLearning)
-            flat0 = init_flat(dims, seed * 1000003 + (r if cfg.server_opt == "none" else 0))
+            # (server optimizer, attack stage: one common starting model, see FederatedMLPLearning)
+            flat0 = init_flat(dims, seed * 1000003 + (0 if common_init(cfg) else r))
+            y_r = flip_labels(y[idx[r]], n_classes) if r in flipped else y[idx[r]]
             if backend == "hip":
-                e = HipRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total,
+                e = HipRoundEngine(X[idx[r]], y_r, n_classes, c, comm, flat0, n_total=n_total,
                                    device=self.device, client_sizes=[len(i) for i in idx])
             elif backend == "torch":
-                e = TorchRoundEngine(X[idx[r]], y[idx[r]], n_classes, c, comm, flat0, n_total=n_total,
+                e = TorchRoundEngine(X[idx[r]], y_r, n_classes, c, comm, flat0, n_total=n_total,
                                      client_sizes=[len(i) for i in idx])
             else:
                 raise ValueError(f"unknown backend {backend!r}")
@@ -131,7 +141,7 @@ class ClientGroup:
                     e.hist.screen = lead.hist.screen
         if backend == "hip":
             lead = self.clients[0]
-            if lead.robust or lead.secagg:   # in place over the k clients' buffers, client r = buffer r
+            if lead.robust or lead.secagg or lead.attack_stage:   # in place over the k clients' buffers, client r = buffer r
                 bufs = [[e.params[q] for e in self.clients] for q in (0, 1)]
                 self._agg = _AggLaunch(lead, bufs, bufs, clamps=[e.sa_clamp for e in self.clients] if lead.secagg else ())
             self.stream = torch.cuda.Stream(device=self.device)
@@ -154,6 +164,9 @@ class ClientGroup:
         if self.tamper is not None:
             with torch.cuda.stream(self.stream):
                 self.tamper(r, bufs)
+        if lead.attack_stage:
+            # Byzantine attack model: one launch rewrites the bad sampled clients' buffers in place
+            self._agg.attack(par, s)
         if lead.robust:
             # one launch, in place: every client's buffer is a source and a destination; the round's
             # live flag, index and sampled mask are the lead client's (identical on all)
@@ -190,6 +203,7 @@ class ClientGroup:
         bufs = [e.fedavg_contribution() for e in self.clients]
         if self.tamper is not None:
             self.tamper(self.rounds, bufs)
+        self.clients[0].attack_rows(bufs)   # Byzantine attack model (nothing when off)
         if self.clients[0].robust:
             tot = self.clients[0].robust_combine(bufs)
         elif self.clients[0].secagg:

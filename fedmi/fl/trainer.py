@@ -27,7 +27,8 @@ import torch
 from ..data.sharding import split_data
 from ..models.mlp import dict_to_flat, flat_to_dict, init_flat
 from ..obs.console import print_history
-from .engine import EngineConfig, make_engine
+from .attack import attack_id, flip_labels
+from .engine import EngineConfig, common_init, make_engine
 from .metrics import METRIC_NAMES, metrics_from_confusion
 
 
@@ -61,8 +62,12 @@ class FederatedMLPLearning:
         # reference: unseeded torch init per rank -> seeded per rank (different models
         # until the first FedAvg, like the reference)
         # (a server optimizer steps from the image a round trained from, which must be the same on
-        # every rank from round 0 on: all clients then start from rank 0's model)
-        flat0 = init_flat(dims, seed * 1000003 + (rank if cfg.server_opt == "none" else 0))
+        # every rank from round 0 on: all clients then start from rank 0's model; the attack stage reads that
+        # image too, fedmi/fl/attack.py)
+        flat0 = init_flat(dims, seed * 1000003 + (0 if common_init(cfg) else rank))
+        if attack_id(cfg, size) and cfg.attack == "label_flip" and int(rank) in [int(k) for k in cfg.attack_clients]:
+            # a Byzantine rank of the label-flip attack trains on the labels C - 1 - y
+            self.y_local = flip_labels(self.y_local, self.output_size)
         self.engine = make_engine(self.X_local, self.y_local, self.output_size, cfg, comm, flat0,
                                   n_total=n_total, backend=backend)
         self.device = getattr(self.engine, "device", torch.device("cpu"))

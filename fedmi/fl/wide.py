@@ -43,7 +43,12 @@ class WideClient:
                  step_size: int = 30, gamma: float = 0.5, seed: int = 0, dtype: str = "bf16",
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
                  fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
-                 compress: str = "none", secagg: bool = False, screen: str = "none"):
+                 compress: str = "none", secagg: bool = False, screen: str = "none", attack: str = "none"):
+        if attack != "none":
+            # the wide path all-reduces its buckets: nothing holds the individual contributions, and its
+            # caller hands it the shard as it is, so nothing flips a bad client's labels either
+            raise ValueError(f"WideClient does not run an attack model (attack={attack!r}); "
+                             "use the round engines (EngineConfig.attack)")
         if screen != "none":
             # the wide path all-reduces its buckets; nothing gathers the clients' models
             raise ValueError(f"WideClient does not run client screening (screen={screen!r}); "

@@ -100,6 +100,10 @@ class FedTrialGroup:
         if getattr(base, "screen", "none") != "none":
             # the trials share one SUM all-reduce; pairwise distances and a selection per trial are not batched
             raise ValueError("fed_sweep does not run client-screening trials (screen)")
+        if getattr(base, "attack", "none") != "none":
+            # the trials share one SUM all-reduce: nothing holds the individual contributions a stage would
+            # rewrite, and the sweep shards its own data, so nothing here flips a bad client's labels either
+            raise ValueError(f"fed_sweep does not run attacked trials (attack={base.attack!r})")
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         rank = comm.rank if comm is not None else 0

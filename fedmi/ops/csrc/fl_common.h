@@ -439,6 +439,38 @@ struct FLSecAgg {
     const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
 };
 
+// Byzantine attack models (fl_attack.hip; fedmi/fl/attack.py is the specification): parameters of the
+// per-round launch that rewrites the contributions of the bad sampled clients in place, before the screen,
+// the robust rule, the secure-aggregation mask and the sum.  With S_r the round's sampled clients (rtab
+// mask), B_r = S_r & bad, H_r = S_r & ~bad, w_j client j's FedAvg weight (wtab row of the round; null: 1),
+// x the image the round trained from and m_j = div(c_j, w_j), every k in B_r gets c_k = mul(w_k, a_k) on
+// the real parameters:
+//   FL_ATTACK_SIGN_FLIP : a_k = sub(x, mul(scale, sub(m_k, x)))
+//   FL_ATTACK_GAUSS     : a_k = add(m_k, mul(scale, n_k)), n_k: dense parameter p takes lane p % 4 of the
+//                         Box-Muller pairs of Philox4x32-10 at counter (p / 4, round, k, FL_ATTACK_STREAM)
+//   FL_ATTACK_ALIE      : a_k = sub(mu, mul(z, sqrt(var))), mu / var the mean and the (|H_r| - 1)-normalised
+//                         variance of the m_j over H_r (var = 0 for |H_r| = 1)  (Baruch et al. 2019)
+//   FL_ATTACK_IPM       : a_k = sub(x, mul(scale, sub(mu, x)))                   (Xie et al. 2020)
+// The kinds' values are their indices in fedmi/fl/attack.py ATTACKS.
+#define FL_ATTACK_SIGN_FLIP 1
+#define FL_ATTACK_GAUSS 2
+#define FL_ATTACK_ALIE 3
+#define FL_ATTACK_IPM 4
+#define FL_ATTACK_MAX_K 64            // width of the rtab mask
+#define FL_ATTACK_STREAM 0x4B435441u  // distinct from the DP noise stream 0x46454450 (fl_dp.hip), FL_QSGD_STREAM,
+                                      // FL_RANDK_STREAM and FL_SECAGG_STREAM
+struct FLAttack {
+    int kind;                 // FL_ATTACK_*
+    int K;                    // buffers, 1 .. FL_ATTACK_MAX_K (buffer k is client k)
+    int max_rounds;           // rounds of rtab / wtab; rounds past it are not live
+    float scale;              // s of sign-flip, sigma of gauss, eps of ipm; finite, > 0
+    float z;                  // alie
+    uint32_t key0, key1;      // gauss: Philox key, the 64-bit attack seed, low and high word
+    unsigned long long bad;   // bit k: client k is Byzantine
+    const float* rtab;        // a client's per-round table (FLBuffers::rtab): the sampled mask
+    const float* wtab;        // [max_rounds][K] fp32 FedAvg weights of the clients' buffers; null: all 1
+};
+
 // Held-out scoring of the round's aggregated model (fl_heldout.hip): parameters of the per-round row and
 // fold launches, passed to those kernels alone, as FLDp is.  Every buffer is caller-owned.  A live
 // round r leaves hist_cm[r] = the C x C confusion counts of the round's output image on the n held-out
@@ -574,6 +606,13 @@ hipError_t fl_launch_screen_select(const FLScreen& p, const float* dist, unsigne
 hipError_t fl_launch_geomed(const MLPDesc& d, const FLGeomed& p, const float* const* src, float* const* dst, int n_dst,
                             const FLState* st, int tails_len, float* scratch, hipStream_t s,
                             const unsigned long long* keep = nullptr);
+// (fl_attack.hip) the Byzantine clients' contributions of the round whose state is `st`: one launch rewrites,
+// in place, the real parameters of the bad sampled ones among the K buffers named by the device table `bufs`
+// (image padding, metric tails, honest and unsampled clients' buffers are never written; a round that is not
+// live, one without a bad sampled client and, alie / ipm, one without an honest sampled client write
+// nothing).  `x`: the image the round trained from.  No per-round host argument: the launch is replayable.
+hipError_t fl_launch_attack(const MLPDesc& d, const FLAttack& p, float* const* bufs, const float* x,
+                            const FLState* st, hipStream_t s);
 // (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
 // place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
 // first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);

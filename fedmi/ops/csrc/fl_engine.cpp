@@ -1409,6 +1409,47 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
                                as_ptr<const unsigned long long>(keep)));
 }
 
+// Byzantine attack stage (fl_attack.hip) across engines' buffers, as robust_aggregate is: one launch rewrites, in
+// place, the contributions of the bad sampled clients among the K buffers of the device table `src` (int64
+// addresses).  `kind`: index in fedmi/fl/attack.py ATTACKS (1 sign_flip, 2 gauss, 3 alie, 4 ipm); `x`: the image
+// the round trained from; `wtab`: [max_rounds, K] fp32 FedAvg weights of the buffers, 0 = all 1; `bad_mask`: bit k
+// = client k is Byzantine.
+static void attack_apply(std::vector<int> dims, int kind, double scale, double z, unsigned long long seed, uintptr_t src,
+                         int K, uintptr_t x, uintptr_t wtab, unsigned long long bad_mask, uintptr_t state, uintptr_t rtab,
+                         int max_rounds, uintptr_t stream) {
+    const MLPDesc d = desc_of(dims, "attack_apply");
+    if (kind < FL_ATTACK_SIGN_FLIP || kind > FL_ATTACK_IPM)
+        throw std::runtime_error("attack_apply: kind must be 1 (sign_flip), 2 (gauss), 3 (alie) or 4 (ipm), got " +
+                                 std::to_string(kind));
+    if (K < 1 || K > FL_ATTACK_MAX_K)
+        throw std::runtime_error("attack_apply: K must be 1.." + std::to_string(FL_ATTACK_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    const float sf = (float)scale, zf = (float)z;
+    if (!(sf > 0.f) || !std::isfinite(sf)) throw std::runtime_error("attack_apply: scale must be finite and > 0 in fp32");
+    if (!std::isfinite(zf)) throw std::runtime_error("attack_apply: z must be finite in fp32");
+    if (K < 64 && (bad_mask >> K) != 0)
+        throw std::runtime_error("attack_apply: bad_mask names a client >= K = " + std::to_string(K));
+    if (max_rounds < 1) throw std::runtime_error("attack_apply: max_rounds must be >= 1");
+    if (!src) throw std::runtime_error("attack_apply: src (the table of buffer addresses) is null");
+    if (!x) throw std::runtime_error("attack_apply: x (the image the round trained from) is null");
+    if (!state) throw std::runtime_error("attack_apply: state is null");
+    if (!rtab) throw std::runtime_error("attack_apply: rtab is null");
+    FLAttack p;
+    std::memset(&p, 0, sizeof(p));
+    p.kind = kind;
+    p.K = K;
+    p.max_rounds = max_rounds;
+    p.scale = sf;
+    p.z = zf;
+    p.key0 = (uint32_t)seed;
+    p.key1 = (uint32_t)(seed >> 32);
+    p.bad = bad_mask;
+    p.rtab = as_ptr<const float>(rtab);
+    p.wtab = as_ptr<const float>(wtab);
+    HIP_CHECK(fl_launch_attack(d, p, as_ptr<float* const>(src), as_ptr<const float>(x), as_ptr<const FLState>(state),
+                               as_stream(stream)));
+}
+
 // Geometric-median aggregate (fl_geomed.hip) across engines' buffers, as robust_aggregate is: the iters + 1
 // launches of the smoothed Weiszfeld iteration.  `scratch`: geomed_scratch_floats(dims, iters) caller-owned
 // floats (distance partials, then one GEOMED_SLOT record per iteration: weights, distances, combined mask).
@@ -1643,6 +1684,11 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
           py::arg("max_rounds"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);
+    m.def("attack_apply", &attack_apply, py::arg("dims"), py::arg("kind"), py::arg("scale"), py::arg("z"), py::arg("seed"),
+          py::arg("src"), py::arg("K"), py::arg("x"), py::arg("wtab"), py::arg("bad_mask"), py::arg("state"),
+          py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+    m.attr("ATTACK_STREAM") = (unsigned)FL_ATTACK_STREAM;
+    m.attr("ATTACK_MAX_K") = (int)FL_ATTACK_MAX_K;
     m.def("geomed_aggregate", &geomed_aggregate, py::arg("dims"), py::arg("iters"), py::arg("nu"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
           py::arg("max_rounds"), py::arg("scratch"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);

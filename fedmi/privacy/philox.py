@@ -18,6 +18,11 @@ DP_STREAM = 0x46454450
 # fedmi/ops/csrc/fl_common.h): same counter layout, the words used as they come (param_words)
 QSGD_STREAM = 0x44475351
 RANDK_STREAM = 0x4B444E52
+# Stream of the Gaussian Byzantine client (fedmi/fl/attack.py; FL_ATTACK_STREAM of fl_common.h, "ATCK"): the DP
+# layout with the bad client's index in the rank word, Box-Muller normals like the DP noise.  Distinct from the
+# streams above and from the pair masks' (fedmi/fl/secagg.py SECAGG_STREAM = 0x47414353).
+ATTACK_STREAM = 0x4B435441
+assert len({DP_STREAM, QSGD_STREAM, RANDK_STREAM, ATTACK_STREAM, 0x47414353}) == 5
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9
