@@ -647,17 +647,21 @@ hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLCon
                                 const float* pg, const FLState* st_in, FLState* st_out, int local_step,
                                 hipStream_t s, bool stage_local = false, int mode = FL_EVAL_CLASSIC,
                                 float* cm_out = nullptr, int fold_mask = FL_FOLD_B, bool shape_spec = false,
-                                bool slab_blocked = false);
+                                bool slab_blocked = false, bool epi_exchange = false);
 // (fl_train_bf16_spec.hip: the train kernel specialised for the reference shape, fl_layout.h FlRefShape.
 // `shape_spec` above lets fl_launch_train_bf16 pick it where fl_train_bf16_spec_ok holds: descriptors
 // byte-equal to the compile-time ones, and a round kind that is instantiated)
 // `slab_blocked` (FLEngine's flag, the same value to fl_launch_adam): the fp16 slab row is the blocked
 // one of fl_layout.h (FlSlabBlk), which only the specialised train / Adam pair writes and reads; a
 // launch that would take another kernel fails instead, so a mixed pair never runs.
+// `epi_exchange` (FLEngine's flag): the specialised kernel's hidden-layer forward and dgrad epilogues are
+// the exchanged ones (fl_layout.h fl_epi_*: transposed tiles, 8-byte LDS stores; the same LDS bytes); the
+// generic kernels have no such form and ignore it.
 bool fl_train_bf16_spec_ok(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, int mode);
 hipError_t fl_launch_train_bf16_spec(const FLConfig& c, const FLBuffers& b, const float* pg, const FLState* st_in,
                                      FLState* st_out, int local_step, hipStream_t s, bool stage_local, int mode,
-                                     float* cm_out, int fold_mask, bool slab_blocked = false);
+                                     float* cm_out, int fold_mask, bool slab_blocked = false,
+                                     bool epi_exchange = false);
 hipError_t fl_set_lds_limit_bf16_spec(size_t bytes);
 hipError_t fl_launch_eval_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                const float* params, float* comm, const FLState* st, hipStream_t s);

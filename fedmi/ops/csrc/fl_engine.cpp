@@ -495,6 +495,14 @@ class FLEngine {
 #endif
             if (slab_blocked_) c_.slab_stride = stride;
         }
+        // Exchanged epilogues of the specialised bf16 train kernel (fl_layout.h fl_epi_*), reported as
+        // layout()["epi_exchange"]: on wherever that kernel runs.  FEDMI_EPI_EXCHANGE=0 keeps the generic
+        // epilogues under the same kernel (A/B, tests).  The launcher gets the flag with every launch.
+        {
+            const char* ee = std::getenv("FEDMI_EPI_EXCHANGE");
+            epi_exchange_ = !(ee != nullptr && ee[0] == '0') && dtype_ == 1 && shape_spec_on_ &&
+                            fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED);
+        }
     }
 
     ~FLEngine() {
@@ -921,6 +929,8 @@ class FLEngine {
         o["slab_f16"] = c_.slab_f16;
         // the slab rows are blocked rows (fl_layout.h FlSlabBlk; slab_map() gives each dense index's position)
         o["slab_blocked"] = slab_blocked_;
+        // the specialised bf16 train kernel runs its exchanged epilogues (fl_layout.h fl_epi_*)
+        o["epi_exchange"] = epi_exchange_;
         o["tail_off"] = c_.tail_off;
         o["tail_stride"] = c_.tail_stride;
         o["tail_len"] = c_.tail_len;
@@ -1022,7 +1032,7 @@ class FLEngine {
                                                               shape_spec_on_));
                 else
                     HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
-                                                   i[3], shape_spec_on_, slab_blocked_));
+                                                   i[3], shape_spec_on_, slab_blocked_, epi_exchange_));
                 break;
             case FLLaunchRec::ADAM: {
                 PeerArgs pa;
@@ -1121,6 +1131,7 @@ class FLEngine {
     bool shape_spec_on_ = true;  // FEDMI_SHAPE_SPEC != 0: launchers may pick shape-specialised kernels
     bool adam_spec_on_ = true;   // ... and FEDMI_ADAM_SPEC != 0: the Adam launcher too
     bool slab_blocked_ = false;  // the fp16 slab rows are blocked rows (fl_layout.h FlSlabBlk; see the constructor)
+    bool epi_exchange_ = false;  // the specialised bf16 train kernel's exchanged epilogues (see the constructor)
     // The engine allows the specialised Adam kernel: no peer plane, and the round's output is the
     // Adam kernel's own (no DP clip, no compression, no server step after it); the launcher checks the shape, the
     // client count, the lag region and the undo buffer per launch (fl_adam_spec_ok).

@@ -41,6 +41,12 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
+// two bf16 activations -> 0xffff per half that is a kept ReLU output (nonzero, sign bit clear: > 0 as int16)
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t relu_mask_pk(uint32_t a) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, a) > (s16x2){0, 0});
+}
+
 __device__ __forceinline__ bf16x8 ld128(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 
 // ds_read_b64_tr_b16: lane 4q+p of each 16-lane group passes &M[r0+q][c0+4p]; lane i of the
@@ -298,9 +304,47 @@ __device__ __forceinline__ void fwd_layer_bf16(const MLPDesc& d_, const MLPDescB
             }
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
+                if constexpr (SP::kEpiExchange) {
+                    // hidden layers: the operands exchange roles, the tile comes out transposed (fl_layout.h
+                    // fl_epi_*; every product keeps its k position in the same MFMA: the same accumulator
+                    // bits, as in wgrad_layer_bf16's blocked row and score_tile)
+                    if (!last) {
+                        acc[rt] = mfma32(bv, av[rt], acc[rt]);
+                        acl[rt] = mfma32(bv, al[rt], acl[rt]);
+                        acl[rt] = mfma32(bl, av[rt], acl[rt]);
+                        continue;
+                    }
+                }
                 acc[rt] = mfma32(av[rt], bv, acc[rt]);
                 acl[rt] = mfma32(al[rt], bv, acl[rt]);
                 acl[rt] = mfma32(av[rt], bl, acl[rt]);
+            }
+        }
+        if constexpr (SP::kEpiExchange) {
+            // a lane holds 4 consecutive columns of one row: one 16-byte bias read, two values per hardware
+            // conversion (v_cvt_pk_bf16_f32: the bits of bf16_bits / lo_bits for finite values, as in
+            // score_tile), one 8-byte store each to act_{l+1} and alo_{l+1} per row tile; no row stagger
+            static_assert(!PLAIN && NWV == FL_WAVES, "exchanged epilogue: the one-client split-bf16 kernel");
+            if (!last) {
+                const f32x4 bq = *reinterpret_cast<const f32x4*>(bias + fl_epi_fwd_col(nt, lane, 0));
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    float v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = fmaxf((acc[rt][j] + acl[rt][j]) + bq[j], 0.f);
+                    const int o = fl_epi_off(fl_epi_row(rt, lane), fl_epi_fwd_col(nt, lane, 0), e.lda[l + 1]);
+#ifdef FL_PROBE_EPI_SWCVT  // timing probes only: software rounding packed into the same stores
+                    const uint32_t h01 = pack_bf16x2(v[0], v[1]), h23 = pack_bf16x2(v[2], v[3]);
+                    const uint32_t l01 = pack_lo_bf16x2(v[0], v[1]), l23 = pack_lo_bf16x2(v[2], v[3]);
+#else
+                    const uint32_t h01 = cvt_pk_bf16(v[0], v[1]), h23 = cvt_pk_bf16(v[2], v[3]);
+                    const uint32_t l01 = cvt_pk_bf16(v[0] - __uint_as_float(h01 << 16), v[1] - __uint_as_float(h01 & 0xffff0000u));
+                    const uint32_t l23 = cvt_pk_bf16(v[2] - __uint_as_float(h23 << 16), v[3] - __uint_as_float(h23 & 0xffff0000u));
+#endif
+                    *reinterpret_cast<uint2*>(lds + e.act_off[l + 1] + o) = make_uint2(h01, h23);
+                    *reinterpret_cast<uint2*>(lds + e.alo_off[l + 1] + o) = make_uint2(l01, l23);
+                }
+                continue;
             }
         }
         const int n = nt * 16 + wc;
@@ -498,7 +542,27 @@ __device__ void dgrad_layer_bf16(const MLPDesc& d_, const MLPDescB& e_, int l, c
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) av[rt] = ld128(pa + rt * 16 * ldd * 2 + os * 64);
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) acc[rt] = mfma32(av[rt], bv, acc[rt]);
+            for (int rt = 0; rt < RT; ++rt) {
+                // exchanged operands: the tile comes out transposed, same accumulator bits (see fwd_layer_bf16)
+                if constexpr (SP::kEpiExchange) acc[rt] = mfma32(bv, av[rt], acc[rt]);
+                else acc[rt] = mfma32(av[rt], bv, acc[rt]);
+            }
+        }
+        if constexpr (SP::kEpiExchange) {
+            // a lane holds features it*16 + 4lg.. of one row (fl_layout.h fl_epi_*): one 8-byte read of the
+            // ReLU mask, two values per hardware conversion, one 8-byte store to D_l per row tile
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const int o = fl_epi_off(fl_epi_row(rt, lane), fl_epi_dgrad_col(it, lane, 0), lda);
+                const uint2 a = *reinterpret_cast<const uint2*>(lds + e.act_off[l] + o);
+#ifdef FL_PROBE_EPI_SWCVT  // timing probes only (see fwd_layer_bf16)
+                const uint32_t g01 = pack_bf16x2(acc[rt][0], acc[rt][1]), g23 = pack_bf16x2(acc[rt][2], acc[rt][3]);
+#else
+                const uint32_t g01 = cvt_pk_bf16(acc[rt][0], acc[rt][1]), g23 = cvt_pk_bf16(acc[rt][2], acc[rt][3]);
+#endif
+                *reinterpret_cast<uint2*>(lds + e.dlt_off[l] + o) = make_uint2(g01 & relu_mask_pk(a.x), g23 & relu_mask_pk(a.y));
+            }
+            continue;
         }
         const int i = it * 16 + lr;
         const bool odd = lg & 1;
@@ -1085,10 +1149,11 @@ fl_eval_fedavg_bf16_kernel(MLPDesc d, MLPDescB e, FLConfig c, FLBuffers b, const
 hipError_t fl_launch_train_bf16(const MLPDesc& d, const MLPDescB& e, const FLConfig& c, const FLBuffers& b,
                                 const float* pg, const FLState* si, FLState* so, int ls, hipStream_t s,
                                 bool stage_local, int mode, float* cm_out, int fold_mask, bool shape_spec,
-                                bool slab_blocked) {
+                                bool slab_blocked, bool epi_exchange) {
     if ((mode == FL_EVAL_FUSED || mode == FL_EVAL_LAGGED) && cm_out == nullptr) return hipErrorInvalidValue;
     if (shape_spec && fl_train_bf16_spec_ok(d, e, c, mode))
-        return fl_launch_train_bf16_spec(c, b, pg, si, so, ls, s, stage_local, mode, cm_out, fold_mask, slab_blocked);
+        return fl_launch_train_bf16_spec(c, b, pg, si, so, ls, s, stage_local, mode, cm_out, fold_mask, slab_blocked,
+                                         epi_exchange);
     if (slab_blocked) return hipErrorInvalidValue;  // only the specialised kernel writes the blocked slab row
     const size_t lds = (size_t)e.lds_bytes;
     const bool lag = mode == FL_EVAL_LAGGED;

@@ -277,6 +277,20 @@ struct FlRefSlabBlk {
     static_assert(fl_slab_blk_gapfree(FlRefShape<R>::d, s), "reference shape: the blocked slab row has no gaps");
 };
 
+// Exchanged epilogues of the specialised bf16 train kernel (SP::kEpiExchange; fl_kernels_bf16.hip
+// fwd_layer_bf16, dgrad_layer_bf16).  With the two MFMA operands exchanged a 16 x 16 tile comes out
+// transposed -- same products at the same k positions, same accumulator bits -- so accumulator j of lane
+// `lane` (lr = lane & 15, lg = lane >> 4) is one row's value at 4 consecutive columns instead of one
+// column's at 4 rows, and the lane's 4 bf16 results leave as one aligned 8-byte LDS store.  Row tile rt:
+// the lane's row.  Forward column tile nt: lane lr loads W row nt*16 + fl_fwd_col(lr), so accumulator
+// 4 lg + j is column nt*16 + fl_fwd_col(4 lg + j) = nt*16 + 4 ((lg + 1) & 3) + j.  dgrad item `it`: the
+// transposed W reads give lane lr feature it*16 + lr, accumulator 4 lg + j is feature it*16 + 4 lg + j.
+// fl_epi_off: byte offset of (row, col) in a bf16 buffer of row stride `lda` elements (act_l, alo_l, D_l).
+__host__ __device__ constexpr int fl_epi_row(int rt, int lane) { return rt * 16 + (lane & 15); }
+__host__ __device__ constexpr int fl_epi_fwd_col(int nt, int lane, int j) { return nt * 16 + 4 * (((lane >> 4) + 1) & 3) + j; }
+__host__ __device__ constexpr int fl_epi_dgrad_col(int it, int lane, int j) { return it * 16 + 4 * (lane >> 4) + j; }
+__host__ __device__ constexpr int fl_epi_off(int row, int col, int lda) { return (row * lda + col) * 2; }
+
 // Shape policies of the train kernels' device functions (template parameter SP): where a function
 // takes its descriptors from.  FlShapeDyn: the by-value kernel arguments, as passed.  FlShapeRef<R>:
 // the reference shape's constants -- the arguments are ignored, every stride, offset and trip count
@@ -288,17 +302,21 @@ struct FlRefSlabBlk {
 // constant-memory symbols the host may overwrite).
 // kSlabBlocked (FlShapeRef<R, true>, bf16 train kernel only): the fp16 slab row is the blocked one
 // above (FlRefSlabBlk<R>) instead of the dense row.
+// kEpiExchange (FlShapeRef<R, BLK, true>, bf16 train kernel only): the hidden layers' forward tiles and
+// the dgrad tiles come out transposed and leave as 8-byte LDS stores (fl_epi_* above).
 struct FlShapeDyn {
     static constexpr bool kStatic = false;
     static constexpr bool kSlabBlocked = false;
+    static constexpr bool kEpiExchange = false;
     static constexpr const MLPDesc* pd = nullptr;
     static constexpr const MLPDescB* pe = nullptr;
     static constexpr const FlSlabBlk* ps = nullptr;
 };
-template <int R, bool BLK = false>
+template <int R, bool BLK = false, bool EPI = false>
 struct FlShapeRef {
     static constexpr bool kStatic = true;
     static constexpr bool kSlabBlocked = BLK;
+    static constexpr bool kEpiExchange = EPI;
     static constexpr const FlSlabBlk* ps = &FlRefSlabBlk<R>::s;
     static constexpr const MLPDesc* pd = &FlRefShape<R>::d;
     static constexpr const MLPDescB* pe = &FlRefShape<R>::e;
