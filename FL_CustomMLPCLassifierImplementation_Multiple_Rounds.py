@@ -110,16 +110,19 @@ def parse_args(argv=None):
                     help="--attack alie: standard deviations below the honest mean (default: the paper's z for the "
                          "federation's size and the number of --attack-clients)")
     ap.add_argument("--attack-seed", type=int, default=0, help="--attack gauss: 64-bit Philox seed")
-    ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk"], default="none",
+    ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk", "powersgd"], default="none",
                     help="compress every client's round update with error feedback: topk = the largest "
                          "--compress-ratio of its entries, sign = one bit per entry and a scale, qsgd = stochastic "
-                         "quantisation to --compress-levels levels, randk = a random --compress-ratio of its entries "
+                         "quantisation to --compress-levels levels, randk = a random --compress-ratio of its entries, "
+                         "powersgd = rank --compress-rank factors of every weight matrix "
                          "(a simulated uplink: the exchange stays dense; --jsonl rows carry uplink_bytes)")
     ap.add_argument("--compress-ratio", type=float, default=0.1,
                     help="--compress topk / randk: fraction of entries kept, in (0, 1]")
     ap.add_argument("--compress-levels", type=int, default=127, help="--compress qsgd: quantisation levels s, in [1, 32767]")
     ap.add_argument("--compress-seed", type=int, default=None,
-                    help="--compress qsgd / randk: seed of the random stream (default: a private draw per client)")
+                    help="--compress qsgd / randk: seed of the random stream; powersgd: seed of the starting factors "
+                         "(default: a private draw per client)")
+    ap.add_argument("--compress-rank", type=int, default=4, help="--compress powersgd: rank r of the factors, in [1, 8]")
     ap.add_argument("--no-error-feedback", action="store_true",
                     help="--compress: discard what the compressor drops instead of carrying it to the next round")
     ap.add_argument("--secagg", action="store_true",
@@ -256,7 +259,7 @@ def _attack_fields(a) -> dict:
 
 def _compress_fields(a) -> dict:
     return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback,
-                compress_levels=a.compress_levels, compress_seed=a.compress_seed)
+                compress_levels=a.compress_levels, compress_seed=a.compress_seed, compress_rank=a.compress_rank)
 
 
 def _secagg_fields(a) -> dict:
@@ -379,7 +382,7 @@ def main(argv=None):
         from fedmi.fl.compress import compress_id
         compress_id(EngineConfig(**_dp_fields(a), **_compress_fields(a)))
     except ValueError as e:
-        raise SystemExit(f"--compress / --compress-ratio / --compress-levels / --compress-seed: {e}")
+        raise SystemExit(f"--compress / --compress-ratio / --compress-levels / --compress-seed / --compress-rank: {e}")
     if a.wide and a.secagg:
         raise SystemExit("--secagg is not supported with --wide")
     try:

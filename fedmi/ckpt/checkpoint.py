@@ -142,7 +142,9 @@ def save_checkpoint(path: str, trainer) -> None:
         "compress_stat": np.asarray(st["history"]["compress_stat"], np.float32),
         # the stochastic kinds: the client's seed (two 32-bit words, as dp_seed)
         **({} if "compress_seed" not in st else {"compress_seed": np.asarray(
-            [int(st["compress_seed"]) & 0xFFFFFFFF, int(st["compress_seed"]) >> 32], np.int64)})}
+            [int(st["compress_seed"]) & 0xFFFFFFFF, int(st["compress_seed"]) >> 32], np.int64)}),
+        # the low-rank kind: Q of the compressed layers
+        **({} if "compress_q" not in st else {"compress_q": np.asarray(st["compress_q"], np.float32)})}
     # secure aggregation: the config's three fields are all a resume needs (the mask seed is no state);
     # the client's own per-round clamp counts stay in its file, as its update norms do
     sa = {} if "secagg_clamped" not in st["history"] else {
@@ -241,6 +243,8 @@ def resume(path: str, trainer) -> int:
     if "compress_seed" in c:
         lo, hi = (int(x) for x in np.asarray(c["compress_seed"]).reshape(-1)[:2])
         st["compress_seed"] = lo | (hi << 32)
+    if "compress_q" in c:
+        st["compress_q"] = np.asarray(c["compress_q"], np.float32)
     if "secagg_clamped" in c:
         st["history"]["secagg_clamped"] = np.asarray(c["secagg_clamped"], np.int64)
     if "heldout_cm" in c:

@@ -38,8 +38,30 @@ The two random compressors draw, for dense parameter ``p`` of round ``r`` of cli
   ``c = u * (P / k)`` (the unbiased variant, ``E c = u``) and ``e' = 0``.  A gain together with a
   memory would count the dropped mass twice.
 
-An unsampled client and a round that is not live leave contribution and residual untouched.  Top-k and
-sign are deterministic: every replica and every graph replay is bit-identical.  The random compressors
+The low-rank compressor is the only one that uses the parameters' matrix structure
+(``fedmi/ops/csrc/fl_lowrank.hip``; PowerSGD, Vogels et al. 2019):
+
+* ``"powersgd"`` (``r = compress_rank``, 1 .. 8) works layer by layer.  Biases travel raw (``c = u``,
+  ``e' = 0``), and so does a weight matrix with ``r (N + K) >= N K`` (the factors would cost as much as the
+  matrix; a compressed layer therefore has ``r < min(N, K)``).  A compressed layer's block of ``u`` is the
+  row-major ``M [N][K]`` (N out, K in) and ``Q [K][r]`` its state; one warm-started power iteration:
+  ``P = M Q``; the columns of ``P`` orthonormalised by modified Gram-Schmidt in column order (column j:
+  for i < j in turn ``d = <P_i, P_j>``, ``P_j = P_j - d P_i``; then ``ss = <P_j, P_j>``, ``P_j = P_j /
+  sqrt(ss)``, one division per element, or the zero column where ``ss == 0``); ``Q' = M^T P``;
+  ``c = P Q'^T``; ``Q <- Q'``; ``e' = u - c``.  If one of the r values ``ss`` is not finite the whole
+  layer travels raw this round and keeps its ``Q``.  Order: the dot products of ``M Q`` (over k), ``M^T P``
+  (over n) and ``P Q'^T`` (over j) run in ascending contraction index from ``+0``, a product and a sum
+  per term; a Gram-Schmidt dot over N is summed as one 64-lane wave does, lane t adding the products of
+  entries t, t + 64, ... in turn from ``+0``, then the xor tree 32 .. 1 (:func:`wave_dot`).  The order
+  depends on the layer's shape and r alone.  ``Q_0``: ``numpy.random.default_rng(compress_seed)
+  .standard_normal((K, r))`` per compressed layer in layer order, cast to fp32 (``None``: a private
+  64-bit draw); there is no device RNG, and ``Q`` is state (``compress_q``).  The statistic is
+  ``sqrt(sum (u - c)^2) / sqrt(sum u^2)`` over all P entries, both sums in :func:`ordered_sum`'s order
+  (0 where ``u = 0`` or the client is not sampled).  A real uplink carries ``r (N + K)`` floats per
+  compressed layer and every raw entry; no indices.
+
+An unsampled client and a round that is not live leave contribution and residual (and powersgd's ``Q``)
+untouched.  Top-k, sign and powersgd are deterministic: every replica and every graph replay is bit-identical.  The random compressors
 are deterministic given ``(compress_seed, round, client)``: the round word comes from the device state,
 so a replayed graph draws fresh words each round, and a resumed run continues the stream.
 """
@@ -55,16 +77,20 @@ COMPRESSORS = ("none", "topk", "sign")
 # stochastic compressors: their output depends on (compress_seed, round, client)
 RANDOM_COMPRESSORS = ("qsgd", "randk")
 ALL_COMPRESSORS = COMPRESSORS + RANDOM_COMPRESSORS
+# low-rank factorisation: the compressor carries a state Q per compressed layer beside the residual
+LOWRANK_COMPRESSORS = ("powersgd",)
+COMPRESSOR_KINDS = ALL_COMPRESSORS + LOWRANK_COMPRESSORS   # compress_id's index: the kernels' FL_COMPRESS_*
 MAX_LEVELS = 32767
+MAX_RANK = 8
 # threads of the kernel's workgroup: the fixed summation order of `s` follows them
 _THREADS = 1024
 
 
 def compress_id(cfg) -> int:
     """Validate the compression fields of an ``EngineConfig``; the compressor's index in
-    ``ALL_COMPRESSORS`` (0 = off)."""
-    if cfg.compress not in ALL_COMPRESSORS:
-        raise ValueError(f"compress must be one of {ALL_COMPRESSORS}, got {cfg.compress!r}")
+    ``COMPRESSOR_KINDS`` (0 = off)."""
+    if cfg.compress not in COMPRESSOR_KINDS:
+        raise ValueError(f"compress must be one of {COMPRESSOR_KINDS}, got {cfg.compress!r}")
     try:
         ratio = float(cfg.compress_ratio)
     except (TypeError, ValueError):
@@ -80,7 +106,10 @@ def compress_id(cfg) -> int:
     if seed is not None and (isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer))
                              or not 0 <= int(seed) < 2 ** 64):
         raise ValueError(f"compress_seed must be None or an integer in [0, 2**64), got {seed!r}")
-    kind = ALL_COMPRESSORS.index(cfg.compress)
+    rank = getattr(cfg, "compress_rank", 4)
+    if isinstance(rank, (bool, np.bool_)) or not isinstance(rank, (int, np.integer)) or not 1 <= int(rank) <= MAX_RANK:
+        raise ValueError(f"compress_rank must be an integer in [1, {MAX_RANK}], got {rank!r}")
+    kind = COMPRESSOR_KINDS.index(cfg.compress)
     if kind and float(cfg.dp_clip) > 0.0:
         raise ValueError(f"compress={cfg.compress!r} does not combine with differential privacy (dp_clip > 0): "
                          "both rewrite the contribution, and the noise calibration assumes the clipped update")
@@ -92,8 +121,13 @@ def topk_count(ratio: float, P: int) -> int:
     return max(1, min(int(P), int(math.ceil(float(ratio) * int(P)))))
 
 
-def compress_k(cfg, P: int) -> int:
-    """Entries a config's compressor transmits of P parameters (sign, qsgd and dense: all P)."""
+def compress_k(cfg, P: int, dims=None) -> int:
+    """Entries a config's compressor transmits of P parameters (sign, qsgd and dense: all P; powersgd:
+    the factors' entries and every raw entry of the model ``dims``)."""
+    if cfg.compress in LOWRANK_COMPRESSORS:
+        if dims is None:
+            raise ValueError("compress_k: compress='powersgd' needs the model's dims")
+        return lowrank_layers(dims, int(cfg.compress_rank))["entries"]
     return topk_count(cfg.compress_ratio, P) if cfg.compress in ("topk", "randk") else int(P)
 
 
@@ -107,16 +141,16 @@ def uplink_bytes(kind: str, k: int, P: int, levels: int = 127) -> int:
     index per kept entry), sign ``4 + ceil(P / 8)`` (the fp32 scale and one bit per coordinate), qsgd
     ``4 + ceil(P * ceil(log2(2 s + 1)) / 8)`` (the fp32 norm and a fixed-width sign-and-level code per
     coordinate; no Elias coding), randk ``4 k`` (the values only: the indices follow from the shared
-    seed), dense ``4 P``."""
-    if kind not in ALL_COMPRESSORS:
-        raise ValueError(f"compress must be one of {ALL_COMPRESSORS}, got {kind!r}")
+    seed), powersgd ``4 k`` (``k`` = :func:`compress_k`: factors and raw entries), dense ``4 P``."""
+    if kind not in COMPRESSOR_KINDS:
+        raise ValueError(f"compress must be one of {COMPRESSOR_KINDS}, got {kind!r}")
     if kind == "topk":
         return 8 * int(k)
     if kind == "sign":
         return 4 + (int(P) + 7) // 8
     if kind == "qsgd":
         return 4 + (int(P) * qsgd_code_bits(levels) + 7) // 8
-    if kind == "randk":
+    if kind == "randk" or kind in LOWRANK_COMPRESSORS:
         return 4 * int(k)
     return 4 * int(P)
 
@@ -289,3 +323,108 @@ def compress_round(local, x, e, w: float, kind: str, k: int = 0, error_feedback:
     c, e_new, stat = compress_torch(u, kind, k, error_feedback, s, levels=levels, seed=seed, round=round,
                                     client=client, norm=norm)
     return torch.tensor(float(w), dtype=local.dtype) * (x + c), e_new, stat
+
+
+# ---- low-rank factors (PowerSGD): the host model of fl_lowrank.hip ----
+def lowrank_layers(dims, r: int) -> dict:
+    """Which layers of the model ``dims`` rank ``r`` compresses: ``layers`` = one dict per Linear layer
+    (``N``, ``K``, ``compressed``, dense offsets ``w_off`` / ``b_off``, ``q_off`` = offset of its
+    ``Q [K][r]`` in the state vector), ``q_len`` = the state's length, ``entries`` = floats a real uplink
+    carries (``r (N + K)`` per compressed layer and every raw entry)."""
+    r = int(r)
+    if not 1 <= r <= MAX_RANK:
+        raise ValueError(f"compress_rank must be an integer in [1, {MAX_RANK}], got {r!r}")
+    layers, off, q_off, entries = [], 0, 0, 0
+    for K, N in zip(dims[:-1], dims[1:]):
+        K, N = int(K), int(N)
+        comp = r * (N + K) < N * K
+        layers.append(dict(N=N, K=K, compressed=comp, w_off=off, b_off=off + N * K, q_off=q_off))
+        off += N * K + N
+        q_off += r * K if comp else 0
+        entries += (r * (N + K) if comp else N * K) + N
+    return dict(layers=layers, q_len=q_off, entries=entries, P=off)
+
+
+def lowrank_q0(dims, r: int, seed: Optional[int]) -> np.ndarray:
+    """``Q_0`` of every compressed layer, concatenated in layer order (fp32 ``[q_len]``): standard normals
+    of ``numpy.random.default_rng(seed)``, one ``(K, r)`` draw per compressed layer; ``None``: a private
+    64-bit seed."""
+    import os
+    g = np.random.default_rng(int.from_bytes(os.urandom(8), "little") if seed is None else int(seed))
+    parts = [g.standard_normal((ly["K"], int(r))).astype(np.float32).reshape(-1)
+             for ly in lowrank_layers(dims, r)["layers"] if ly["compressed"]]
+    return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+
+
+def wave_dot(a: np.ndarray, b: np.ndarray):
+    """``<a, b>`` as one 64-lane wave of the kernel sums it: lane t adds the products of entries t,
+    t + 64, ... in turn from ``+0``, then the xor tree (offsets 32, 16, ... 1).  (A lane's sum is never
+    ``-0``, so the ``+0`` products of the padding change no bit.)"""
+    ft = a.dtype.type
+    prod = a * b
+    pad = np.zeros(-(-prod.shape[0] // 64) * 64, ft)
+    pad[:prod.shape[0]] = prod
+    lanes = np.zeros(64, ft)
+    for row in pad.reshape(-1, 64):
+        lanes = lanes + row
+    idx, off = np.arange(64), 32
+    while off:
+        lanes = lanes + lanes[idx ^ off]
+        off >>= 1
+    return lanes[0]
+
+
+def _lowrank_layer(M: np.ndarray, Q: np.ndarray):
+    """One power iteration on ``M [N][K]`` from ``Q [K][r]``: ``(c, Q', finite)``; every operation one
+    rounding in ``M``'s float type, the orders of the module docstring."""
+    ft = M.dtype.type
+    N, K = M.shape
+    r = Q.shape[1]
+    P = np.zeros((N, r), ft)
+    for k in range(K):
+        P = P + M[:, k:k + 1] * Q[k:k + 1, :]
+    finite = True
+    for j in range(r):
+        for i in range(j):
+            P[:, j] = P[:, j] - wave_dot(P[:, i], P[:, j]) * P[:, i]
+        ss = wave_dot(P[:, j], P[:, j])
+        finite = finite and bool(np.isfinite(ss))
+        P[:, j] = ft(0.0) if ss == 0 else P[:, j] / np.sqrt(ss)
+    Qn = np.zeros((K, r), ft)
+    for n in range(N):
+        Qn = Qn + M[n, :, None] * P[n:n + 1, :]
+    c = np.zeros((N, K), ft)
+    for j in range(r):
+        c = c + P[:, j:j + 1] * Qn[None, :, j]
+    return c, Qn, finite
+
+
+def lowrank_torch(u, q, dims, r: int, error_feedback: bool = True):
+    """``(c, e', q', stat)`` of the dense vector ``u`` and the state ``q`` (:func:`lowrank_layers` order)
+    for the model ``dims`` at rank ``r``.  In fp32 a bit-exact model of the kernel; float64 inputs run the
+    same rule in float64."""
+    u = _vec(u)
+    a = u.numpy()
+    ft = a.dtype.type
+    qv = np.ascontiguousarray(torch.as_tensor(q).detach().cpu().numpy().reshape(-1), dtype=a.dtype)
+    plan = lowrank_layers(dims, r)
+    if a.shape[0] != plan["P"] or qv.shape[0] != plan["q_len"]:
+        raise ValueError(f"lowrank_torch: u has {a.shape[0]} entries and q {qv.shape[0]}, the model "
+                         f"{plan['P']} and {plan['q_len']}")
+    c, e, qn = a.copy(), np.zeros_like(a), qv.copy()
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for ly in plan["layers"]:
+            if not ly["compressed"]:
+                continue
+            N, K, wo, qo = ly["N"], ly["K"], ly["w_off"], ly["q_off"]
+            cl, ql, finite = _lowrank_layer(a[wo:wo + N * K].reshape(N, K), qv[qo:qo + K * int(r)].reshape(K, int(r)))
+            if finite:   # else: the layer travels raw and keeps its Q
+                c[wo:wo + N * K] = cl.reshape(-1)
+                e[wo:wo + N * K] = a[wo:wo + N * K] - c[wo:wo + N * K]
+                qn[qo:qo + K * int(r)] = ql.reshape(-1)
+        d = a - c
+        den = np.sqrt(ordered_sum(a * a))
+        stat = ft(0.0) if den == 0 else ft(np.sqrt(ordered_sum(d * d)) / den)
+    if not error_feedback:
+        e = np.zeros_like(a)
+    return torch.as_tensor(c), torch.as_tensor(e), torch.as_tensor(qn), float(stat)

@@ -34,7 +34,8 @@ from .aggregate import (AGGREGATORS, ALL_AGGREGATORS, GEOMED_MAX_ITERS, MAX_ROBU
                         geomed_torch, mask_bits, pair_distances_torch, robust_aggregate_torch, screen_select)
 from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
                      attack_torch)
-from .compress import COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch, uplink_bytes
+from .compress import (COMPRESSORS, LOWRANK_COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch,
+                       lowrank_layers, lowrank_q0, lowrank_torch, uplink_bytes)
 from .early_stop import EarlyStopper
 from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
 from .secagg import (MAX_SECAGG_CLIENTS, SECAGG_STREAM, secagg_id, secagg_mask, secagg_open,
@@ -173,12 +174,17 @@ class EngineConfig:
     # without it the kept entries are scaled by P / k, the unbiased variant; compress_stat = the
     # selection's quantile).  compress_seed: None = a private 64-bit draw per client (kept in the portable
     # state, so a resume continues the stream), an int in [0, 2**64) = reproducible runs.
+    # "powersgd" (Vogels et al. 2019) sends rank-compress_rank factors of every weight matrix they are
+    # cheaper than (one warm-started power iteration per round; biases and the other matrices travel raw;
+    # deterministic; compress_stat = the relative error ||u - c|| / ||u||).  Its per-layer state Q starts
+    # from numpy.random.default_rng(compress_seed) and travels in the portable state as compress_q.
     # Not with dp_clip > 0, trial batches (comm_buffers), fed_sweep or WideClient.
     compress: str = "none"
     compress_ratio: float = 0.1
     error_feedback: bool = True
     compress_levels: int = 127
     compress_seed: Optional[int] = None
+    compress_rank: int = 4
     # Secure aggregation (fedmi/fl/secagg.py; Bonawitz et al. 2017): every sampled client quantises its
     # weighted contribution to fixed point with secagg_bits fractional bits and adds / subtracts one
     # Philox mask per pair of the round's sampled clients (mod 2^32) before the exchange; the masks
@@ -575,7 +581,13 @@ class RoundEngineBase:
         self.tail_stride = self.n_classes * self.n_classes + 1
         self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress),
                              secagg=bool(self.secagg), screen=bool(self.screen))
-        self.compress_k = compress_k(cfg, self.P)   # entries a contribution transmits (sign, dense: P)
+        # entries a contribution transmits (sign, dense: P; powersgd: factors and raw entries)
+        self.compress_k = compress_k(cfg, self.P, self.dims)
+        # the low-rank kind carries one more piece of state: Q of every compressed layer, from Q_0
+        self.compress_lowrank = cfg.compress in LOWRANK_COMPRESSORS
+        if self.compress_lowrank:
+            self.compress_q_len = lowrank_layers(self.dims, cfg.compress_rank)["q_len"]
+            self._compress_q0 = lowrank_q0(self.dims, cfg.compress_rank, cfg.compress_seed)
         self.heldout = False     # set_heldout: the global model is scored on a held-out set every round
         self.keep_best = False   # ... and the model of the round with the smallest held-out loss is kept
         assert init_flat.shape == (self.P,)
@@ -833,12 +845,30 @@ class RoundEngineBase:
     def _set_compress_seed(self, seed: int) -> None:
         self.compress_seed = int(seed)
 
-    def _compress_state_out(self, residual) -> dict:
-        """The compression entries of a portable state: the dense residual and, stochastic kinds, the seed."""
+    def _compress_state_out(self, residual, q=None) -> dict:
+        """The compression entries of a portable state: the dense residual and, stochastic kinds, the seed,
+        low-rank kind, the layers' Q."""
         if not self.compress:
             return {}
         return {"compress_residual": residual,
-                **({"compress_seed": int(self.compress_seed)} if self.compress_random else {})}
+                **({"compress_seed": int(self.compress_seed)} if self.compress_random else {}),
+                **({"compress_q": np.asarray(q, np.float32).copy()} if self.compress_lowrank else {})}
+
+    def _compress_q_in(self, st: dict):
+        """The low-rank state Q of a portable state for this engine, or None for the other kinds; a state
+        and an engine that disagree on having one, or on its length, do not match."""
+        has = st.get("compress_q") is not None
+        if has != self.compress_lowrank:
+            raise ValueError("checkpoint and engine disagree on compression: the state "
+                             + ("carries" if has else "has no") + " compress_q, the engine has compress="
+                             + repr(self.cfg.compress))
+        if not has:
+            return None
+        q = np.asarray(st["compress_q"], np.float32).reshape(-1)
+        if q.shape != (self.compress_q_len,):
+            raise ValueError(f"compress_q has {q.shape[0]} entries, the model at compress_rank="
+                             f"{self.cfg.compress_rank} {self.compress_q_len}")
+        return q
 
     def uplink_bytes(self) -> int:
         """Bytes per round a real uplink would carry for this client's contribution (the exchange
@@ -909,6 +939,8 @@ class TorchRoundEngine(RoundEngineBase):
         if self.compress:
             self.compress_residual = torch.zeros(self.P, dtype=torch.float32)   # dense order
             self._compressed = (-1, None)   # (round, x + C(u)) of the last compressed round
+            if self.compress_lowrank:
+                self.compress_q = torch.as_tensor(self._compress_q0.copy())
 
     def train_one_epoch(self) -> float:
         """``local_steps`` full-batch Adam steps + one StepLR step (reference C:63-73)."""
@@ -1118,8 +1150,12 @@ class TorchRoundEngine(RoundEngineBase):
             u = (local.to(torch.float32) - x) + self.compress_residual
             rnd = (dict(levels=int(self.cfg.compress_levels), seed=self.compress_seed, round=r, client=self.rank)
                    if self.compress_random else {})
-            c, self.compress_residual, stat = compress_torch(u, self.cfg.compress, self.compress_k,
-                                                             bool(self.cfg.error_feedback), **rnd)
+            if self.compress_lowrank:
+                c, self.compress_residual, self.compress_q, stat = lowrank_torch(
+                    u, self.compress_q, self.dims, int(self.cfg.compress_rank), bool(self.cfg.error_feedback))
+            else:
+                c, self.compress_residual, stat = compress_torch(u, self.cfg.compress, self.compress_k,
+                                                                 bool(self.cfg.error_feedback), **rnd)
             self.hist.cstat[r] = stat
             out = x + c
         self._compressed = (r, out)
@@ -1332,7 +1368,8 @@ class TorchRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
-            **self._compress_state_out(self.compress_residual.numpy().copy() if self.compress else None),
+            **self._compress_state_out(self.compress_residual.numpy().copy() if self.compress else None,
+                                       self.compress_q.numpy() if self.compress and self.compress_lowrank else None),
             **self._heldout_state_out(None if not self.heldout or self._ho_best_flat is None
                                       else self._ho_best_flat.copy()),
         }
@@ -1342,7 +1379,10 @@ class TorchRoundEngine(RoundEngineBase):
         cfg = self.cfg
         sv = self._server_state_in(st)
         ce = self._compress_state_in(st)
+        cq = self._compress_q_in(st)
         ho = self._heldout_state_in(st)
+        if cq is not None:
+            self.compress_q = torch.as_tensor(cq.copy())
         if ho is not None:
             self._ho_best = np.float32(ho["best_loss_sum"])
             self._ho_best_flat = (None if ho.get("best_flat") is None or not self.keep_best
@@ -1551,6 +1591,13 @@ class HipRoundEngine(RoundEngineBase):
             if self.compress_random:
                 ecfg.update({"compress_levels": int(cfg.compress_levels), "compress_seed": int(self.compress_seed)})
             bufs.update({"compress_residual": self.cp_res.data_ptr(), "compress_stat": self.cp_stat.data_ptr()})
+            if self.compress_lowrank:
+                # Q of the compressed layers: two halves by round parity as the residual (fl_lowrank.hip), both Q_0
+                # (one float at least, so a model without a compressed layer still has a buffer to name)
+                self.cp_q = torch.zeros(2 * max(1, self.compress_q_len), **f32)
+                self.cp_q[:2 * self.compress_q_len].copy_(torch.as_tensor(self._compress_q0).repeat(2))
+                ecfg["compress_rank"] = int(cfg.compress_rank)
+                bufs["compress_q"] = self.cp_q.data_ptr()
         if self.server:
             # server optimizer state: image-shaped fp32 (m = 0; v = tau^2 everywhere, padding included)
             if comm_buffers is not None:
@@ -2321,6 +2368,14 @@ class HipRoundEngine(RoundEngineBase):
         half = int(self.hist.rounds_run) & 1
         return image_to_dense(self.cp_res[half * self.Pimg:(half + 1) * self.Pimg].cpu().numpy(), self.dims)
 
+    @property
+    def compress_q(self) -> np.ndarray:
+        """The low-rank state Q of the compressed layers as the next live round will read it (the half the
+        last live round wrote, as :attr:`compress_residual`)."""
+        self.stream.synchronize()
+        n, half = self.compress_q_len, int(self.hist.rounds_run) & 1
+        return self.cp_q[half * n:(half + 1) * n].cpu().numpy()
+
     def portable_state(self) -> dict:
         self.sync_history()
         r = self.rounds_issued
@@ -2336,7 +2391,8 @@ class HipRoundEngine(RoundEngineBase):
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
-            **self._compress_state_out(self.compress_residual if self.compress else None),
+            **self._compress_state_out(self.compress_residual if self.compress else None,
+                                       self.compress_q if self.compress and self.compress_lowrank else None),
             **self._heldout_state_out(None if not (self.heldout and self.keep_best and self._ho_best_words()[1] >= 0)
                                       else self.best_flat()),
         }
@@ -2347,6 +2403,7 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"checkpoint has {r} rounds > max_rounds {self.cfg.max_rounds}")
         sv = self._server_state_in(st)
         ce = self._compress_state_in(st)
+        cq = self._compress_q_in(st)
         ho = self._heldout_state_in(st)
         self.stream.synchronize()
         dev = self.device
@@ -2364,6 +2421,8 @@ class HipRoundEngine(RoundEngineBase):
                                                 img(sv[1])))
             if ce is not None:   # both halves: whichever the next live round reads
                 self.cp_res.copy_(img(ce).repeat(2))
+            if cq is not None:
+                self.cp_q[:2 * self.compress_q_len].copy_(torch.as_tensor(cq, device=dev).repeat(2))
             es = st["es"]
             rec = np.zeros(1, dtype=_STATE_DTYPE)
             rec["next_round"] = r

@@ -103,9 +103,16 @@ def _build_lock():
             fcntl.flock(f, fcntl.LOCK_UN)
 
 
+# Flags of single sources.  fl_lowrank.hip is held bit for bit to a numpy model with one rounding per
+# operation: it is compiled without the packed fp32 forms (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32), so
+# the vectoriser cannot pair its separate products and sums into them.
+_SOURCE_FLAGS = {"fl_lowrank.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _compile(src: str, digest: str) -> str:
     obj = os.path.join(BUILD, os.path.basename(src) + ".o")
     extra = os.environ.get("FEDMI_HIPCC_FLAGS", "").split()  # experiments, e.g. -DFL_THREADS=1024
+    extra += _SOURCE_FLAGS.get(os.path.basename(src), [])
     cmd = ["hipcc", "-c", "-fPIC", "-O3", "-std=c++17", f"--offload-arch={ARCH}", *extra,
            f'-DFEDMI_SRC_DIGEST="{digest}"', "-I" + CSRC, *_pybind_includes(), src, "-o", obj]
     if src.endswith(".cpp"):

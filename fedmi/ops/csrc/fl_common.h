@@ -352,6 +352,28 @@ struct FLCompress {
     uint32_t key0, key1; // stochastic kinds: Philox key, the client's 64-bit compress seed, low and high word
 };
 
+// Low-rank compression (fl_lowrank.hip; PowerSGD, Vogels et al. 2019): parameters of the per-round kernel that
+// takes fl_compress's place for this kind, passed to that kernel alone.  Per weight matrix M [N][K] of u with
+// rank (N + K) < N K, one warm-started power iteration on the layer's state Q [K][rank]: P = M Q, P's columns
+// orthonormalised (modified Gram-Schmidt), Q' = M^T P, C(M) = P Q'^T, Q <- Q'; biases and the other matrices
+// travel raw.  fl_lowrank_plan fills everything but the flags and the pointers.
+#define FL_COMPRESS_POWERSGD 5
+#define FL_LOWRANK_MAX_RANK 8
+struct FLLowRank {
+    int rank;            // r, 1 .. FL_LOWRANK_MAX_RANK
+    int error_feedback;  // as FLCompress
+    int max_rounds;      // entries of stat_hist; rounds past it are not live
+    int comp;            // bit l: layer l is compressed
+    int Qlen;            // floats of one half of q: rank * sum K over the compressed layers
+    int Plen;            // floats of the P factors: rank * sum N over the compressed layers
+    int entries;         // floats a real uplink carries: rank (N + K) per compressed layer + every raw entry
+    int q_off[FL_MAX_LAYERS + 1];  // offset of layer l's Q [K][rank] in a half of q (prefix sums; [L..]: Qlen)
+    int p_off[FL_MAX_LAYERS + 1];  // offset of layer l's P [N][rank] in the kernel's LDS (prefix sums)
+    float* residual;     // [2][Pimg] fp32, as FLCompress::residual
+    float* stat_hist;    // [max_rounds] sqrt(sum (u - c)^2) / sqrt(sum u^2) (0: not sampled, or u = 0)
+    float* q;            // [2][Qlen] fp32, caller-owned, both halves Q_0 at start: halves by round parity as residual
+};
+
 // Robust aggregation (fl_robust.hip; Yin et al. 2018): parameters of the per-round coordinate-wise
 // median / trimmed mean over K clients' buffers, passed to that kernel alone.  Of the round's K_r
 // sampled clients (rtab mask) the fl_robust_trim lowest and highest values of every coordinate are
@@ -571,6 +593,13 @@ hipError_t fl_launch_dp(const MLPDesc& d, const FLDp& p, const float* local, con
 hipError_t fl_set_lds_limit_compress(const MLPDesc& d, int kind = FL_COMPRESS_TOPK);
 hipError_t fl_launch_compress(const MLPDesc& d, const FLCompress& p, const float* local, const float* pg, float* comm,
                               const FLState* st, const float* rtab, hipStream_t s);
+// (fl_lowrank.hip) the same slot for FL_COMPRESS_POWERSGD.  fl_lowrank_plan: the layers rank `rank` compresses
+// and their offsets into `p` (pointers and flags are the caller's); fl_set_lds_limit_lowrank: once per model
+// and rank before the first launch (dynamic LDS).
+hipError_t fl_lowrank_plan(const MLPDesc& d, int rank, FLLowRank& p);
+hipError_t fl_set_lds_limit_lowrank(const MLPDesc& d, const FLLowRank& p);
+hipError_t fl_launch_lowrank(const MLPDesc& d, const FLLowRank& p, const float* local, const float* pg, float* comm,
+                             const FLState* st, const float* rtab, hipStream_t s);
 // (fl_server.hip) server-optimizer step of the round whose state is `st`: `x` = the image the round
 // trained from, `a` = its aggregated image, replaced in place (first Pimg floats only) by the new
 // global image.  `e` / `pk` (bf16 mode, else null): the same launch also writes the packed

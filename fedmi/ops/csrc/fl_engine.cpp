@@ -300,7 +300,24 @@ class FLEngine {
             if (dp_.sigma == nullptr || dp_.norm_hist == nullptr)
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
         }
-        if (tr_.compress_on) {
+        std::memset(&lr_, 0, sizeof(lr_));
+        if (cp_.kind == FL_COMPRESS_POWERSGD) {
+            // low-rank factors (fl_lowrank.hip) in the compression slot: its own argument struct, the same
+            // residual and statistic buffers, and the Q state beside them
+            const int rank = cfg["compress_rank"].cast<int>();
+            if (fl_lowrank_plan(d_, rank, lr_) != hipSuccess)
+                throw std::runtime_error("FLEngine: compress_rank must be in 1 .. " + std::to_string(FL_LOWRANK_MAX_RANK));
+            cp_.P = d_.P;
+            cp_.k = lr_.entries;
+            lr_.error_feedback = cp_.error_feedback = cfg["error_feedback"].cast<bool>() ? 1 : 0;
+            lr_.max_rounds = cp_.max_rounds = c_.max_rounds;
+            lr_.residual = cp_.residual = as_ptr<float>(bufs["compress_residual"].cast<uintptr_t>());
+            lr_.stat_hist = cp_.stat_hist = as_ptr<float>(bufs["compress_stat"].cast<uintptr_t>());
+            lr_.q = as_ptr<float>(bufs["compress_q"].cast<uintptr_t>());
+            if (lr_.residual == nullptr || lr_.stat_hist == nullptr || lr_.q == nullptr)
+                throw std::runtime_error("FLEngine: powersgd needs the residual, the statistic history and compress_q");
+            HIP_CHECK(fl_set_lds_limit_lowrank(d_, lr_));
+        } else if (tr_.compress_on) {
             if (cp_.kind < FL_COMPRESS_TOPK || cp_.kind > FL_COMPRESS_RANDK)
                 throw std::runtime_error("FLEngine: unknown compressor");
             cp_.P = d_.P;
@@ -939,7 +956,7 @@ class FLEngine {
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
         {
             // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
-            static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk"};
+            static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk", "powersgd"};
             const long long P = d_.P, k = tr_.compress_on ? cp_.k : P;
             long long code_bits = 0;  // qsgd: ceil(log2(2 s + 1)), a fixed-width sign-and-level code
             while ((1ll << code_bits) < 2ll * cp_.levels + 1) ++code_bits;
@@ -950,9 +967,13 @@ class FLEngine {
             c["uplink_bytes"] = cp_.kind == FL_COMPRESS_TOPK   ? 8 * k
                                 : cp_.kind == FL_COMPRESS_SIGN ? 4 + (P + 7) / 8
                                 : cp_.kind == FL_COMPRESS_QSGD ? 4 + (P * code_bits + 7) / 8
-                                : cp_.kind == FL_COMPRESS_RANDK ? 4 * k
+                                : cp_.kind == FL_COMPRESS_RANDK || cp_.kind == FL_COMPRESS_POWERSGD ? 4 * k
                                                                : 4 * P;
             if (cp_.kind == FL_COMPRESS_QSGD) c["levels"] = cp_.levels;
+            if (cp_.kind == FL_COMPRESS_POWERSGD) {  // k: the factors' entries and every raw entry
+                c["rank"] = lr_.rank;
+                c["q_len"] = lr_.Qlen;
+            }
             o["compress"] = c;
         }
         static const char* server_names[] = {"none", "sgd", "adagrad", "adam", "yogi"};
@@ -1077,7 +1098,10 @@ class FLEngine {
                 HIP_CHECK(fl_launch_dp(d_, dp_, F(0), F(1), F(2), S(3), b_.rtab, s));
                 break;
             case FLLaunchRec::COMPRESS:
-                HIP_CHECK(fl_launch_compress(d_, cp_, F(0), F(1), F(2), S(3), b_.rtab, s));
+                if (cp_.kind == FL_COMPRESS_POWERSGD)
+                    HIP_CHECK(fl_launch_lowrank(d_, lr_, F(0), F(1), F(2), S(3), b_.rtab, s));
+                else
+                    HIP_CHECK(fl_launch_compress(d_, cp_, F(0), F(1), F(2), S(3), b_.rtab, s));
                 break;
             case FLLaunchRec::SERVER:
                 HIP_CHECK(fl_launch_server(d_, sv_, F(0), F(1), S(2), eb, dtype_ == 1 ? b_.pk_global : nullptr, s));
@@ -1152,6 +1176,7 @@ class FLEngine {
     void** sa_tab_ = nullptr;        // ... device pointer tables of the mask launch: {send 0, send 1, clamp history}
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
+    FLLowRank lr_;             // ... or, cp_.kind == FL_COMPRESS_POWERSGD, fl_lowrank_kernel in its place
     bool compress_random() const { return cp_.kind == FL_COMPRESS_QSGD || cp_.kind == FL_COMPRESS_RANDK; }
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLHeldout ho_ = {};        // held-out scoring: fl_heldout row + fold launches at the end of every round
@@ -1607,6 +1632,28 @@ static void compress_launch(std::vector<int> dims, int kind, int k, bool error_f
                                  as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
 }
 
+// One fl_lowrank launch on caller-owned buffers of the image of `dims` (tests, tools): `residual` and `stat`
+// as compress_launch's, `q` = 2 x Qlen floats (halves by round parity; fedmi/fl/compress.py lowrank_layers).
+static void lowrank_launch(std::vector<int> dims, int rank, bool error_feedback, uintptr_t local, uintptr_t x,
+                           uintptr_t comm, uintptr_t residual, uintptr_t q, uintptr_t stat, uintptr_t state,
+                           uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    const MLPDesc d = desc_of(dims, "lowrank_launch");
+    FLLowRank p;
+    std::memset(&p, 0, sizeof(p));
+    if (fl_lowrank_plan(d, rank, p) != hipSuccess)
+        throw std::runtime_error("lowrank_launch: rank must be in 1 .. " + std::to_string(FL_LOWRANK_MAX_RANK));
+    if (max_rounds < 1 || !local || !x || !comm || !residual || !q || !stat || !state || !rtab)
+        throw std::runtime_error("lowrank_launch: bad arguments");
+    p.error_feedback = error_feedback ? 1 : 0;
+    p.max_rounds = max_rounds;
+    p.residual = as_ptr<float>(residual);
+    p.stat_hist = as_ptr<float>(stat);
+    p.q = as_ptr<float>(q);
+    HIP_CHECK(fl_set_lds_limit_lowrank(d, p));
+    HIP_CHECK(fl_launch_lowrank(d, p, as_ptr<const float>(local), as_ptr<const float>(x), as_ptr<float>(comm),
+                                as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
+}
+
 #ifndef FEDMI_SRC_DIGEST
 #define FEDMI_SRC_DIGEST "unknown"
 #endif
@@ -1717,6 +1764,10 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
           py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"),
           py::arg("levels") = 127, py::arg("client") = 0, py::arg("seed") = 0ull);
+    m.def("lowrank_launch", &lowrank_launch, py::arg("dims"), py::arg("rank"), py::arg("error_feedback"),
+          py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"), py::arg("q"), py::arg("stat"),
+          py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+    m.attr("LOWRANK_MAX_RANK") = (int)FL_LOWRANK_MAX_RANK;
     m.def("secagg_mask", &secagg_mask, py::arg("dims"), py::arg("bits"), py::arg("seed"), py::arg("bufs"), py::arg("n"),
           py::arg("first_client"), py::arg("state"), py::arg("rtab"), py::arg("clamp"), py::arg("max_rounds"),
           py::arg("stream"));

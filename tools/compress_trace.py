@@ -35,6 +35,10 @@ NEW_CASES = [("qsgd-127", dict(compress="qsgd", compress_levels=127, compress_se
              ("qsgd-1", dict(compress="qsgd", compress_levels=1, compress_seed=1)),
              ("randk-10%", dict(compress="randk", compress_ratio=0.1, compress_seed=1)),
              ("randk-1%", dict(compress="randk", compress_ratio=0.01, compress_seed=1))]
+# low-rank factors next to the two kernels they are placed against (same session)
+LOWRANK_CASES = [("classic", {}), ("sign", dict(compress="sign")), ("topk-10%", dict(compress="topk", compress_ratio=0.1)),
+                 *[(f"powersgd-r{r}", dict(compress="powersgd", compress_rank=r, compress_seed=1)) for r in (1, 4, 8)]]
+LOWRANK_CONV = [(f"powersgd-r{r}", dict(compress="powersgd", compress_rank=r, compress_seed=1)) for r in (1, 2, 4)]
 
 
 def main():
@@ -44,13 +48,13 @@ def main():
     ap.add_argument("--backend", default="hip", help="--convergence: hip | torch")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compress_trace.jsonl"))
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
-    ap.add_argument("--cases", choices=["old", "new", "all"], default="all",
-                    help="old: classic, dp-clip, top-k, sign; new: qsgd, rand-k")
+    ap.add_argument("--cases", choices=["old", "new", "all", "lowrank"], default="all",
+                    help="old: classic, dp-clip, top-k, sign; new: qsgd, rand-k; lowrank: powersgd beside sign and top-k")
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--no-trace", action="store_true", help="--convergence only")
     a = ap.parse_args()
-    timed = {"old": CASES, "new": NEW_CASES, "all": CASES + NEW_CASES}[a.cases]
-    conv = {"old": CASES[2:], "new": NEW_CASES, "all": CASES[2:] + NEW_CASES}[a.cases]
+    timed = {"old": CASES, "new": NEW_CASES, "all": CASES + NEW_CASES, "lowrank": LOWRANK_CASES}[a.cases]
+    conv = {"old": CASES[2:], "new": NEW_CASES, "all": CASES[2:] + NEW_CASES, "lowrank": LOWRANK_CONV}[a.cases]
     so = os.environ.get("FEDMI_NATIVE_SO") or "tree"
     from fedmi.data.tabular import load_tabular
     from fedmi.fl.engine import EngineConfig, HipRoundEngine
@@ -79,7 +83,7 @@ def main():
                       "compress_layout": e.layout["compress"], "native_so": so,
                       **{k: (round(v, 2) if isinstance(v, float) else v) for k, v in tr.items()}})
     if a.convergence:
-        table = ([("dense", {})] if a.cases != "new" else []) + [
+        table = ([("dense", {})] if a.cases in ("old", "all") else []) + [
             (f"{name} ef={int(ef)}", dict(error_feedback=ef, **kw)) for name, kw in conv for ef in (True, False)]
         for name, kw in table:
             cfg = EngineConfig(max_rounds=300, **kw)
@@ -87,7 +91,8 @@ def main():
             from fedmi.fl.compress import compress_k, uplink_bytes
             P = len(flat)
             emit({"what": "rounds_to_target", "clients": 8, "backend": a.backend, "case": name,
-                  "uplink_bytes": uplink_bytes(cfg.compress, compress_k(cfg, P), P, cfg.compress_levels), **res})
+                  "uplink_bytes": uplink_bytes(cfg.compress, compress_k(cfg, P, [X.shape[1], 50, 200, 2]), P,
+                                               cfg.compress_levels), **res})
     out.close()
 
 
