@@ -140,6 +140,10 @@ def parse_args(argv=None):
                     help="score the round's GLOBAL model on the 20 %% test split at the end of every round (in the "
                          "round's graph on the HIP engine); --jsonl rows gain heldout_accuracy|precision|recall|f1|loss "
                          "and the run ends with one line naming the best held-out round (not with --wide)")
+    ap.add_argument("--heldout-auc", action="store_true",
+                    help="--heldout, and every round also ranks the test split by the global model's probability on "
+                         "the device: --jsonl rows gain heldout_auc (ROC AUC of class 1) and the closing line prints "
+                         "the final round's (implies --heldout; at most 32768 held-out rows)")
     ap.add_argument("--keep-best", action="store_true",
                     help="--heldout: keep the model of the round with the smallest held-out loss (--predict-out then "
                          "writes its probabilities)")
@@ -192,7 +196,9 @@ def parse_args(argv=None):
                     help="--wide: Adam learning rate (default fedmi.fl.wide.WIDE_LR = 1e-4: the reference's 0.004 "
                          "makes the 4096-wide model diverge, in torch as on the kernels, profiles/wide_learn_r3.log)")
     ap.add_argument("--wide-warmup", type=int, default=0, help="--wide: linear LR warm-up rounds")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    a.heldout = a.heldout or a.heldout_auc
+    return a
 
 
 def main_wide(a, comm):
@@ -285,8 +291,12 @@ def _print_heldout(a, h: dict) -> None:
         if b < 0:
             print("Held-out: no round scored a finite loss", flush=True)
         else:
+            auc = ""
+            if a.heldout_auc and h["rounds_run"]:
+                from fedmi.fl.engine import heldout_auc_score
+                auc = f"; final held-out AUC {float(heldout_auc_score(h)[-1]):.4f}"
             print(f"Best held-out round: {b + 1} (loss {float(h['heldout_loss'][b]):.4f}, accuracy "
-                  f"{float(heldout_metrics(h)[b, 0]):.4f})", flush=True)
+                  f"{float(heldout_metrics(h)[b, 0]):.4f}){auc}", flush=True)
 
 
 def _write_predictions(a, eng, X_test) -> None:
@@ -317,7 +327,8 @@ def main_clients(a, comm):
     shard = a.partition or ("compat" if a.mode == "compat" else "iid")
     g = ClientGroup(ds.X_train, ds.y_train, a.clients, cfg, backend=backend, shard_mode=shard, seed=a.seed,
                     alpha=a.alpha, device=comm.device if backend == "hip" else None,
-                    heldout=(ds.X_test, ds.y_test) if a.heldout else None, keep_best=a.keep_best)
+                    heldout=(ds.X_test, ds.y_test) if a.heldout else None, keep_best=a.keep_best,
+                    heldout_auc=a.heldout_auc)
     t0 = time.perf_counter()
     g.run(a.rounds)
     wall = time.perf_counter() - t0
@@ -423,7 +434,7 @@ def main(argv=None):
                                    output_size=2 if a.synthetic else None,
                                    n_total=a.synthetic_rows * size if a.synthetic else None)
     if a.heldout:
-        trainer.set_heldout(ds.X_test, ds.y_test, keep_best=a.keep_best)   # before --resume: the rows continue
+        trainer.set_heldout(ds.X_test, ds.y_test, keep_best=a.keep_best, auc=a.heldout_auc)   # before --resume: the rows continue
     t_setup = time.perf_counter()
     done = 0   # rounds restored from a checkpoint (not run by this process)
     if a.resume:

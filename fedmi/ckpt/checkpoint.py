@@ -156,6 +156,9 @@ def save_checkpoint(path: str, trainer) -> None:
         "heldout_loss_sum": np.asarray(st["history"]["heldout_loss_sum"], np.float32),
         "heldout_best": np.asarray([st["heldout"]["best_loss_sum"]], np.float32),
         "heldout_best_round": np.asarray([int(st["heldout"]["best_round"])], np.int64),
+        # (set_heldout(auc=True): the exact doubled Mann-Whitney counts; the AUCs are derived from them)
+        **({"heldout_auc_u2": np.asarray(st["history"]["heldout_auc_u2"], np.int64)}
+           if st["heldout"].get("auc") else {}),
         **({} if st["heldout"].get("best_flat") is None else
            {"heldout_best_flat": np.asarray(st["heldout"]["best_flat"], np.float32)})}
     _atomic(os.path.join(path, tagged(cname, R)), lambda tmp: save_file(
@@ -254,6 +257,9 @@ def resume(path: str, trainer) -> int:
         st["heldout"] = {"best_round": st["history"]["heldout_best_round"],
                          "best_loss_sum": float(np.asarray(c["heldout_best"], np.float32).reshape(-1)[0]),
                          "best_flat": np.asarray(c["heldout_best_flat"], np.float32) if "heldout_best_flat" in c else None}
+        if "heldout_auc_u2" in c:
+            st["history"]["heldout_auc_u2"] = np.asarray(c["heldout_auc_u2"], np.int64)
+            st["heldout"]["auc"] = True
     eng.load_portable_state(st)   # raises when checkpoint and engine disagree on the server optimizer / compression
     return st["rounds"]
 

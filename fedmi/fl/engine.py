@@ -37,7 +37,8 @@ from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients
 from .compress import (COMPRESSORS, LOWRANK_COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch,
                        lowrank_layers, lowrank_q0, lowrank_torch, uplink_bytes)
 from .early_stop import EarlyStopper
-from .metrics import METRIC_NAMES, confusion_matrix, metrics_from_confusion, metric_vector
+from .metrics import (METRIC_NAMES, auc_from_u2, auc_u2_model, confusion_matrix, metrics_from_confusion,
+                      metric_vector)
 from .secagg import (MAX_SECAGG_CLIENTS, SECAGG_STREAM, secagg_id, secagg_mask, secagg_open,
                      secagg_quantize)
 
@@ -429,6 +430,24 @@ def heldout_metrics(history: dict) -> np.ndarray:
     return np.stack([metric_vector(metrics_from_confusion(c)) for c in cm])
 
 
+# ... and with auc=True (fedmi/ops/csrc/fl_common.h FL_AUC_MAX_ROWS: one workgroup's LDS holds a class's keys).
+AUC_MAX_ROWS = 32768
+
+
+def heldout_auc_score(history: dict) -> np.ndarray:
+    """``[rounds_run]`` held-out ROC AUC of the global model, round by round, from
+    ``history()["heldout_auc"]``: class 1's for two classes (scikit-learn's binary convention), else the
+    unweighted mean over the classes whose AUC is defined (NaN where none is)."""
+    if "heldout_auc" not in history:
+        raise KeyError("history has no held-out AUC rows: call set_heldout(X, y, auc=True) before the rounds")
+    a = np.asarray(history["heldout_auc"], dtype=np.float64)
+    if a.shape[1] == 2:
+        return a[:, 1].copy()
+    ok = ~np.isnan(a)
+    with np.errstate(invalid="ignore"):
+        return np.where(ok.any(1), np.where(ok, a, 0.0).sum(1) / np.maximum(ok.sum(1), 1), np.nan)
+
+
 def _softmax_ce_rows(z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """Per-row softmax cross-entropy lse(z) - z[y] in the logits' dtype."""
     return torch.logsumexp(z, 1) - z.gather(1, y.view(-1, 1)).squeeze(1)
@@ -441,13 +460,22 @@ class _History:
     ho_loss = None
     ho_best_round = -1
     ho_n = 0
+    # ... with auc=True: the doubled Mann-Whitney counts [max_rounds, C] and the set's positives per class
+    ho_u2 = None
+    ho_pos = None
 
-    def enable_heldout(self, n_classes: int, n_rows: int) -> None:
+    def enable_heldout(self, n_classes: int, n_rows: int, auc_pos=None) -> None:
         if self.ho_cm is None:
             mr = len(self.loss)
             self.ho_cm = np.zeros((mr, n_classes, n_classes), dtype=np.int64)
             self.ho_loss = np.zeros(mr, dtype=np.float32)
         self.ho_n = int(n_rows)
+        if auc_pos is None:
+            self.ho_u2 = self.ho_pos = None
+        else:
+            if self.ho_u2 is None:
+                self.ho_u2 = np.zeros((len(self.loss), n_classes), dtype=np.int64)
+            self.ho_pos = np.asarray(auc_pos, dtype=np.int64)
 
     def __init__(self, max_rounds: int, world: int, dp: bool = False, compress: bool = False,
                  secagg: bool = False, screen: bool = False):
@@ -489,6 +517,9 @@ class _History:
             out["heldout_loss_sum"] = self.ho_loss[:n].copy()
             out["heldout_loss"] = self.ho_loss[:n].astype(np.float64) / float(max(self.ho_n, 1))
             out["heldout_best_round"] = int(self.ho_best_round)
+        if self.ho_u2 is not None:
+            out["heldout_auc_u2"] = self.ho_u2[:n].copy()
+            out["heldout_auc"] = auc_from_u2(self.ho_u2[:n], self.ho_pos[None, :], self.ho_n - self.ho_pos[None, :])
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -589,6 +620,7 @@ class RoundEngineBase:
             self.compress_q_len = lowrank_layers(self.dims, cfg.compress_rank)["q_len"]
             self._compress_q0 = lowrank_q0(self.dims, cfg.compress_rank, cfg.compress_seed)
         self.heldout = False     # set_heldout: the global model is scored on a held-out set every round
+        self.heldout_auc = False  # ... and its rows ranked per class (auc=True)
         self.keep_best = False   # ... and the model of the round with the smallest held-out loss is kept
         assert init_flat.shape == (self.P,)
         if self.dp:
@@ -700,7 +732,7 @@ class RoundEngineBase:
         raise NotImplementedError
 
     # -- held-out scoring of the global model, inference --
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
         """Score the round's GLOBAL (aggregated, post-server-step) model on the held-out rows ``(X, y)``
         at the end of every live round: ``history()`` gains ``heldout_cm`` ``[rounds_run, C, C]`` (int64),
         ``heldout_loss`` ``[rounds_run]`` (mean softmax cross-entropy: the fp32 sum / n in float64; the
@@ -708,11 +740,16 @@ class RoundEngineBase:
         smallest loss sum under a plain ``<``: NaN never wins, ties keep the earlier round; -1: none).
         ``keep_best``: that round's model is kept (:meth:`best_flat`).  Call it before the first round or
         between ``run()`` calls (rounds run before it have all-zero rows).  The local metrics, the
-        early-stop rule and every weight are untouched.  The data is not config: it is not saved, a
+        early-stop rule and every weight are untouched.  ``auc``: every live round also ranks the rows by
+        each class's fp32 probability (``predict_proba(X, "global")``'s bits; NaN ranks above 1.0) and
+        ``history()`` gains ``heldout_auc_u2`` ``[rounds_run, C]`` (int64: over (row i of the class, row j
+        of another) the sum of ``2 [s_j < s_i] + [s_j == s_i]``, an exact integer) and ``heldout_auc``
+        (float64 ``U2 / (2 P N)``, NaN for a class without positives or negatives; one number per round:
+        :func:`heldout_auc_score`); at most ``AUC_MAX_ROWS`` rows then.  The data is not config: it is not saved, a
         resumed engine is given its set again before the state is loaded."""
         raise NotImplementedError
 
-    def _check_heldout(self, X, y):
+    def _check_heldout(self, X, y, auc: bool = False):
         X = np.ascontiguousarray(np.asarray(X), dtype=np.float32)
         y = np.asarray(y)
         if X.ndim != 2 or X.shape[1] != self.dims[0]:
@@ -722,6 +759,9 @@ class RoundEngineBase:
             raise ValueError(f"held-out y must be [{n}], got {tuple(y.shape)}")
         if not 1 <= n <= HELDOUT_MAX_ROWS:
             raise ValueError(f"held-out set: 1 .. {HELDOUT_MAX_ROWS} rows, got {n}")
+        if auc and n > AUC_MAX_ROWS:
+            raise ValueError(f"held-out set with auc=True: at most {AUC_MAX_ROWS} rows (a class's keys are "
+                             f"sorted inside one workgroup), got {n}; auc=False takes up to {HELDOUT_MAX_ROWS}")
         if not np.issubdtype(y.dtype, np.integer):
             raise ValueError(f"held-out labels must be integers, got dtype {y.dtype}")
         if int(y.min()) < 0 or int(y.max()) >= self.n_classes:
@@ -758,7 +798,7 @@ class RoundEngineBase:
         if not self.heldout:
             return {}
         return {"heldout": {"best_round": int(self.hist.ho_best_round), "best_loss_sum": float(self._ho_best_sum()),
-                            "best_flat": best_flat}}
+                            "best_flat": best_flat, **({"auc": True} if self.heldout_auc else {})}}
 
     def _heldout_state_in(self, st: dict):
         """The held-out part of a portable state for this engine, or None without held-out scoring; a
@@ -768,6 +808,10 @@ class RoundEngineBase:
             raise ValueError("checkpoint and engine disagree on held-out scoring: the state "
                              + ("carries" if has else "has no") + " held-out rows, the engine "
                              + ("scores a held-out set" if self.heldout else "has none (set_heldout)"))
+        if has and bool(st["heldout"].get("auc")) != bool(self.heldout_auc):
+            raise ValueError("checkpoint and engine disagree on held-out AUC: the state "
+                             + ("carries" if st["heldout"].get("auc") else "has no") + " heldout_auc_u2 rows, the "
+                             "engine " + ("ranks (set_heldout(auc=True))" if self.heldout_auc else "does not (auc=False)"))
         return st["heldout"] if has else None
 
     def _allreduce_scalar(self, x: float) -> float:
@@ -826,6 +870,8 @@ class RoundEngineBase:
                 self.hist.ho_cm[:n] = np.asarray(h["heldout_cm"], dtype=np.int64).reshape(n, C, C)
                 self.hist.ho_loss[:n] = np.asarray(h["heldout_loss_sum"], dtype=np.float32).reshape(n)
             self.hist.ho_best_round = int(h.get("heldout_best_round", -1))
+            if self.hist.ho_u2 is not None and n and "heldout_auc_u2" in h:
+                self.hist.ho_u2[:n] = np.asarray(h["heldout_auc_u2"], dtype=np.int64).reshape(n, C)
 
     def _load_dp_seed(self, st: dict) -> None:
         """A resumed DP engine continues the checkpoint's noise stream (a private seed drawn at
@@ -988,11 +1034,12 @@ class TorchRoundEngine(RoundEngineBase):
         self.stopper = EarlyStopper(cfg.patience, cfg.tolerance, cfg.rtol, enabled=cfg.early_stop)
 
     # -- held-out scoring (the HIP engine's definitions in torch fp32: its own oracle, not bit-equal) --
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
-        X, y = self._check_heldout(X, y)
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
+        X, y = self._check_heldout(X, y, auc)
         self.ho_X = torch.as_tensor(X, device=self.device)
         self.ho_y = torch.as_tensor(y, dtype=torch.long, device=self.device)
-        self.hist.enable_heldout(self.n_classes, len(X))
+        self.hist.enable_heldout(self.n_classes, len(X), np.bincount(y, minlength=self.n_classes) if auc else None)
+        self.heldout_auc = bool(auc)
         if not self.heldout:
             self._ho_best = np.float32(np.inf)
             self._ho_best_flat = None
@@ -1009,6 +1056,10 @@ class TorchRoundEngine(RoundEngineBase):
             z = self.model(self.ho_X).to(torch.float32)
             _, pred = torch.max(z, 1)
             loss = np.float32(_softmax_ce_rows(z, self.ho_y).sum().item())
+            if self.heldout_auc:   # predict_proba's expression on the same logits
+                proba = torch.softmax(z, 1).cpu().numpy().astype(np.float32)
+                yv = self.ho_y.cpu().numpy()
+                self.hist.ho_u2[r] = [auc_u2_model(proba[:, c], yv == c) for c in range(self.n_classes)]
         self.hist.ho_cm[r] = confusion_matrix(self.ho_y.cpu().numpy(), pred.cpu().numpy(), self.n_classes)
         self.hist.ho_loss[r] = loss
         if loss < self._ho_best:    # plain <: NaN never wins, ties keep the earlier round
@@ -1885,10 +1936,10 @@ class HipRoundEngine(RoundEngineBase):
             self.engine.phase(r, 3, self._stream(), None)
 
     # -- held-out scoring of the global model (fedmi/ops/csrc/fl_heldout.hip), inference --
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
         if self._packed:
             raise ValueError("trial packing (comm_buffers) does not run held-out scoring (set_heldout)")
-        X, y = self._check_heldout(X, y)
+        X, y = self._check_heldout(X, y, auc)
         self.stream.synchronize()
         dev, C, mr = self.device, self.n_classes, int(self.cfg.max_rounds)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -1902,13 +1953,23 @@ class HipRoundEngine(RoundEngineBase):
             # {best loss sum (+inf), best round (-1)} as two words, and the best round's image
             self.ho_best = torch.as_tensor(np.array([0x7F800000, -1], np.int32), device=dev)
             self.ho_best_image = torch.zeros(self.Pimg, dtype=torch.float32, device=dev)
-        self.hist.enable_heldout(C, len(X))
+        self.hist.enable_heldout(C, len(X), np.bincount(y, minlength=C) if auc else None)
+        if auc:
+            self.ho_keys = torch.zeros(C * len(X), **i32)   # [C][n] uint32, rewritten by every live round
+            if getattr(self, "ho_u2", None) is None:
+                self.ho_u2 = torch.zeros(mr * C, dtype=torch.int64, device=dev)
+        else:
+            self.ho_keys = self.ho_u2 = None
         torch.cuda.current_stream(dev).synchronize()
         # (the fold tracks the best round whether or not its image is kept: history()["heldout_best_round"])
         self.engine.set_heldout(self.ho_X.data_ptr(), self.ho_y.data_ptr(), len(X), self.ho_scratch.data_ptr(),
                                 self.ho_cm.data_ptr(), self.ho_loss.data_ptr(), self.ho_best_image.data_ptr(),
                                 self.ho_best.data_ptr(), True)
-        self.heldout, self.keep_best = True, bool(keep_best)
+        self.engine.set_heldout_auc(self.ho_keys.data_ptr() if auc else 0, self.ho_u2.data_ptr() if auc else 0)
+        self.layout.pop("heldout_auc", None)
+        if auc:
+            self.layout["heldout_auc"] = {"max_rows": AUC_MAX_ROWS, "launches": 2}
+        self.heldout, self.keep_best, self.heldout_auc = True, bool(keep_best), bool(auc)
         self._graph_ready = False   # the native engine dropped its graphs, as for set_debug
         self._mirror = None         # the streaming mirror gains the held-out buffers
 
@@ -1924,12 +1985,14 @@ class HipRoundEngine(RoundEngineBase):
         self.stream.synchronize()
         return self._ho_best_words()[0]
 
-    def _read_heldout(self, n: int, cm, loss, best) -> None:
+    def _read_heldout(self, n: int, cm, loss, best, u2=None) -> None:
         """Rows [0, n) and the best round from (device or pinned-host) copies of the held-out buffers."""
         C = self.n_classes
         if n:
             self.hist.ho_cm[:n] = cm[:n * C * C].cpu().numpy().reshape(n, C, C)
             self.hist.ho_loss[:n] = loss[:n].cpu().numpy()
+            if self.heldout_auc:
+                self.hist.ho_u2[:n] = u2[:n * C].cpu().numpy().reshape(n, C)
         self.hist.ho_best_round = int(best.cpu().numpy()[1])
 
     def best_flat(self) -> np.ndarray:
@@ -2017,7 +2080,7 @@ class HipRoundEngine(RoundEngineBase):
         :meth:`profile`, which runs classic phases): the native engine issues them eagerly with
         a hipEvent after every launch behind a gate kernel (FLEngine::trace), so the kernels
         run back to back.  Returns mean us per round by kernel kind (``train``, ``adam``,
-        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``compress``, ``server``, ``heldout``), ``round`` and launch counts.  Each
+        ``eval``, ``pack``, ``allreduce``, ``eval_fedavg``, ``dp``, ``compress``, ``server``, ``heldout``, ``heldout_auc``), ``round`` and launch counts.  Each
         interval carries the eager launch + event marker cost: measured on MI355X (bench N = 1,
         profiles/kernel_trace_r5.log) ~1.5 us per kernel over the rocprofv3 kernel durations
         (markers without the system-scope fence; ~3.2 us with it).
@@ -2220,6 +2283,8 @@ class HipRoundEngine(RoundEngineBase):
                         m["ho_cm"].copy_(self.ho_cm, non_blocking=True)
                         m["ho_loss"].copy_(self.ho_loss, non_blocking=True)
                         m["ho_best"].copy_(self.ho_best, non_blocking=True)
+                        if self.heldout_auc:
+                            m["ho_u2"].copy_(self.ho_u2, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 new = (ev, slot, desc)
@@ -2258,7 +2323,8 @@ class HipRoundEngine(RoundEngineBase):
                              **({"clamp": mk(self.sa_clamp)} if self.secagg else {}),
                              **({"screen": mk(self.screen_hist)} if self.screen else {}),
                              **({"ho_cm": mk(self.ho_cm), "ho_loss": mk(self.ho_loss), "ho_best": mk(self.ho_best)}
-                                if self.heldout else {})}
+                                if self.heldout else {}),
+                             **({"ho_u2": mk(self.ho_u2)} if self.heldout_auc else {})}
                             for _ in range(2)]
         return self._mirror
 
@@ -2279,7 +2345,7 @@ class HipRoundEngine(RoundEngineBase):
             if self.screen:
                 self.hist.screen[:n] = m["screen"][:n].numpy().view(np.uint64)
         if self.heldout:
-            self._read_heldout(n, m["ho_cm"], m["ho_loss"], m["ho_best"])
+            self._read_heldout(n, m["ho_cm"], m["ho_loss"], m["ho_best"], m.get("ho_u2"))
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -2315,7 +2381,7 @@ class HipRoundEngine(RoundEngineBase):
             if self.screen:
                 self.hist.screen[:n] = self.screen_hist[:n].cpu().numpy().view(np.uint64)
         if self.heldout:
-            self._read_heldout(n, self.ho_cm, self.ho_loss, self.ho_best)
+            self._read_heldout(n, self.ho_cm, self.ho_loss, self.ho_best, self.ho_u2)
         if st["stopped"]:
             self.hist.stop_round = int(st["stop_round"])
             self.hist.stop_trigger = int(st["stop_round"]) - 1
@@ -2462,6 +2528,10 @@ class HipRoundEngine(RoundEngineBase):
                     self.ho_cm[:n * C * C].copy_(torch.as_tensor(self.hist.ho_cm[:n].reshape(-1).astype(np.int32),
                                                                  device=dev))
                     self.ho_loss[:n].copy_(torch.as_tensor(self.hist.ho_loss[:n], device=dev))
+                if self.heldout_auc:
+                    self.ho_u2.zero_()
+                    if n:
+                        self.ho_u2[:n * C].copy_(torch.as_tensor(self.hist.ho_u2[:n].reshape(-1), device=dev))
                 words = np.array([np.float32(ho["best_loss_sum"]).view(np.int32), int(self.hist.ho_best_round)], np.int32)
                 if ho.get("best_flat") is not None:
                     self.ho_best_image.copy_(img(ho["best_flat"]))

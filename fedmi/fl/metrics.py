@@ -68,3 +68,41 @@ def pooled(cms: Sequence[np.ndarray]) -> Dict[str, float]:
 def format_metrics(m: Dict[str, float]) -> str:
     return (f"[accuracy: {m['accuracy']:.4f}, precision: {m['precision']:.4f}, "
             f"recall: {m['recall']:.4f}, f1: {m['f1']:.4f}]")
+
+
+# ---- held-out ROC AUC as an exact integer (fedmi/ops/csrc/fl_auc.hip ranks the same keys on the device) ----
+AUC_NAN_BITS = 0x3F800001   # a NaN probability ranks as the fp32 value just above 1.0
+
+
+def auc_keys(proba_column_fp32, pos_mask) -> np.ndarray:
+    """uint32 keys ``(bits(s) << 1) | positive`` of one class's fp32 probabilities ``s`` (in [0, 1] or
+    NaN): their unsigned order is the order by probability, a tie group's negatives ahead of its positives."""
+    s = np.ascontiguousarray(proba_column_fp32, dtype=np.float32).reshape(-1)
+    pos = np.asarray(pos_mask, dtype=bool).reshape(-1)
+    if s.shape != pos.shape:
+        raise ValueError(f"auc_keys: {s.shape[0]} probabilities, {pos.shape[0]} labels")
+    bits = np.where(np.isnan(s), np.uint32(AUC_NAN_BITS), s.view(np.uint32)).astype(np.uint32)
+    return (bits << np.uint32(1)) | pos.astype(np.uint32)
+
+
+def auc_u2_from_keys(keys) -> int:
+    """The doubled Mann-Whitney count of a key array: over (positive i, negative j) the sum of
+    ``2 [s_j < s_i] + [s_j == s_i]``.  A positive's key is odd and its tied negatives' key is the even one
+    below it, so the count is (negatives below the key) + (negatives below the key - 1)."""
+    keys = np.asarray(keys, dtype=np.uint32).astype(np.int64)
+    neg = np.sort(keys[(keys & 1) == 0])
+    pos = keys[(keys & 1) == 1]
+    return int(np.searchsorted(neg, pos, "left").sum() + np.searchsorted(neg, pos - 1, "left").sum())
+
+
+def auc_u2_model(proba_column_fp32, pos_mask) -> int:
+    """``U2`` of one class: ``auc_u2_from_keys(auc_keys(...))``; ``AUC = U2 / (2 P N)`` (:func:`auc_from_u2`)."""
+    return auc_u2_from_keys(auc_keys(proba_column_fp32, pos_mask))
+
+
+def auc_from_u2(u2, n_pos, n_neg) -> np.ndarray:
+    """float64 ``U2 / (2 P N)``, elementwise; NaN where a class has no positive or no negative row."""
+    u2, p, n = (np.asarray(a, dtype=np.float64) for a in (u2, n_pos, n_neg))
+    den = 2.0 * p * n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, u2 / np.where(den > 0, den, 1.0), np.nan)

@@ -76,7 +76,7 @@ class ClientGroup:
                  seed: int = 0, alpha: float = 0.5, device=None, n_classes: Optional[int] = None,
                  tamper: Optional[Callable[[int, List[torch.Tensor]], None]] = None,
                  wire: Optional[Callable[[int, List[torch.Tensor]], None]] = None,
-                 heldout=None, keep_best: bool = False):
+                 heldout=None, keep_best: bool = False, heldout_auc: bool = False):
         """``heldout=(X, y)``: the lead client scores the round's global model on these rows after the
         aggregation and the server steps of every round (``set_heldout``): :meth:`history` carries the
         held-out keys, ``keep_best`` keeps the best round's model for :meth:`best_flat`.
@@ -150,7 +150,7 @@ class ClientGroup:
                 e.stream = self.stream   # one stream: every client's kernels and the sums in order
         if heldout is not None:
             Xv, yv = heldout
-            self.clients[0].set_heldout(Xv, yv, keep_best=keep_best)   # only the lead holds the set
+            self.clients[0].set_heldout(Xv, yv, keep_best=keep_best, auc=heldout_auc)   # only the lead holds (and ranks) the set
         self.rounds = 0
 
     # ---- rounds ----

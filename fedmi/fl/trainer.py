@@ -187,11 +187,11 @@ class FederatedMLPLearning:
         return metrics_from_confusion(cm)
 
     # ---- held-out scoring of the global model, inference (fedmi/fl/engine.py set_heldout) ----
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
         """Score the round's global model on the held-out rows ``(X, y)`` at the end of every round
         (``history()`` gains the ``heldout_*`` keys); ``keep_best`` keeps the best round's model
         (:meth:`best_weights`).  ``train_and_evaluate``'s return value and console output are unchanged."""
-        self.engine.set_heldout(X, y, keep_best=keep_best)
+        self.engine.set_heldout(X, y, keep_best=keep_best, auc=auc)
 
     def predict_proba(self, X, which: str = "global") -> np.ndarray:
         """``[n, C]`` float32 class probabilities of the global (or ``which="local"``) model."""

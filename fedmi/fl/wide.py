@@ -514,7 +514,7 @@ class WideClient:
         self.evaluate_shard()
         return float(self.metrics()["accuracy"])
 
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
         """Refused: the wide path's layered kernels have no held-out scoring (the round engines do)."""
         raise ValueError("WideClient does not run held-out scoring (set_heldout): use a round engine "
                          "(HipRoundEngine / TorchRoundEngine / ClientGroup)")

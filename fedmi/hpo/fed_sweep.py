@@ -152,7 +152,7 @@ class FedTrialGroup:
             raise ValueError(f"unknown backend {backend!r}")
         self.rounds_issued = 0
 
-    def set_heldout(self, X, y, keep_best: bool = False) -> None:
+    def set_heldout(self, X, y, keep_best: bool = False, auc: bool = False) -> None:
         """Refused: the trials of a group share launches, a held-out record per trial is not batched."""
         raise ValueError("fed_sweep does not run held-out scoring (set_heldout): score the chosen trial's "
                          "model afterwards (evaluate_global / predict)")

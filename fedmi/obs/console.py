@@ -75,6 +75,10 @@ class JsonlWriter:
                 ho = metrics_from_confusion(hist["heldout_cm"][r])
                 norm.update({f"heldout_{k}": float(ho[k]) for k in METRIC_NAMES})
                 norm["heldout_loss"] = float(hist["heldout_loss"][r])
+            # (... with auc: its ROC AUC on that set, heldout_auc_score's one number)
+            if "heldout_auc" in hist:
+                from ..fl.engine import heldout_auc_score
+                norm["heldout_auc"] = float(heldout_auc_score(hist)[r])
             self.write(round=r + 1, **{k: float(hist["global"][r][i]) for i, k in enumerate(METRIC_NAMES)},
                        per_rank=hist["per_rank"][r].tolist(), loss=float(hist["loss"][r]), **norm, **extra)
 

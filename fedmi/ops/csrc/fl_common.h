@@ -513,6 +513,22 @@ struct FLHeldout {
     float* best;         // keep_best: {best loss sum (starts at +inf), best round's index as int bits (starts at -1)}
 };
 
+// Held-out ROC AUC (fl_auc.hip): parameters of the key and rank launches that follow a round's held-out
+// pair when AUC is on, passed to those kernels alone, as FLHeldout is.  Every buffer is caller-owned.  A
+// live round r leaves hist_u2[r][c] = the doubled one-vs-rest Mann-Whitney count of class c on the n
+// held-out rows: over (i with y == c, j with y != c) the sum of 2 [s_j < s_i] + [s_j == s_i], s the fp32
+// softmax probability of class c under the round's output image (NaN ranks above every real value).
+#define FL_AUC_THREADS 1024
+#define FL_AUC_MAX_ROWS 32768  // the rank kernel sorts a class's keys inside one workgroup's LDS
+struct FLAuc {
+    const float* X;               // the held-out set's rows and labels (FLHeldout::X, ::y)
+    const int* y;
+    int n;                        // 1 .. FL_AUC_MAX_ROWS
+    int max_rounds;               // rows of hist_u2; rounds past it are not live
+    uint32_t* keys;               // [C][n]: (bits of s << 1) | (y == c), rewritten every live round
+    unsigned long long* hist_u2;  // [max_rounds][C]
+};
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -663,6 +679,16 @@ hipError_t fl_launch_heldout(const MLPDesc& d, int R, const FLHeldout& p, const 
                              hipStream_t s);
 // ... and its row mode: the fp32 softmax of `params`' logits on rows [0, n) of X into proba[n][C] and / or
 // their first-maximum argmax into pred[n] (either may be null, not both); ungated.
+// (fl_auc.hip) the key launch (grid and forward of the held-out row launch; d and R as for
+// fl_launch_heldout) and the rank launch (one workgroup per class) of the round whose state is `st`.
+// A round issues fl_launch_auc_keys, then fl_launch_auc_rank(p.keys, p.n, C, p.max_rounds, st, p.hist_u2).
+// fl_launch_auc_rank with st == nullptr: ungated, out[c] = U2 of keys[c][0..n) for any key pattern.
+// fl_set_lds_limit_auc: before the first launch (forward_bytes: the key kernels' dynamic LDS, 0: rank only).
+hipError_t fl_set_lds_limit_auc(size_t forward_bytes);
+hipError_t fl_launch_auc_keys(const MLPDesc& d, int R, const FLAuc& p, const float* image, const FLState* st,
+                              hipStream_t s);
+hipError_t fl_launch_auc_rank(const uint32_t* keys, int n, int C, int max_rounds, const FLState* st,
+                              unsigned long long* out, hipStream_t s);
 hipError_t fl_launch_heldout_predict(const MLPDesc& d, int R, const float* X, int n, const float* params,
                                      float* proba, int* pred, hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When

@@ -795,10 +795,35 @@ class FLEngine {
             prepare_heldout();
         }
         ho_ = h;
+        std::memset(&au_, 0, sizeof(au_));  // (AUC belongs to the set it was switched on for: set_heldout_auc)
         tr_.heldout_on = X != 0;
         refresh_undo();
         drop_graph();
     }
+    // Held-out ROC AUC (fl_auc.hip): the key and the rank launch follow the held-out pair of every round
+    // that has one; `keys` = 0 turns them off.  keys: [C][n] uint32, hist_u2: [max_rounds][C] uint64,
+    // caller-owned.  Launches change, so captured graphs are dropped.
+    void set_heldout_auc(uintptr_t keys, uintptr_t hist_u2) {
+        FLAuc a;
+        std::memset(&a, 0, sizeof(a));
+        if (keys != 0) {
+            if (!tr_.heldout_on) throw std::runtime_error("set_heldout_auc: no held-out set (set_heldout)");
+            if (ho_.n > FL_AUC_MAX_ROWS)
+                throw std::runtime_error("set_heldout_auc: at most " + std::to_string(FL_AUC_MAX_ROWS) +
+                                         " held-out rows with auc, got " + std::to_string(ho_.n));
+            if (!hist_u2) throw std::runtime_error("set_heldout_auc: missing buffers");
+            a.X = ho_.X;
+            a.y = ho_.y;
+            a.n = ho_.n;
+            a.max_rounds = c_.max_rounds;
+            a.keys = as_ptr<uint32_t>(keys);
+            a.hist_u2 = as_ptr<unsigned long long>(hist_u2);
+            HIP_CHECK(fl_set_lds_limit_auc((size_t)dh_.lds_floats * 4));
+        }
+        au_ = a;
+        drop_graph();
+    }
+    bool heldout_auc() const { return au_.keys != nullptr; }
     bool heldout() const { return tr_.heldout_on; }
     int heldout_rows_per_block() const { return ho_R(); }
 
@@ -871,9 +896,10 @@ class FLEngine {
         }
         tev_ = nullptr;
         HIP_CHECK(hipStreamSynchronize(s));
-        constexpr int TR_N = FLLaunchRec::N_KINDS;  // events are tagged with the launch kind
+        constexpr int TR_N = FLLaunchRec::N_KINDS + 2;  // events are tagged with the launch kind (kTraceAuc: the AUC launches)
         static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
-                                          "server", "finalize", "compress", "heldout"};
+                                          "server", "finalize", "compress", "heldout", "heldout_auc_keys",
+                                          "heldout_auc_rank"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -892,6 +918,12 @@ class FLEngine {
                 out[names[k]] = us[k] / n;
                 launches[names[k]] = cnt[k];
             }
+        if (cnt[kTraceAuc]) {  // the two AUC launches under one key, as "heldout" holds its pair
+            out["heldout_auc"] = (us[kTraceAuc] + us[kTraceAuc + 1]) / n;
+            launches["heldout_auc"] = cnt[kTraceAuc] + cnt[kTraceAuc + 1];
+            launches.attr("pop")("heldout_auc_keys");
+            launches.attr("pop")("heldout_auc_rank");
+        }
         out["round"] = 1e3 * total / n;
         out["launches"] = launches;
         out["rounds"] = n;
@@ -1108,6 +1140,14 @@ class FLEngine {
                 break;
             case FLLaunchRec::HELDOUT:  // the row launch, then the fold launch
                 HIP_CHECK(fl_launch_heldout(dh_, ho_R(), ho_, F(0), S(1), s));
+                if (au_.keys != nullptr) {  // ... then the key launch and the rank launch (a trace key of their own)
+                    mark(m.kind, s);
+                    HIP_CHECK(fl_launch_auc_keys(dh_, ho_R(), au_, F(0), S(1), s));
+                    mark(kTraceAuc, s);
+                    HIP_CHECK(fl_launch_auc_rank(au_.keys, au_.n, dh_.dim[dh_.L], au_.max_rounds, S(1), au_.hist_u2, s));
+                    mark(kTraceAuc + 1, s);
+                    return;
+                }
                 break;
             case FLLaunchRec::FINALIZE:
                 HIP_CHECK(fl_launch_finalize(d_, c_, b_, F(0), S(1), S(2), s, i[0],
@@ -1180,6 +1220,8 @@ class FLEngine {
     bool compress_random() const { return cp_.kind == FL_COMPRESS_QSGD || cp_.kind == FL_COMPRESS_RANDK; }
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLHeldout ho_ = {};        // held-out scoring: fl_heldout row + fold launches at the end of every round
+    FLAuc au_ = {};            // ... and, keys != nullptr, fl_auc's key + rank launches behind them
+    static constexpr int kTraceAuc = FLLaunchRec::N_KINDS;  // trace() tags of those two: kTraceAuc, kTraceAuc + 1
     MLPDesc dh_ = {};          // ... the fp32 forward layout at its rows per workgroup (prepare_heldout)
     // rows per workgroup of the held-out kernels: the engine's, at most 32 (the fp32 forward's tiles)
     int ho_R() const { return c_.R > 32 ? 32 : c_.R; }
@@ -1709,6 +1751,8 @@ PYBIND11_MODULE(_fedmi_hip, m) {
         .def("set_heldout", &FLEngine::set_heldout, py::arg("X"), py::arg("y"), py::arg("n"), py::arg("scratch"),
              py::arg("hist_cm"), py::arg("hist_loss"), py::arg("best_image"), py::arg("best"), py::arg("keep_best"))
         .def_property_readonly("heldout", &FLEngine::heldout)
+        .def("set_heldout_auc", &FLEngine::set_heldout_auc, py::arg("keys"), py::arg("hist_u2"))
+        .def_property_readonly("heldout_auc", &FLEngine::heldout_auc)
         .def_property_readonly("heldout_rows_per_block", &FLEngine::heldout_rows_per_block)
         .def("predict", &FLEngine::predict, py::arg("X"), py::arg("n"), py::arg("params"), py::arg("proba"),
              py::arg("pred"), py::arg("stream"))
@@ -1779,6 +1823,13 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.attr("RANDK_STREAM") = (unsigned)FL_RANDK_STREAM;
     m.attr("ROBUST_MAX_K") = (int)FL_ROBUST_MAX_K;
     m.attr("HELDOUT_MAX_ROWS") = (int)FL_HELDOUT_MAX_ROWS;
+    // the rank launch of fl_auc.hip alone, ungated, on caller-owned buffers: out[c] = U2 of keys[c][0..n)
+    m.def("auc_rank", [](uintptr_t keys, int n, int C, uintptr_t out, uintptr_t stream) {
+        HIP_CHECK(fl_set_lds_limit_auc(0));
+        HIP_CHECK(fl_launch_auc_rank(as_ptr<const uint32_t>(keys), n, C, 0, nullptr,
+                                     as_ptr<unsigned long long>(out), as_stream(stream)));
+    }, py::arg("keys"), py::arg("n"), py::arg("C"), py::arg("out"), py::arg("stream"));
+    m.attr("AUC_MAX_ROWS") = (int)FL_AUC_MAX_ROWS;
     m.def("device_info", &device_info);
     m.attr("STATE_BYTES") = (int)sizeof(FLState);
     // floats per slab row an engine of this model may need at R rows per workgroup: the dense row, or the
