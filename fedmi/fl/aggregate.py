@@ -54,6 +54,18 @@ clients ``S``:
 parameter images, with the distances added in the kernel's one order (:func:`geomed_block_sums`);
 :func:`geomed_torch` is the rule in the tensor's dtype with torch's own summation order: what the torch
 engines run in fp32, and the float64 oracle in float64.
+
+Centered clipping (``aggregator="cclip"``; Karimireddy, He, Jaggi 2021, "Learning from History for Byzantine
+Robust Optimization") is the one rule with a memory: it starts from the previous aggregate -- the image ``x``
+the round trained from -- and moves towards every client by at most ``tau``, so a colluder at any distance has
+bounded pull and attacks that hide inside the honest spread of ONE round (ALIE, IPM) lose their lever.  It is
+the ``CENTERED_AGGREGATORS`` entry, id 4 in ``AGGREGATOR_NAMES``.  With ``T = cclip_iters``,
+``tau = float32(cclip_tau)`` and ``K_r`` sampled (kept) clients ``S``, from ``z_0 = x``, ``T`` times:
+``d_i = sum (v_i - z_l)^2`` over the real parameters; the clients with ``d_i < +inf`` are included;
+``c_i = tau / sqrt(d_i)`` where ``sqrt(d_i) > tau``, else 1; ``z_{l+1} = z_l + (sum c_i (v_i - z_l)) / K_r``,
+the sum in client order from ``+0``, the divisor ``K_r`` whoever is included; nobody included: ``z`` stays.
+:func:`cclip_model` is the bit-exact fp32 model of the launches (``fedmi/ops/csrc/fl_cclip.hip``), with the
+geometric median's distance order; :func:`cclip_torch` the rule in the tensor's dtype.
 """
 from __future__ import annotations
 
@@ -69,18 +81,30 @@ AGGREGATORS = ("mean", "median", "trimmed_mean")
 # rules that iterate over whole models (several launches, scratch of their own); ids follow AGGREGATORS'
 ITERATIVE_AGGREGATORS = ("geomed",)
 ALL_AGGREGATORS = AGGREGATORS + ITERATIVE_AGGREGATORS
+# rules that iterate around a centre of their own (the image the round trained from)
+CENTERED_AGGREGATORS = ("cclip",)
+# every rule: what the validators accept, and the order of the engines' ``robust`` ids (cclip: 4)
+AGGREGATOR_NAMES = ALL_AGGREGATORS + CENTERED_AGGREGATORS
 MAX_ROBUST_CLIENTS = 64   # width of the per-round sampled-client mask (fl_common.h FL_ROBUST_MAX_K)
 SCREENS = ("none", "multi_krum")
 _SCREEN_THREADS = 256     # workgroup of the distance kernel (fl_screen.hip FL_SCREEN_THREADS)
 GEOMED_MAX_ITERS = 32     # fl_common.h FL_GEOMED_MAX_ITERS
 GEOMED_BLOCK = 256        # floats of the image per block of a distance sum (fl_common.h FL_GEOMED_THREADS)
 GEOMED_SLOT = 192         # floats of one iteration's record in the scratch (fl_common.h FL_GEOMED_SLOT)
+CCLIP_MAX_ITERS = 8       # fl_common.h FL_CCLIP_MAX_ITERS
+CCLIP_SLOT = 192          # floats of one iteration's record in the scratch (fl_common.h FL_CCLIP_SLOT)
 
 
 def geomed_scratch_floats(pimg: int, iters: int) -> int:
     """Floats of scratch the geomed launches need for an image of ``pimg`` floats (fl_common.h
     fl_geomed_scratch_floats): two sets of 64 distance partials per block, then ``iters`` records."""
     return 2 * ((int(pimg) + GEOMED_BLOCK - 1) // GEOMED_BLOCK) * MAX_ROBUST_CLIENTS + int(iters) * GEOMED_SLOT
+
+
+def cclip_scratch_floats(pimg: int, iters: int) -> int:
+    """Floats of scratch the cclip launches need for an image of ``pimg`` floats (fl_common.h
+    fl_cclip_scratch_floats): two sets of 64 distance partials per block of 256, then ``iters`` records."""
+    return 2 * ((int(pimg) + GEOMED_BLOCK - 1) // GEOMED_BLOCK) * MAX_ROBUST_CLIENTS + int(iters) * CCLIP_SLOT
 
 
 def trim_count(kind: str, beta: float, k_r: int) -> int:
@@ -118,8 +142,15 @@ class _AggLaunch:
         self._src = [table(s) for s in src]
         self._dst = self._src if dst is src else [table(s) for s in dst]
         self._clamp = table(clamps)
-        self._dist = self._keep = self._geomed = None
-        if ALL_AGGREGATORS[getattr(lead, "robust", 0)] == "geomed":
+        self._dist = self._keep = self._geomed = self._cclip = None
+        rule = AGGREGATOR_NAMES[getattr(lead, "robust", 0)]
+        if rule == "cclip":
+            # distance partials and the iterations' records (clip factors, distances, included mask) of the
+            # cclip launches; the centre, the other parity's image of the lead, is never a destination
+            self._cclip = torch.zeros(cclip_scratch_floats(lead.Pimg, int(lead.cfg.cclip_iters)),
+                                      dtype=torch.float32, device=lead.device)
+            self._dst_addrs = [[t.data_ptr() for t in ts] for ts in dst]
+        if rule == "geomed":
             # distance partials and the iterations' records (weights, distances, combined mask) of the geomed launches
             self._geomed = torch.zeros(geomed_scratch_floats(lead.Pimg, int(lead.cfg.geomed_iters)),
                                        dtype=torch.float32, device=lead.device)
@@ -155,6 +186,13 @@ class _AggLaunch:
             e.m.geomed_aggregate(e.dims, int(e.cfg.geomed_iters), float(e.cfg.geomed_nu), self._src[par].data_ptr(),
                                  self._k, self._dst[par].data_ptr(), self._n, *self._round(par),
                                  self._k * e.tail_stride, int(e.cfg.max_rounds), self._geomed.data_ptr(), stream, *keep)
+            return
+        if self._cclip is not None:
+            # centered clipping: cclip_iters + 1 launches (fl_cclip.hip) around the image the round trained from
+            e.m.cclip_aggregate(e.dims, int(e.cfg.cclip_iters), float(e.cfg.cclip_tau), self._src[par].data_ptr(),
+                                self._k, e.params[par ^ 1].data_ptr(), self._dst[par].data_ptr(), self._n,
+                                *self._round(par), self._k * e.tail_stride, int(e.cfg.max_rounds),
+                                self._cclip.data_ptr(), stream, *keep, dst_addrs=self._dst_addrs[par])
             return
         e.m.robust_aggregate(e.dims, e.robust, float(e.robust_beta), self._src[par].data_ptr(), self._k,
                              self._dst[par].data_ptr(), self._n, *self._round(par), self._k * e.tail_stride,
@@ -334,6 +372,96 @@ def geomed_model(stack, active: Sequence[bool], real, iters: int, nu: float, tra
                 z = acc / tot
             if records is not None:
                 records.append({"d": d, "b": eff_b.copy(), "mask": eff_mask})
+    return np.where(real, z, np.float32(0.0)).astype(np.float32)
+
+
+def _check_cclip(who: str, K: int, active: Sequence[bool], iters: int, tau: float):
+    act = [bool(a) for a in active]
+    if len(act) != K:
+        raise ValueError(f"{who}: {len(act)} mask entries for {K} clients")
+    if not any(act):
+        raise ValueError(f"{who}: needs at least one sampled client")
+    if not 1 <= int(iters) <= CCLIP_MAX_ITERS:
+        raise ValueError(f"{who}: iters must be in [1, {CCLIP_MAX_ITERS}], got {iters!r}")
+    tau32 = np.float32(tau)   # the kernels' radius is (float)cclip_tau
+    if not (np.isfinite(tau32) and tau32 > 0):
+        raise ValueError(f"{who}: tau must be finite and > 0 in fp32, got {tau!r}")
+    return act, tau32
+
+
+def cclip_torch(stack: torch.Tensor, active: Sequence[bool], x: torch.Tensor, iters: int, tau: float,
+                trace: Optional[list] = None) -> torch.Tensor:
+    """Centered clipping (Karimireddy et al. 2021) of the rows of ``stack`` [K, P] whose ``active`` entry is
+    true around ``x`` [P], in ``stack``'s dtype (float32: what the torch engines run; float64: the oracle):
+    ``iters`` times ``d_i = sum (v_i - z)^2`` in torch's own summation order, the clients with ``d_i < +inf``
+    pulling ``z`` by ``min(1, tau / sqrt(d_i)) (v_i - z)``, added in client order and divided by the number
+    of active clients; nobody at a finite distance: ``z`` stays.  ``trace``: a list that receives each
+    iteration's ``{"c", "d", "mask"}`` (clip factors and distances [K], included clients as mask bits)."""
+    if stack.dim() != 2 or stack.dtype not in (torch.float32, torch.float64):
+        raise ValueError("cclip_torch: needs a [K, P] float32 or float64 tensor")
+    K = int(stack.shape[0])
+    act, tau32 = _check_cclip("cclip_torch", K, active, iters, tau)
+    S = [i for i, a in enumerate(act) if a]
+    z = x.to(stack.dtype).reshape(-1).clone()
+    if z.shape[0] != stack.shape[1]:
+        raise ValueError("cclip_torch: x must have the clients' length")
+    radius = torch.tensor(float(tau32), dtype=stack.dtype, device=stack.device)
+    k_r = torch.tensor(float(len(S)), dtype=stack.dtype, device=stack.device)
+    for _ in range(int(iters)):
+        d = ((stack[S] - z[None]) ** 2).sum(1)
+        ok = (d < math.inf).tolist()
+        s = torch.sqrt(d)
+        c = torch.where(s > radius, radius / s, torch.ones_like(s))
+        if trace is not None:
+            cK, dK, okK = np.zeros(K), np.zeros(K), [False] * K
+            for j, i in enumerate(S):
+                cK[i], dK[i], okK[i] = (float(c[j]) if ok[j] else 0.0), (float(d[j]) if ok[j] else math.inf), ok[j]
+            trace.append({"c": cK, "d": dK, "mask": mask_bits(okK)})
+        if not any(ok):
+            continue   # (z stays, and so does every later iteration's distance)
+        g = torch.zeros_like(z)
+        for j, i in enumerate(S):
+            if ok[j]:   # selected, never multiplied by 0: an excluded row may hold NaN
+                g = g + c[j] * (stack[i] - z)
+        z = z + g / k_r
+    return z
+
+
+def cclip_model(stack, active: Sequence[bool], real, x, iters: int, tau: float, trace: Optional[list] = None) -> np.ndarray:
+    """What the ``fl_cclip`` launches write for the parameter images ``stack`` [K, Pimg] (fp32) around the
+    image ``x`` [Pimg], bit for bit: the image of the centered-clipping aggregate of the ``active`` clients,
+    padding (``real`` [Pimg] false) exact 0.  The rule is :func:`cclip_torch`'s with every operation one fp32
+    rounding and the distances added in the kernel's order (:func:`geomed_block_sums`; padding adds ``+0``
+    whatever it holds).  ``trace`` receives each iteration's scratch record as the kernel leaves it: ``c`` [K]
+    the clip factors (0: not included), ``d`` [K] the distances (``+inf`` for a sum that is not ``< +inf``, 0
+    for a client that is not active) and ``mask`` the included clients."""
+    a = np.ascontiguousarray(np.asarray(stack, np.float32))
+    real = np.asarray(real, bool).reshape(-1)
+    K, n = a.shape
+    z = np.array(np.asarray(x, np.float32).reshape(-1), np.float32)
+    if real.shape[0] != n or z.shape[0] != n:
+        raise ValueError("cclip_model: needs [K, Pimg] images, Pimg flags and a centre of Pimg floats")
+    act, tau32 = _check_cclip("cclip_model", K, active, iters, tau)
+    S = [i for i in range(K) if act[i]]
+    inf, one, k_r = np.float32(np.inf), np.float32(1.0), np.float32(len(S))
+    with np.errstate(all="ignore"):
+        for _ in range(int(iters)):
+            df = a[S] - z[None]
+            dS = geomed_block_sums(np.where(real[None], df * df, np.float32(0.0)))
+            d = np.zeros(K, np.float32)
+            d[S] = np.where(dS < inf, dS, inf)
+            ok = [i for i in S if d[i] < inf]
+            c = np.zeros(K, np.float32)
+            for i in ok:
+                s = np.sqrt(d[i])
+                c[i] = tau32 / s if s > tau32 else one
+            if trace is not None:
+                trace.append({"c": c, "d": d, "mask": mask_bits(i in ok for i in range(K))})
+            if ok:
+                g = np.zeros(n, np.float32)
+                for i in ok:
+                    g = g + c[i] * (a[i] - z)
+                z = z + g / k_r
     return np.where(real, z, np.float32(0.0)).astype(np.float32)
 
 

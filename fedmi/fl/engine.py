@@ -30,8 +30,9 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
-from .aggregate import (AGGREGATORS, ALL_AGGREGATORS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS, _AggLaunch,
-                        geomed_torch, mask_bits, pair_distances_torch, robust_aggregate_torch, screen_select)
+from .aggregate import (AGGREGATOR_NAMES, AGGREGATORS, CCLIP_MAX_ITERS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS,
+                        _AggLaunch, cclip_torch, geomed_torch, mask_bits, pair_distances_torch,
+                        robust_aggregate_torch, screen_select)
 from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
                      attack_torch)
 from .compress import (COMPRESSORS, LOWRANK_COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch,
@@ -155,10 +156,20 @@ class EngineConfig:
     # median, weights 1 / max(geomed_nu, distance); geomed_iters + 1 launches per round (fl_geomed.hip).
     # Composes as the median does; on a multi-rank HipRoundEngine over the host gather only
     # (gather_plane="xgmi" is refused: the one-shot select kernel cannot iterate).
+    # "cclip" = centered clipping (Karimireddy, He, Jaggi 2021): the one rule with a memory.  From the image x
+    # the round trained from -- the previous aggregate -- cclip_iters times z += (sum over the sampled clients
+    # of min(1, cclip_tau / ||v_i - z||) (v_i - z)) / K_r: every client, at whatever distance, moves the
+    # aggregate by at most cclip_tau / K_r per iteration, so colluders that hide inside one round's honest
+    # spread (attack="alie", "ipm") gain no lever.  No Byzantine count, no sorting; a client at a distance that
+    # is not finite is left out of that iteration.  cclip_iters + 1 launches per round (fl_cclip.hip), no
+    # state (x is the model).  Composes as geomed does, host gather only; every client starts from one
+    # common model, as with server_opt (the centre must be the same image on every replica from round 0).
     aggregator: str = "mean"
     trim_ratio: float = 0.1
     geomed_iters: int = 3
     geomed_nu: float = 1e-6
+    cclip_tau: float = 1.0
+    cclip_iters: int = 3
     # Update compression with error feedback (fedmi/fl/compress.py): every sampled client compresses
     # u = (local - x) + e (x: the image the round trained from, e: its residual) before the exchange and
     # contributes w (x + C(u)); what C drops stays in e (error_feedback=False: it is discarded).  "topk"
@@ -248,6 +259,10 @@ class EngineConfig:
         d = asdict(self)
         d["hidden"] = list(self.hidden)
         d["betas"] = list(self.betas)
+        if self.aggregator != "cclip":
+            # (another rule: a checkpoint's config record is what it was before the cclip fields existed)
+            for k in ("cclip_tau", "cclip_iters"):
+                del d[k]
         if self.attack == "none":
             # (off: a checkpoint's config record is what it was before the attack fields existed)
             for k in ("attack", "attack_clients", "attack_scale", "attack_z", "attack_seed"):
@@ -310,11 +325,20 @@ def server_opt_id(cfg: EngineConfig) -> int:
 
 
 def aggregator_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
-    """Validate the aggregation fields; the rule's index in ``ALL_AGGREGATORS`` (0 = the weighted mean).
+    """Validate the aggregation fields; the rule's index in ``AGGREGATOR_NAMES`` (0 = the weighted mean).
     ``world``: the federation's size when the caller knows it -- the aggregate of one client is the
     identity, so no combination is refused there."""
-    if not isinstance(cfg.aggregator, str) or cfg.aggregator not in ALL_AGGREGATORS:
-        raise ValueError(f"aggregator must be one of {ALL_AGGREGATORS}, got {cfg.aggregator!r}")
+    if not isinstance(cfg.aggregator, str) or cfg.aggregator not in AGGREGATOR_NAMES:
+        raise ValueError(f"aggregator must be one of {AGGREGATOR_NAMES}, got {cfg.aggregator!r}")
+    T = cfg.cclip_iters
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 1 <= int(T) <= CCLIP_MAX_ITERS:
+        raise ValueError(f"cclip_iters must be an integer in [1, {CCLIP_MAX_ITERS}], got {T!r}")
+    try:
+        tau = float(np.float32(cfg.cclip_tau)) if not isinstance(cfg.cclip_tau, bool) else math.nan
+    except (TypeError, ValueError):
+        tau = math.nan
+    if not (math.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"cclip_tau must be a finite number > 0 (in fp32), got {cfg.cclip_tau!r}")
     T = cfg.geomed_iters
     if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 1 <= int(T) <= GEOMED_MAX_ITERS:
         raise ValueError(f"geomed_iters must be an integer in [1, {GEOMED_MAX_ITERS}], got {T!r}")
@@ -330,13 +354,16 @@ def aggregator_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
         beta = math.nan
     if not (math.isfinite(beta) and 0.0 <= beta < 0.5):
         raise ValueError(f"trim_ratio must be a finite number in [0, 0.5), got {cfg.trim_ratio!r}")
-    kind = ALL_AGGREGATORS.index(cfg.aggregator)
+    kind = AGGREGATOR_NAMES.index(cfg.aggregator)
     if kind and float(cfg.dp_clip) > 0.0:
         raise ValueError(f"aggregator={cfg.aggregator!r} does not combine with differential privacy (dp_clip > 0): "
                          "the noise calibration assumes a weighted sum")
     if cfg.aggregator == "geomed" and cfg.gather_plane == "xgmi" and (world is None or int(world) > 1):
         raise ValueError("aggregator='geomed' does not run on gather_plane='xgmi': the one-shot select kernel "
                          "cannot iterate; use gather_plane='host'")
+    if cfg.aggregator == "cclip" and cfg.gather_plane == "xgmi" and (world is None or int(world) > 1):
+        raise ValueError("aggregator='cclip' does not run on gather_plane='xgmi': the one-shot select kernel "
+                         "cannot iterate and never holds the image the round trained from; use gather_plane='host'")
     return kind
 
 
@@ -375,9 +402,9 @@ def attack_stage(cfg: EngineConfig, world: Optional[int] = None) -> bool:
 
 
 def common_init(cfg: EngineConfig) -> bool:
-    """Every client starts from one model: a server optimizer and the attack stage both read the image a round
-    trained from, which must be the same on every replica from round 0 on."""
-    return cfg.server_opt != "none" or cfg.attack in DEVICE_ATTACKS
+    """Every client starts from one model: a server optimizer, the attack stage and centered clipping all read
+    the image a round trained from, which must be the same on every replica from round 0 on."""
+    return cfg.server_opt != "none" or cfg.attack in DEVICE_ATTACKS or cfg.aggregator == "cclip"
 
 
 GATHER_PLANES = ("host", "xgmi")
@@ -544,7 +571,7 @@ class RoundEngineBase:
         self.comm = comm
         self.world = comm.size if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
-        # index in ALL_AGGREGATORS, 0 = the weighted mean; the aggregate of one client is the identity
+        # index in AGGREGATOR_NAMES, 0 = the weighted mean; the aggregate of one client is the identity
         kind = aggregator_id(cfg, self.world)
         self.robust = kind if self.world > 1 else 0
         if self.robust and self.world > MAX_ROBUST_CLIENTS:
@@ -1101,7 +1128,7 @@ class TorchRoundEngine(RoundEngineBase):
     def step_train(self) -> None:
         r = self.rounds_issued
         self._active = self.rank in self.participants(r)
-        if self.dp or self.compress or self.attack_stage:
+        if self.dp or self.compress or self.attack_stage or AGGREGATOR_NAMES[self.robust] == "cclip":
             self._dp_input = self.model.flat.detach().cpu().clone()   # the image the round trains from
         if self._active:
             self._loss = self.train_one_epoch()
@@ -1290,8 +1317,11 @@ class TorchRoundEngine(RoundEngineBase):
             active = screen_select(pair_distances_torch(stack, active), active, int(self.cfg.screen_byzantine),
                                    self.cfg.screen_keep)
             self.hist.screen[self.rounds_issued] = mask_bits(active)
-        if ALL_AGGREGATORS[self.robust] == "geomed":
+        if AGGREGATOR_NAMES[self.robust] == "geomed":
             out[:self.P] = geomed_torch(stack, active, int(self.cfg.geomed_iters), float(self.cfg.geomed_nu))
+        elif AGGREGATOR_NAMES[self.robust] == "cclip":
+            out[:self.P] = cclip_torch(stack, active, self._dp_input.to(stack.dtype), int(self.cfg.cclip_iters),
+                                       float(self.cfg.cclip_tau))
         else:
             out[:self.P] = robust_aggregate_torch(stack, active, AGGREGATORS[self.robust], self.robust_beta)
         return out
@@ -1693,9 +1723,12 @@ class HipRoundEngine(RoundEngineBase):
         # mean of the kept clients
         self.layout["aggregator"] = cfg.aggregator if self.robust else AGGREGATORS[0]
         self.layout["screen"] = SCREENS[self.screen]
-        if ALL_AGGREGATORS[self.robust] == "geomed":
+        if AGGREGATOR_NAMES[self.robust] == "geomed":
             self.layout["geomed"] = {"iters": int(cfg.geomed_iters), "nu": float(np.float32(cfg.geomed_nu)),
                                      "launches": int(cfg.geomed_iters) + 1}
+        if AGGREGATOR_NAMES[self.robust] == "cclip":
+            self.layout["cclip"] = {"iters": int(cfg.cclip_iters), "tau": float(np.float32(cfg.cclip_tau)),
+                                    "launches": int(cfg.cclip_iters) + 1}
         if self.secagg:
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
         if self.attack:

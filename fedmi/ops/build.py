@@ -107,8 +107,9 @@ def _build_lock():
 # operation: it is compiled without the packed fp32 forms (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32), so
 # the vectoriser cannot pair its separate products and sums into them.
 # fl_auc.hip's keys are the bits of the held-out row kernel's softmax: the same separate operations.
+# fl_cclip.hip is held bit for bit to cclip_model: its replayed pulls are separate products and sums too.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-_SOURCE_FLAGS = {"fl_lowrank.hip": _NO_PACKED_FP32, "fl_auc.hip": _NO_PACKED_FP32}
+_SOURCE_FLAGS = {"fl_lowrank.hip": _NO_PACKED_FP32, "fl_auc.hip": _NO_PACKED_FP32, "fl_cclip.hip": _NO_PACKED_FP32}
 
 
 def _compile(src: str, digest: str) -> str:

@@ -441,6 +441,31 @@ __host__ __device__ constexpr long long fl_geomed_scratch_floats(int Pimg, int T
     return 2ll * fl_geomed_blocks(Pimg) * FL_GEOMED_MAX_K + (long long)T * FL_GEOMED_SLOT;
 }
 
+// Centered-clipping aggregation (fl_cclip.hip; Karimireddy, He, Jaggi 2021): parameters of the per-round
+// launches, passed to those kernels alone.  From the image x the round trained from, T times: squared
+// whole-model distances d_i of the round's sampled clients (rtab mask) to the estimate z, clip factors
+// c_i = min(1, tau / sqrt(d_i)) over the clients with d_i < +inf, z += (sum c_i (v_i - z)) / K_r.
+#define FL_CCLIP_MAX_K 64            // width of the rtab mask
+#define FL_CCLIP_MAX_ITERS 8         // the replay is quadratic in T; the paper uses 1 .. 5
+#define FL_CCLIP_THREADS 256         // floats of the image per workgroup: d_i's summation order is fl_geomed's
+// one iteration's record in the caller's scratch, floats: [0, 64) the clip factors c_i (0: not included),
+// [64, 128) the distances d_i it measured (+inf: a sum that is not < +inf; 0: not sampled), [128, 130) the
+// mask of the included clients (two 32-bit halves; 0: z stayed)
+#define FL_CCLIP_SLOT 192
+struct FLCclip {
+    int K;               // sources, 1 .. FL_CCLIP_MAX_K (source k is client k)
+    int max_rounds;      // rounds of rtab; rounds past it are not live
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+    int T;               // clipping iterations, 1 .. FL_CCLIP_MAX_ITERS
+    float tau;           // clipping radius, > 0
+};
+__host__ __device__ constexpr int fl_cclip_blocks(int Pimg) { return (Pimg + FL_CCLIP_THREADS - 1) / FL_CCLIP_THREADS; }
+// floats of scratch the launches need: two sets of per-workgroup distance partials (64 per workgroup),
+// then T iteration records
+__host__ __device__ constexpr long long fl_cclip_scratch_floats(int Pimg, int T) {
+    return 2ll * fl_cclip_blocks(Pimg) * FL_CCLIP_MAX_K + (long long)T * FL_CCLIP_SLOT;
+}
+
 // Secure aggregation (fl_secagg.hip; Bonawitz et al. 2017, the arithmetic only): parameters of the
 // per-round mask and open launches, passed to those kernels alone.  A sampled client's contribution c
 // becomes q = clamp(rint(c 2^bits), -L, L), L = (2^31 - 1) / K_r, plus / minus the pair masks
@@ -658,6 +683,19 @@ hipError_t fl_launch_geomed(const MLPDesc& d, const FLGeomed& p, const float* co
 // nothing).  `x`: the image the round trained from.  No per-round host argument: the launch is replayable.
 hipError_t fl_launch_attack(const MLPDesc& d, const FLAttack& p, float* const* bufs, const float* x,
                             const FLState* st, hipStream_t s);
+// (fl_cclip.hip) centered-clipping aggregate of the round whose state is `st`: the T + 1 launches over the K
+// buffers of Pimg + tails_len floats named by `src`, around the image `x` the round trained from (Pimg
+// floats, read only), the result into the n_dst buffers named by `dst` (they may be the sources; never x).
+// `scratch`: fl_cclip_scratch_floats caller-owned floats; iteration l's record (FL_CCLIP_SLOT) lies at
+// 2 * blocks * 64 + l * FL_CCLIP_SLOT.  x must not be a destination.  The table `dst` lives on the device,
+// where the launcher cannot read it without a synchronising copy (which a captured sequence cannot hold), so
+// it takes the destinations' addresses as the host knows them in `dst_host` (n_dst entries, required) and
+// returns hipErrorInvalidValue when x overlaps one of them.  A round that is not live is
+// the whole-buffer left fold and writes no scratch.  `keep` as fl_launch_robust's.  No per-round host argument:
+// the sequence is replayable.
+hipError_t fl_launch_cclip(const MLPDesc& d, const FLCclip& p, const float* const* src, const float* x,
+                           float* const* dst, int n_dst, const FLState* st, int tails_len, float* scratch,
+                           hipStream_t s, const unsigned long long* keep, const unsigned long long* dst_host);
 // (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
 // place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
 // first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);

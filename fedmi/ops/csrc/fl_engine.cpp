@@ -1557,6 +1557,37 @@ static void geomed_aggregate(std::vector<int> dims, int iters, double nu, uintpt
                                as_ptr<const unsigned long long>(keep)));
 }
 
+// Centered-clipping aggregate (fl_cclip.hip) across engines' buffers, as geomed_aggregate is: the iters + 1
+// launches around `x`, the image the round trained from (Pimg floats; never a destination).  `scratch`:
+// cclip_scratch_floats(dims, iters) caller-owned floats (distance partials, then one CCLIP_SLOT record per
+// iteration: clip factors, distances, included mask).  `dst_addrs` (required): the n_dst destination addresses as
+// the caller's host knows them (the table `dst` is device memory): x among them is refused.
+static void cclip_aggregate(std::vector<int> dims, int iters, double tau, uintptr_t src, int K, uintptr_t x, uintptr_t dst,
+                            int n_dst, uintptr_t state, uintptr_t rtab, int tails_len, int max_rounds, uintptr_t scratch,
+                            uintptr_t stream, uintptr_t keep, const std::vector<unsigned long long>& dst_addrs) {
+    const MLPDesc d = desc_of(dims, "cclip_aggregate");
+    if (K < 1 || K > FL_CCLIP_MAX_K)
+        throw std::runtime_error("cclip_aggregate: 1.." + std::to_string(FL_CCLIP_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (iters < 1 || iters > FL_CCLIP_MAX_ITERS)
+        throw std::runtime_error("cclip_aggregate: iters must be in 1.." + std::to_string(FL_CCLIP_MAX_ITERS));
+    const float tauf = (float)tau;
+    if (!(tauf > 0.f) || !std::isfinite(tauf)) throw std::runtime_error("cclip_aggregate: tau must be finite and > 0 in fp32");
+    if (n_dst < 1 || n_dst > FL_CCLIP_MAX_K || tails_len < 0 || max_rounds < 1 || !src || !x || !dst || !state || !rtab ||
+        !scratch || (int)dst_addrs.size() != n_dst)
+        throw std::runtime_error("cclip_aggregate: bad arguments");
+    FLCclip p;
+    std::memset(&p, 0, sizeof(p));
+    p.K = K;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    p.T = iters;
+    p.tau = tauf;
+    HIP_CHECK(fl_launch_cclip(d, p, as_ptr<const float* const>(src), as_ptr<const float>(x), as_ptr<float* const>(dst),
+                              n_dst, as_ptr<const FLState>(state), tails_len, as_ptr<float>(scratch), as_stream(stream),
+                              as_ptr<const unsigned long long>(keep), dst_addrs.data()));
+}
+
 // Multi-Krum screening (fl_screen.hip) across engines' buffers, as robust_aggregate is.  `src`: device table
 // of K buffer addresses (int64); `dist`: K x K floats; `keep`: one uint64; `hist`: max_rounds uint64, all
 // caller-owned; `f` / `m`: Byzantine clients assumed and clients kept (0: K_r - f).
@@ -1800,6 +1831,15 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.attr("GEOMED_SLOT") = (int)FL_GEOMED_SLOT;
     m.attr("GEOMED_THREADS") = (int)FL_GEOMED_THREADS;
     m.attr("GEOMED_MAX_ITERS") = (int)FL_GEOMED_MAX_ITERS;
+    m.def("cclip_aggregate", &cclip_aggregate, py::arg("dims"), py::arg("iters"), py::arg("tau"), py::arg("src"),
+          py::arg("K"), py::arg("x"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"),
+          py::arg("tails_len"), py::arg("max_rounds"), py::arg("scratch"), py::arg("stream"),
+          py::arg("keep") = (uintptr_t)0, py::kw_only(), py::arg("dst_addrs"));
+    m.def("cclip_scratch_floats", [](const std::vector<int>& dims, int iters) {
+        return fl_cclip_scratch_floats(desc_of(dims, "cclip_scratch_floats").Pimg, iters);
+    });
+    m.attr("CCLIP_SLOT") = (int)FL_CCLIP_SLOT;
+    m.attr("CCLIP_MAX_ITERS") = (int)FL_CCLIP_MAX_ITERS;
     m.def("screen_dist", &screen_dist, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("dist"), py::arg("state"),
           py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("tile") = 0);
     m.def("screen_select", &screen_select, py::arg("dist"), py::arg("K"), py::arg("f"), py::arg("m"), py::arg("keep"),
