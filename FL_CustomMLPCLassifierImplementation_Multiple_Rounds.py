@@ -116,11 +116,12 @@ def parse_args(argv=None):
                     help="--attack alie: standard deviations below the honest mean (default: the paper's z for the "
                          "federation's size and the number of --attack-clients)")
     ap.add_argument("--attack-seed", type=int, default=0, help="--attack gauss: 64-bit Philox seed")
-    ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk", "powersgd"], default="none",
+    ap.add_argument("--compress", choices=["none", "topk", "sign", "qsgd", "randk", "powersgd", "mx"], default="none",
                     help="compress every client's round update with error feedback: topk = the largest "
                          "--compress-ratio of its entries, sign = one bit per entry and a scale, qsgd = stochastic "
                          "quantisation to --compress-levels levels, randk = a random --compress-ratio of its entries, "
-                         "powersgd = rank --compress-rank factors of every weight matrix "
+                         "powersgd = rank --compress-rank factors of every weight matrix, mx = blocks of 32 entries "
+                         "share a power-of-two scale and send --compress-format elements "
                          "(a simulated uplink: the exchange stays dense; --jsonl rows carry uplink_bytes)")
     ap.add_argument("--compress-ratio", type=float, default=0.1,
                     help="--compress topk / randk: fraction of entries kept, in (0, 1]")
@@ -129,6 +130,10 @@ def parse_args(argv=None):
                     help="--compress qsgd / randk: seed of the random stream; powersgd: seed of the starting factors "
                          "(default: a private draw per client)")
     ap.add_argument("--compress-rank", type=int, default=4, help="--compress powersgd: rank r of the factors, in [1, 8]")
+    ap.add_argument("--compress-format", choices=["e4m3", "e5m2", "e2m1"], default="e4m3",
+                    help="--compress mx: element format (FP8 E4M3, FP8 E5M2, FP4 E2M1)")
+    ap.add_argument("--compress-rounding", choices=["nearest", "stochastic"], default="nearest",
+                    help="--compress mx: element rounding (stochastic draws from --compress-seed)")
     ap.add_argument("--no-error-feedback", action="store_true",
                     help="--compress: discard what the compressor drops instead of carrying it to the next round")
     ap.add_argument("--secagg", action="store_true",
@@ -272,7 +277,8 @@ def _attack_fields(a) -> dict:
 
 def _compress_fields(a) -> dict:
     return dict(compress=a.compress, compress_ratio=a.compress_ratio, error_feedback=not a.no_error_feedback,
-                compress_levels=a.compress_levels, compress_seed=a.compress_seed, compress_rank=a.compress_rank)
+                compress_levels=a.compress_levels, compress_seed=a.compress_seed, compress_rank=a.compress_rank,
+                compress_format=a.compress_format, compress_rounding=a.compress_rounding)
 
 
 def _secagg_fields(a) -> dict:

@@ -60,8 +60,29 @@ The low-rank compressor is the only one that uses the parameters' matrix structu
   (0 where ``u = 0`` or the client is not sampled).  A real uplink carries ``r (N + K)`` floats per
   compressed layer and every raw entry; no indices.
 
+The block-scaled quantiser is the only rule that is local: a block's code depends on its own 32 values
+(``fedmi/ops/csrc/fl_mx.hip``; OCP Microscaling Formats "MX" v1.0, Rouhani et al. 2023):
+
+* ``"mx"`` (``compress_format`` in ``e4m3`` / ``e5m2`` / ``e2m1``, ``compress_rounding`` in ``nearest`` /
+  ``stochastic``).  A block is 32 consecutive dense parameters; the last one is partial.  ``A`` = the largest
+  ``bits(u) & 0x7fffffff`` of the block, ``E = A >> 23``.  ``E == 255`` (an inf or NaN in the block): the block
+  travels raw, ``c = u``, ``e' = 0`` (qsgd's escape, per block).  ``E < 32`` (block maximum below ``2**-95``):
+  ``c = copysign(0, u)``, ``e' = u - c``; the cut-off keeps every scale and every dequantised value a normal
+  fp32.  Otherwise ``e = E - 127 - emax`` with ``emax`` = 8 / 15 / 2, the MX scale ``2**(floor(log2 max) -
+  emax)``; ``t = |u| * 2**-e`` exactly; the element grid is the format's non-negative finite values (e4m3:
+  bias 7, subnormals, maximum 448, no inf; e5m2: bias 15, subnormals, maximum 57344; e2m1: 0, 0.5, 1, 1.5,
+  2, 3, 4, 6); ``t`` at or above the maximum saturates to it (the band up to ``2**(emax + 1)`` is reachable in
+  every block).  ``"nearest"``: the nearest grid value, ties to the even element code.  ``"stochastic"``: with
+  ``l <= t < h`` the neighbouring grid values and ``frac = (t - l) / (h - l)``, ``q = h if (word >> 8) < frac
+  * 2**24 else l`` (``t`` on the grid or saturated: ``q = t``), ``word`` as for the random compressors on
+  ``MX_STREAM``.  ``c = copysign(q * 2**e, u)``, exact; ``e' = u - c``.  The statistic is the largest block
+  scale ``2**e`` of the round's quantised blocks (0: none, or the client is not sampled).  A real uplink
+  carries one E8M0 scale byte per block and ``bits`` = 8 / 8 / 4 per element: ``ceil(P / 32) + ceil(P * bits /
+  8)`` bytes; blocks that travel raw are not counted.  :func:`mx_quantize` states the rule from the formats'
+  value tables.
+
 An unsampled client and a round that is not live leave contribution and residual (and powersgd's ``Q``)
-untouched.  Top-k, sign and powersgd are deterministic: every replica and every graph replay is bit-identical.  The random compressors
+untouched.  Top-k, sign, powersgd and mx with nearest rounding are deterministic: every replica and every graph replay is bit-identical.  The random compressors
 are deterministic given ``(compress_seed, round, client)``: the round word comes from the device state,
 so a replayed graph draws fresh words each round, and a resumed run continues the stream.
 """
@@ -80,6 +101,12 @@ ALL_COMPRESSORS = COMPRESSORS + RANDOM_COMPRESSORS
 # low-rank factorisation: the compressor carries a state Q per compressed layer beside the residual
 LOWRANK_COMPRESSORS = ("powersgd",)
 COMPRESSOR_KINDS = ALL_COMPRESSORS + LOWRANK_COMPRESSORS   # compress_id's index: the kernels' FL_COMPRESS_*
+# block floating point: 32 consecutive parameters share one power-of-two scale (OCP MX)
+BLOCK_COMPRESSORS = ("mx",)
+COMPRESSOR_NAMES = COMPRESSOR_KINDS + BLOCK_COMPRESSORS   # ... and with "mx" = FL_COMPRESS_MX = 6 behind them
+MX_FORMATS = ("e4m3", "e5m2", "e2m1")                     # the kernel's FL_MX_* index
+MX_ROUNDINGS = ("nearest", "stochastic")
+MX_BLOCK = 32
 MAX_LEVELS = 32767
 MAX_RANK = 8
 # threads of the kernel's workgroup: the fixed summation order of `s` follows them
@@ -88,9 +115,9 @@ _THREADS = 1024
 
 def compress_id(cfg) -> int:
     """Validate the compression fields of an ``EngineConfig``; the compressor's index in
-    ``COMPRESSOR_KINDS`` (0 = off)."""
-    if cfg.compress not in COMPRESSOR_KINDS:
-        raise ValueError(f"compress must be one of {COMPRESSOR_KINDS}, got {cfg.compress!r}")
+    ``COMPRESSOR_NAMES`` (0 = off)."""
+    if cfg.compress not in COMPRESSOR_NAMES:
+        raise ValueError(f"compress must be one of {COMPRESSOR_NAMES}, got {cfg.compress!r}")
     try:
         ratio = float(cfg.compress_ratio)
     except (TypeError, ValueError):
@@ -109,7 +136,12 @@ def compress_id(cfg) -> int:
     rank = getattr(cfg, "compress_rank", 4)
     if isinstance(rank, (bool, np.bool_)) or not isinstance(rank, (int, np.integer)) or not 1 <= int(rank) <= MAX_RANK:
         raise ValueError(f"compress_rank must be an integer in [1, {MAX_RANK}], got {rank!r}")
-    kind = COMPRESSOR_KINDS.index(cfg.compress)
+    fmt, rounding = getattr(cfg, "compress_format", "e4m3"), getattr(cfg, "compress_rounding", "nearest")
+    if not isinstance(fmt, str) or fmt not in MX_FORMATS:
+        raise ValueError(f"compress_format must be one of {MX_FORMATS}, got {fmt!r}")
+    if not isinstance(rounding, str) or rounding not in MX_ROUNDINGS:
+        raise ValueError(f"compress_rounding must be one of {MX_ROUNDINGS}, got {rounding!r}")
+    kind = COMPRESSOR_NAMES.index(cfg.compress)
     if kind and float(cfg.dp_clip) > 0.0:
         raise ValueError(f"compress={cfg.compress!r} does not combine with differential privacy (dp_clip > 0): "
                          "both rewrite the contribution, and the noise calibration assumes the clipped update")
@@ -136,14 +168,22 @@ def qsgd_code_bits(levels: int) -> int:
     return (2 * int(levels)).bit_length()   # 2 s + 1 codes: the smallest b with 2**b >= 2 s + 1
 
 
-def uplink_bytes(kind: str, k: int, P: int, levels: int = 127) -> int:
+def mx_uplink_bytes(P: int, fmt: str) -> int:
+    """Bytes of an MX uplink: one E8M0 scale per block of 32 and 8 / 8 / 4 bits per element."""
+    return (int(P) + MX_BLOCK - 1) // MX_BLOCK + (int(P) * (4 if MX_FORMATS.index(fmt) == 2 else 8) + 7) // 8
+
+
+def uplink_bytes(kind: str, k: int, P: int, levels: int = 127, fmt: str = "e4m3") -> int:
     """Bytes a real uplink would carry per client and round: top-k ``8 k`` (an fp32 value and an int32
     index per kept entry), sign ``4 + ceil(P / 8)`` (the fp32 scale and one bit per coordinate), qsgd
     ``4 + ceil(P * ceil(log2(2 s + 1)) / 8)`` (the fp32 norm and a fixed-width sign-and-level code per
     coordinate; no Elias coding), randk ``4 k`` (the values only: the indices follow from the shared
-    seed), powersgd ``4 k`` (``k`` = :func:`compress_k`: factors and raw entries), dense ``4 P``."""
-    if kind not in COMPRESSOR_KINDS:
-        raise ValueError(f"compress must be one of {COMPRESSOR_KINDS}, got {kind!r}")
+    seed), powersgd ``4 k`` (``k`` = :func:`compress_k`: factors and raw entries), mx
+    :func:`mx_uplink_bytes` of ``fmt`` (raw blocks are not counted), dense ``4 P``."""
+    if kind not in COMPRESSOR_NAMES:
+        raise ValueError(f"compress must be one of {COMPRESSOR_NAMES}, got {kind!r}")
+    if kind in BLOCK_COMPRESSORS:
+        return mx_uplink_bytes(P, fmt)
     if kind == "topk":
         return 8 * int(k)
     if kind == "sign":
@@ -224,10 +264,11 @@ def _largest_mask(key: np.ndarray, k: int) -> torch.Tensor:
 
 def compress_words(kind: str, P: int, seed: int, round: int, client: int) -> np.ndarray:
     """The 32-bit Philox word of every dense parameter for a random compressor (uint32 ``[P]``)."""
-    from ..privacy.philox import QSGD_STREAM, RANDK_STREAM, param_words
-    if kind not in RANDOM_COMPRESSORS:
-        raise ValueError(f"compress_words: kind must be one of {RANDOM_COMPRESSORS}, got {kind!r}")
-    return param_words(P, round, client, seed, QSGD_STREAM if kind == "qsgd" else RANDK_STREAM)
+    from ..privacy.philox import MX_STREAM, QSGD_STREAM, RANDK_STREAM, param_words
+    streams = {"qsgd": QSGD_STREAM, "randk": RANDK_STREAM, "mx": MX_STREAM}
+    if kind not in streams:
+        raise ValueError(f"compress_words: kind must be one of {tuple(streams)}, got {kind!r}")
+    return param_words(P, round, client, seed, streams[kind])
 
 
 def randk_keys(P: int, seed: int, round: int, client: int) -> np.ndarray:
@@ -255,11 +296,12 @@ def qsgd_levels(u, levels: int, norm, words: np.ndarray) -> np.ndarray:
 
 def compress_torch(u, kind: str, k: int = 0, error_feedback: bool = True,
                    s: Optional[float] = None, *, levels: int = 127, seed: int = 0, round: int = 0,
-                   client: int = 0, norm: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, float]:
+                   client: int = 0, norm: Optional[float] = None, fmt: str = "e4m3",
+                   rounding: str = "nearest") -> Tuple[torch.Tensor, torch.Tensor, float]:
     """``(c, e', stat)`` of the vector ``u`` (fp32, or float64 kept as float64): the compressed update,
     the new residual and the round's statistic (top-k: the magnitude of the k-th kept entry; sign: the
     scale ``s``; qsgd: the norm; randk: ``key31`` of the k-th kept entry times ``2**-31``, the selection's
-    quantile).  In fp32 a bit-exact model of the kernel given the same ``u`` and, for sign / qsgd, the same
+    quantile; mx: the largest block scale).  In fp32 a bit-exact model of the kernel given the same ``u`` and, for sign / qsgd, the same
     ``s`` / ``norm`` (``None``: the host model of the kernel's sum, :func:`sign_scale` / :func:`qsgd_norm`).
     The random kinds draw the words of ``(seed, round, client)``."""
     u = _vec(u)
@@ -304,8 +346,13 @@ def compress_torch(u, kind: str, k: int = 0, error_feedback: bool = True,
             c = torch.where(kept, u * float(ft(ft(P) / ft(int(k)))), zero)
         e = torch.where(kept, zero, u)
         stat = float(np.float32(key[kept.numpy()].min()) * np.float32(2.0 ** -31))
+    elif kind == "mx":
+        words = compress_words("mx", P, seed, round, client) if rounding == "stochastic" else None
+        c, raw, stat = mx_quantize(u, fmt, rounding, words)
+        with np.errstate(invalid="ignore"):
+            e = torch.where(raw, torch.zeros_like(u), u - c)
     else:
-        raise ValueError(f"compress_torch: kind must be one of {ALL_COMPRESSORS[1:]}, got {kind!r}")
+        raise ValueError(f"compress_torch: kind must be one of {ALL_COMPRESSORS[1:] + BLOCK_COMPRESSORS}, got {kind!r}")
     if not error_feedback:
         e = torch.zeros_like(u)
     return c, e, stat
@@ -313,7 +360,8 @@ def compress_torch(u, kind: str, k: int = 0, error_feedback: bool = True,
 
 def compress_round(local, x, e, w: float, kind: str, k: int = 0, error_feedback: bool = True,
                    s: Optional[float] = None, *, levels: int = 127, seed: int = 0, round: int = 0,
-                   client: int = 0, norm: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, float]:
+                   client: int = 0, norm: Optional[float] = None, fmt: str = "e4m3",
+                   rounding: str = "nearest") -> Tuple[torch.Tensor, torch.Tensor, float]:
     """The whole rule for one sampled client of a live round: ``(contribution, e', stat)`` from its
     local model, the image ``x`` the round trained from, its residual ``e`` and FedAvg weight ``w``
     (dense vectors; fp32 unless ``local`` is float64)."""
@@ -321,8 +369,63 @@ def compress_round(local, x, e, w: float, kind: str, k: int = 0, error_feedback:
     x, e = _vec(x).to(local.dtype), _vec(e).to(local.dtype)
     u = (local - x) + e
     c, e_new, stat = compress_torch(u, kind, k, error_feedback, s, levels=levels, seed=seed, round=round,
-                                    client=client, norm=norm)
+                                    client=client, norm=norm, fmt=fmt, rounding=rounding)
     return torch.tensor(float(w), dtype=local.dtype) * (x + c), e_new, stat
+
+
+# ---- block-scaled FP8 / FP4 elements (OCP MX): the rule fl_mx.hip is held to ----
+_MX_SPEC = {"e4m3": (7, 3, 8, 0x7E), "e5m2": (15, 2, 15, 0x7B), "e2m1": (1, 1, 2, 0x7)}   # bias, mantissa bits, emax, top code
+
+
+def mx_grid(fmt: str) -> np.ndarray:
+    """The non-negative finite values of an element format in code order (float64; index = element code)."""
+    bias, m, _, top = _MX_SPEC[fmt]
+    vals = []
+    for code in range(top + 1):
+        ex, man = code >> m, code & ((1 << m) - 1)
+        vals.append(man * 2.0 ** (1 - bias - m) if ex == 0 else (1.0 + man * 2.0 ** -m) * 2.0 ** (ex - bias))
+    return np.asarray(vals, np.float64)
+
+
+def mx_quantize(u, fmt: str = "e4m3", rounding: str = "nearest", words: Optional[np.ndarray] = None):
+    """``(c, raw, stat)`` of the vector ``u`` under the MX rule of the module docstring, block by block in
+    float64 from :func:`mx_grid`: ``c`` in ``u``'s float type, ``raw`` = the entries of blocks that travel as
+    they are, ``stat`` = the largest block scale (0: no block was quantised).  ``words``: the uint32 word of
+    every entry (``"stochastic"``)."""
+    if fmt not in MX_FORMATS or rounding not in MX_ROUNDINGS:
+        raise ValueError(f"mx_quantize: fmt must be one of {MX_FORMATS} and rounding one of {MX_ROUNDINGS}")
+    u = _vec(u)
+    a = u.numpy().astype(np.float64)
+    grid, emax = mx_grid(fmt), _MX_SPEC[fmt][2]
+    if rounding == "stochastic":
+        if words is None or len(words) != a.shape[0]:
+            raise ValueError("mx_quantize: stochastic rounding needs one word per entry")
+        w24 = (np.asarray(words, np.uint32) >> np.uint32(8)).astype(np.float64)
+    c, raw, best = a.copy(), np.zeros(a.shape[0], bool), None
+    for b in range(0, a.shape[0], MX_BLOCK):
+        blk = a[b:b + MX_BLOCK]
+        if not np.all(np.isfinite(blk)):
+            raw[b:b + MX_BLOCK] = True
+            continue
+        top = np.abs(blk).max()
+        if top < 2.0 ** -95:
+            c[b:b + MX_BLOCK] = np.copysign(0.0, blk)
+            continue
+        e = math.frexp(top)[1] - 1 - emax                   # floor(log2 max) - emax
+        t = np.minimum(np.ldexp(np.abs(blk), -e), grid[-1])   # exact; the band above the maximum saturates
+        hi = np.minimum(np.searchsorted(grid, t, side="right"), len(grid) - 1)
+        lo = np.searchsorted(grid, t, side="right") - 1      # grid[lo] <= t, and t < grid[hi] unless saturated
+        l, h = grid[lo], grid[hi]
+        if rounding == "nearest":
+            mid = 0.5 * (l + h)
+            up = (t > mid) | ((t == mid) & (lo % 2 == 1))    # a tie goes to the even code
+        else:
+            frac = (t - l) / np.where(h > l, h - l, 1.0)     # exact: a 25-bit difference over a power of two
+            up = w24[b:b + MX_BLOCK] < frac * 2.0 ** 24
+        c[b:b + MX_BLOCK] = np.copysign(np.ldexp(np.where(up, h, l), e), blk)
+        best = e if best is None else max(best, e)
+    stat = 0.0 if best is None else 2.0 ** best
+    return torch.as_tensor(c.astype(u.numpy().dtype)), torch.as_tensor(raw), float(stat)
 
 
 # ---- low-rank factors (PowerSGD): the host model of fl_lowrank.hip ----

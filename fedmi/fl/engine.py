@@ -35,7 +35,8 @@ from .aggregate import (AGGREGATOR_NAMES, AGGREGATORS, CCLIP_MAX_ITERS, GEOMED_M
                         robust_aggregate_torch, screen_select)
 from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
                      attack_torch)
-from .compress import (COMPRESSORS, LOWRANK_COMPRESSORS, RANDOM_COMPRESSORS, compress_id, compress_k, compress_torch,
+from .compress import (BLOCK_COMPRESSORS, COMPRESSORS, LOWRANK_COMPRESSORS, MX_FORMATS, RANDOM_COMPRESSORS, compress_id,
+                       compress_k, compress_torch,
                        lowrank_layers, lowrank_q0, lowrank_torch, uplink_bytes)
 from .early_stop import EarlyStopper
 from .metrics import (METRIC_NAMES, auc_from_u2, auc_u2_model, confusion_matrix, metrics_from_confusion,
@@ -197,6 +198,12 @@ class EngineConfig:
     compress_levels: int = 127
     compress_seed: Optional[int] = None
     compress_rank: int = 4
+    # "mx" (OCP Microscaling): blocks of 32 consecutive parameters share one power-of-two scale and send
+    # compress_format ("e4m3" / "e5m2" / "e2m1") elements, rounded to "nearest" (deterministic) or
+    # "stochastic" (Philox words of (compress_seed, round, client), a seeded engine as qsgd); compress_stat =
+    # the round's largest block scale.
+    compress_format: str = "e4m3"
+    compress_rounding: str = "nearest"
     # Secure aggregation (fedmi/fl/secagg.py; Bonawitz et al. 2017): every sampled client quantises its
     # weighted contribution to fixed point with secagg_bits fractional bits and adds / subtracts one
     # Philox mask per pair of the round's sampled clients (mod 2^32) before the exchange; the masks
@@ -563,7 +570,9 @@ class RoundEngineBase:
         self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
         self.compress = compress_id(cfg)   # index in ALL_COMPRESSORS; 0 = dense contributions
         # the stochastic kinds carry one more piece of state: the client's seed (config, or a private draw)
-        self.compress_random = cfg.compress in RANDOM_COMPRESSORS
+        self.compress_block = cfg.compress in BLOCK_COMPRESSORS
+        self.compress_random = cfg.compress in RANDOM_COMPRESSORS or (
+            self.compress_block and cfg.compress_rounding == "stochastic")
         if self.compress_random:
             self.compress_seed = (int.from_bytes(os.urandom(8), "little") if cfg.compress_seed is None
                                   else int(cfg.compress_seed))
@@ -946,7 +955,8 @@ class RoundEngineBase:
     def uplink_bytes(self) -> int:
         """Bytes per round a real uplink would carry for this client's contribution (the exchange
         itself stays dense: compression is simulated)."""
-        return uplink_bytes(self.cfg.compress, self.compress_k, self.P, int(self.cfg.compress_levels))
+        return uplink_bytes(self.cfg.compress, self.compress_k, self.P, int(self.cfg.compress_levels),
+                            self.cfg.compress_format)
 
     def _compress_state_in(self, st: dict):
         """The dense compression residual of a portable state for this engine, or None without
@@ -1228,6 +1238,8 @@ class TorchRoundEngine(RoundEngineBase):
             u = (local.to(torch.float32) - x) + self.compress_residual
             rnd = (dict(levels=int(self.cfg.compress_levels), seed=self.compress_seed, round=r, client=self.rank)
                    if self.compress_random else {})
+            if self.compress_block:
+                rnd.update(fmt=self.cfg.compress_format, rounding=self.cfg.compress_rounding)
             if self.compress_lowrank:
                 c, self.compress_residual, self.compress_q, stat = lowrank_torch(
                     u, self.compress_q, self.dims, int(self.cfg.compress_rank), bool(self.cfg.error_feedback))
@@ -1679,6 +1691,9 @@ class HipRoundEngine(RoundEngineBase):
                 self.cp_q[:2 * self.compress_q_len].copy_(torch.as_tensor(self._compress_q0).repeat(2))
                 ecfg["compress_rank"] = int(cfg.compress_rank)
                 bufs["compress_q"] = self.cp_q.data_ptr()
+            if self.compress_block:
+                ecfg.update({"compress_format": MX_FORMATS.index(cfg.compress_format),
+                             "compress_stochastic": cfg.compress_rounding == "stochastic"})
         if self.server:
             # server optimizer state: image-shaped fp32 (m = 0; v = tau^2 everywhere, padding included)
             if comm_buffers is not None:

@@ -374,6 +374,31 @@ struct FLLowRank {
     float* q;            // [2][Qlen] fp32, caller-owned, both halves Q_0 at start: halves by round parity as residual
 };
 
+// Block-scaled quantisation (fl_mx.hip; OCP Microscaling, "MX"): parameters of the per-round kernel that takes
+// fl_compress's place for this kind, passed to that kernel alone.  32 consecutive dense parameters of u share
+// one power-of-two scale 2^e, e = floor(log2 max|u|) - emax of the element format; an element is
+// |u| 2^-e rounded into the format's finite grid (nearest, ties to the even code; or stochastic by word p % 4 of
+// Philox4x32-10 at counter (p / 4, round, client, FL_MX_STREAM) under (key0, key1)), saturating at its maximum.
+// A block with an inf or NaN travels raw; a block below 2^-95 sends signed zeros.  (5 is FL_COMPRESS_POWERSGD.)
+#define FL_COMPRESS_MX 6
+#define FL_MX_BLOCK 32
+#define FL_MX_E4M3 0
+#define FL_MX_E5M2 1
+#define FL_MX_E2M1 2
+#define FL_MX_STREAM 0x3453584Du     // "MXS4": distinct from the compressors', the DP, attack and pair-mask streams
+struct FLMx {
+    int fmt;             // FL_MX_E4M3 / FL_MX_E5M2 / FL_MX_E2M1
+    int stochastic;      // 0: nearest, ties to the even element code; 1: stochastic rounding
+    int error_feedback;  // as FLCompress
+    int max_rounds;      // entries of stat_hist; rounds past it are not live
+    int client;          // stochastic: third word of the counter, as FLCompress::client
+    uint32_t key0, key1; // stochastic: Philox key, the client's 64-bit compress seed, low and high word
+    int conv;            // -1: the conversion path fl_mx.hip chose for (fmt, rounding); 0: integer code; 1: the
+                         // gfx950 scaled conversion instructions (nearest only) -- tests and tools compare the two
+    float* residual;     // [2][Pimg] fp32, as FLCompress::residual
+    float* stat_hist;    // [max_rounds] the largest block scale 2^e of the round (0: not sampled, nothing quantised)
+};
+
 // Robust aggregation (fl_robust.hip; Yin et al. 2018): parameters of the per-round coordinate-wise
 // median / trimmed mean over K clients' buffers, passed to that kernel alone.  Of the round's K_r
 // sampled clients (rtab mask) the fl_robust_trim lowest and highest values of every coordinate are
@@ -641,6 +666,11 @@ hipError_t fl_lowrank_plan(const MLPDesc& d, int rank, FLLowRank& p);
 hipError_t fl_set_lds_limit_lowrank(const MLPDesc& d, const FLLowRank& p);
 hipError_t fl_launch_lowrank(const MLPDesc& d, const FLLowRank& p, const float* local, const float* pg, float* comm,
                              const FLState* st, const float* rtab, hipStream_t s);
+// (fl_mx.hip) the same slot for FL_COMPRESS_MX: no LDS limit to set, no plan.  fl_mx_uplink_bytes: what a real
+// uplink carries, one E8M0 scale per block and the element codes.
+hipError_t fl_launch_mx(const MLPDesc& d, const FLMx& p, const float* local, const float* pg, float* comm,
+                        const FLState* st, const float* rtab, hipStream_t s);
+long long fl_mx_uplink_bytes(int P, int fmt);
 // (fl_server.hip) server-optimizer step of the round whose state is `st`: `x` = the image the round
 // trained from, `a` = its aggregated image, replaced in place (first Pimg floats only) by the new
 // global image.  `e` / `pk` (bf16 mode, else null): the same launch also writes the packed

@@ -301,6 +301,7 @@ class FLEngine {
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
         }
         std::memset(&lr_, 0, sizeof(lr_));
+        std::memset(&mx_, 0, sizeof(mx_));
         if (cp_.kind == FL_COMPRESS_POWERSGD) {
             // low-rank factors (fl_lowrank.hip) in the compression slot: its own argument struct, the same
             // residual and statistic buffers, and the Q state beside them
@@ -317,6 +318,28 @@ class FLEngine {
             if (lr_.residual == nullptr || lr_.stat_hist == nullptr || lr_.q == nullptr)
                 throw std::runtime_error("FLEngine: powersgd needs the residual, the statistic history and compress_q");
             HIP_CHECK(fl_set_lds_limit_lowrank(d_, lr_));
+        } else if (cp_.kind == FL_COMPRESS_MX) {
+            // block-scaled FP8 / FP4 elements (fl_mx.hip) in the compression slot: its own argument struct, the
+            // same residual and statistic buffers; the stochastic rounding draws words of (compress_seed, round,
+            // this client)
+            mx_.fmt = cfg["compress_format"].cast<int>();
+            mx_.stochastic = cfg["compress_stochastic"].cast<bool>() ? 1 : 0;
+            mx_.conv = -1;
+            if (mx_.fmt < FL_MX_E4M3 || mx_.fmt > FL_MX_E2M1)
+                throw std::runtime_error("FLEngine: compress_format must be 0 (e4m3), 1 (e5m2) or 2 (e2m1)");
+            if (mx_.stochastic) {
+                const unsigned long long seed = cfg["compress_seed"].cast<unsigned long long>();
+                mx_.client = c_.rank;
+                mx_.key0 = (uint32_t)seed;
+                mx_.key1 = (uint32_t)(seed >> 32);
+            }
+            cp_.P = cp_.k = d_.P;
+            mx_.error_feedback = cp_.error_feedback = cfg["error_feedback"].cast<bool>() ? 1 : 0;
+            mx_.max_rounds = cp_.max_rounds = c_.max_rounds;
+            mx_.residual = cp_.residual = as_ptr<float>(bufs["compress_residual"].cast<uintptr_t>());
+            mx_.stat_hist = cp_.stat_hist = as_ptr<float>(bufs["compress_stat"].cast<uintptr_t>());
+            if (mx_.residual == nullptr || mx_.stat_hist == nullptr)
+                throw std::runtime_error("FLEngine: mx needs the residual and the statistic history");
         } else if (tr_.compress_on) {
             if (cp_.kind < FL_COMPRESS_TOPK || cp_.kind > FL_COMPRESS_RANDK)
                 throw std::runtime_error("FLEngine: unknown compressor");
@@ -669,9 +692,10 @@ class FLEngine {
     // Philox key of a stochastic compressor (resume: the checkpoint's stream continues); a kernel
     // argument, so captured graphs are dropped.
     void set_compress_seed(unsigned long long seed) {
-        if (!compress_random()) throw std::runtime_error("set_compress_seed: no stochastic compressor (qsgd, randk)");
-        cp_.key0 = (uint32_t)seed;
-        cp_.key1 = (uint32_t)(seed >> 32);
+        if (!compress_random())
+            throw std::runtime_error("set_compress_seed: no stochastic compressor (qsgd, randk, mx with stochastic rounding)");
+        mx_.key0 = cp_.key0 = (uint32_t)seed;
+        mx_.key1 = cp_.key1 = (uint32_t)(seed >> 32);
         drop_graph();
     }
 
@@ -988,7 +1012,7 @@ class FLEngine {
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
         {
             // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
-            static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk", "powersgd"};
+            static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk", "powersgd", "mx"};
             const long long P = d_.P, k = tr_.compress_on ? cp_.k : P;
             long long code_bits = 0;  // qsgd: ceil(log2(2 s + 1)), a fixed-width sign-and-level code
             while ((1ll << code_bits) < 2ll * cp_.levels + 1) ++code_bits;
@@ -1000,11 +1024,17 @@ class FLEngine {
                                 : cp_.kind == FL_COMPRESS_SIGN ? 4 + (P + 7) / 8
                                 : cp_.kind == FL_COMPRESS_QSGD ? 4 + (P * code_bits + 7) / 8
                                 : cp_.kind == FL_COMPRESS_RANDK || cp_.kind == FL_COMPRESS_POWERSGD ? 4 * k
+                                : cp_.kind == FL_COMPRESS_MX ? fl_mx_uplink_bytes(d_.P, mx_.fmt)
                                                                : 4 * P;
             if (cp_.kind == FL_COMPRESS_QSGD) c["levels"] = cp_.levels;
             if (cp_.kind == FL_COMPRESS_POWERSGD) {  // k: the factors' entries and every raw entry
                 c["rank"] = lr_.rank;
                 c["q_len"] = lr_.Qlen;
+            }
+            if (cp_.kind == FL_COMPRESS_MX) {  // one E8M0 scale per 32 entries and the element codes; raw blocks not counted
+                static const char* mx_formats[] = {"e4m3", "e5m2", "e2m1"};
+                c["format"] = std::string(mx_formats[mx_.fmt]);
+                c["rounding"] = std::string(mx_.stochastic ? "stochastic" : "nearest");
             }
             o["compress"] = c;
         }
@@ -1132,6 +1162,8 @@ class FLEngine {
             case FLLaunchRec::COMPRESS:
                 if (cp_.kind == FL_COMPRESS_POWERSGD)
                     HIP_CHECK(fl_launch_lowrank(d_, lr_, F(0), F(1), F(2), S(3), b_.rtab, s));
+                else if (cp_.kind == FL_COMPRESS_MX)
+                    HIP_CHECK(fl_launch_mx(d_, mx_, F(0), F(1), F(2), S(3), b_.rtab, s));
                 else
                     HIP_CHECK(fl_launch_compress(d_, cp_, F(0), F(1), F(2), S(3), b_.rtab, s));
                 break;
@@ -1217,7 +1249,10 @@ class FLEngine {
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLLowRank lr_;             // ... or, cp_.kind == FL_COMPRESS_POWERSGD, fl_lowrank_kernel in its place
-    bool compress_random() const { return cp_.kind == FL_COMPRESS_QSGD || cp_.kind == FL_COMPRESS_RANDK; }
+    FLMx mx_;                  // ... or, cp_.kind == FL_COMPRESS_MX, fl_mx_kernel
+    bool compress_random() const {
+        return cp_.kind == FL_COMPRESS_QSGD || cp_.kind == FL_COMPRESS_RANDK || (cp_.kind == FL_COMPRESS_MX && mx_.stochastic);
+    }
     FLServer sv_;              // server optimizer: fl_server_kernel after every round's aggregation
     FLHeldout ho_ = {};        // held-out scoring: fl_heldout row + fold launches at the end of every round
     FLAuc au_ = {};            // ... and, keys != nullptr, fl_auc's key + rank launches behind them
@@ -1727,6 +1762,34 @@ static void lowrank_launch(std::vector<int> dims, int rank, bool error_feedback,
                                 as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
 }
 
+// One fl_mx launch on caller-owned buffers of the image of `dims` (tests, tools): `residual` and `stat` as
+// compress_launch's.  `conv`: -1 = the conversion path the kernel file chose for (fmt, rounding), 0 = integer
+// code, 1 = the scaled conversion instructions (nearest only).
+static void mx_launch(std::vector<int> dims, int fmt, bool stochastic, bool error_feedback, uintptr_t local, uintptr_t x,
+                      uintptr_t comm, uintptr_t residual, uintptr_t stat, uintptr_t state, uintptr_t rtab, int max_rounds,
+                      uintptr_t stream, int client, unsigned long long seed, int conv) {
+    const MLPDesc d = desc_of(dims, "mx_launch");
+    if (fmt < FL_MX_E4M3 || fmt > FL_MX_E2M1) throw std::runtime_error("mx_launch: fmt must be 0 (e4m3), 1 (e5m2) or 2 (e2m1)");
+    if (conv < -1 || conv > 1 || (conv == 1 && stochastic))
+        throw std::runtime_error("mx_launch: conv must be -1, 0 or 1 (1: nearest only)");
+    if (max_rounds < 1 || !local || !x || !comm || !residual || !stat || !state || !rtab)
+        throw std::runtime_error("mx_launch: bad arguments");
+    FLMx p;
+    std::memset(&p, 0, sizeof(p));
+    p.fmt = fmt;
+    p.stochastic = stochastic ? 1 : 0;
+    p.error_feedback = error_feedback ? 1 : 0;
+    p.max_rounds = max_rounds;
+    p.client = client;
+    p.key0 = (uint32_t)seed;
+    p.key1 = (uint32_t)(seed >> 32);
+    p.conv = conv;
+    p.residual = as_ptr<float>(residual);
+    p.stat_hist = as_ptr<float>(stat);
+    HIP_CHECK(fl_launch_mx(d, p, as_ptr<const float>(local), as_ptr<const float>(x), as_ptr<float>(comm),
+                           as_ptr<const FLState>(state), as_ptr<const float>(rtab), as_stream(stream)));
+}
+
 #ifndef FEDMI_SRC_DIGEST
 #define FEDMI_SRC_DIGEST "unknown"
 #endif
@@ -1852,6 +1915,12 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"), py::arg("q"), py::arg("stat"),
           py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
     m.attr("LOWRANK_MAX_RANK") = (int)FL_LOWRANK_MAX_RANK;
+    m.def("mx_launch", &mx_launch, py::arg("dims"), py::arg("fmt"), py::arg("stochastic"), py::arg("error_feedback"),
+          py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"), py::arg("stat"), py::arg("state"),
+          py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("client") = 0, py::arg("seed") = 0ull,
+          py::arg("conv") = -1);
+    m.attr("MX_STREAM") = (unsigned)FL_MX_STREAM;
+    m.attr("COMPRESS_MX") = (int)FL_COMPRESS_MX;
     m.def("secagg_mask", &secagg_mask, py::arg("dims"), py::arg("bits"), py::arg("seed"), py::arg("bufs"), py::arg("n"),
           py::arg("first_client"), py::arg("state"), py::arg("rtab"), py::arg("clamp"), py::arg("max_rounds"),
           py::arg("stream"));

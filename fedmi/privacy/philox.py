@@ -22,7 +22,9 @@ RANDK_STREAM = 0x4B444E52
 # layout with the bad client's index in the rank word, Box-Muller normals like the DP noise.  Distinct from the
 # streams above and from the pair masks' (fedmi/fl/secagg.py SECAGG_STREAM = 0x47414353).
 ATTACK_STREAM = 0x4B435441
-assert len({DP_STREAM, QSGD_STREAM, RANDK_STREAM, ATTACK_STREAM, 0x47414353}) == 5
+# Stream of the block-scaled quantiser's stochastic rounding (fedmi/fl/compress.py "mx"; FL_MX_STREAM, "MXS4")
+MX_STREAM = 0x3453584D
+assert len({DP_STREAM, QSGD_STREAM, RANDK_STREAM, ATTACK_STREAM, MX_STREAM, 0x47414353}) == 6
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9

@@ -38,6 +38,12 @@ NEW_CASES = [("qsgd-127", dict(compress="qsgd", compress_levels=127, compress_se
 # low-rank factors next to the two kernels they are placed against (same session)
 LOWRANK_CASES = [("classic", {}), ("sign", dict(compress="sign")), ("topk-10%", dict(compress="topk", compress_ratio=0.1)),
                  *[(f"powersgd-r{r}", dict(compress="powersgd", compress_rank=r, compress_seed=1)) for r in (1, 4, 8)]]
+# block-scaled FP8 / FP4 elements next to the kernels they are placed against (same session)
+MX_CASES = [*CASES[:2], ("sign", dict(compress="sign")),
+            ("qsgd-127", dict(compress="qsgd", compress_levels=127, compress_seed=1)),
+            *[(f"mx-{f}-{r[:2]}", dict(compress="mx", compress_format=f, compress_rounding=r, compress_seed=1))
+              for f in ("e4m3", "e5m2", "e2m1") for r in ("nearest", "stochastic")]]
+MX_CONV = [(f"mx-{f}", dict(compress="mx", compress_format=f)) for f in ("e4m3", "e5m2", "e2m1")]
 LOWRANK_CONV = [(f"powersgd-r{r}", dict(compress="powersgd", compress_rank=r, compress_seed=1)) for r in (1, 2, 4)]
 
 
@@ -48,13 +54,14 @@ def main():
     ap.add_argument("--backend", default="hip", help="--convergence: hip | torch")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compress_trace.jsonl"))
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
-    ap.add_argument("--cases", choices=["old", "new", "all", "lowrank"], default="all",
-                    help="old: classic, dp-clip, top-k, sign; new: qsgd, rand-k; lowrank: powersgd beside sign and top-k")
+    ap.add_argument("--cases", choices=["old", "new", "all", "lowrank", "mx"], default="all",
+                    help="old: classic, dp-clip, top-k, sign; new: qsgd, rand-k; lowrank: powersgd beside sign and top-k; "
+                         "mx: block-scaled elements beside dp-clip, sign and qsgd")
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--no-trace", action="store_true", help="--convergence only")
     a = ap.parse_args()
-    timed = {"old": CASES, "new": NEW_CASES, "all": CASES + NEW_CASES, "lowrank": LOWRANK_CASES}[a.cases]
-    conv = {"old": CASES[2:], "new": NEW_CASES, "all": CASES[2:] + NEW_CASES, "lowrank": LOWRANK_CONV}[a.cases]
+    timed = {"old": CASES, "new": NEW_CASES, "all": CASES + NEW_CASES, "lowrank": LOWRANK_CASES, "mx": MX_CASES}[a.cases]
+    conv = {"old": CASES[2:], "new": NEW_CASES, "all": CASES[2:] + NEW_CASES, "lowrank": LOWRANK_CONV, "mx": MX_CONV}[a.cases]
     so = os.environ.get("FEDMI_NATIVE_SO") or "tree"
     from fedmi.data.tabular import load_tabular
     from fedmi.fl.engine import EngineConfig, HipRoundEngine
@@ -92,7 +99,7 @@ def main():
             P = len(flat)
             emit({"what": "rounds_to_target", "clients": 8, "backend": a.backend, "case": name,
                   "uplink_bytes": uplink_bytes(cfg.compress, compress_k(cfg, P, [X.shape[1], 50, 200, 2]), P,
-                                               cfg.compress_levels), **res})
+                                               cfg.compress_levels, cfg.compress_format), **res})
     out.close()
 
 
