@@ -67,6 +67,13 @@ def parse_args(argv=None):
                     help="differential privacy: L2 bound S of every client's round update (0 = off)")
     ap.add_argument("--dp-noise", type=float, default=0.0,
                     help="differential privacy: noise multiplier z (needs --dp-clip; 0 = clipping only)")
+    ap.add_argument("--dpsgd-clip", type=float, default=0.0,
+                    help="record-level DP-SGD: L2 bound C of every EXAMPLE's gradient in every local step (0 = off; "
+                         "fp32 engines; not with --wide or --dtype bf16)")
+    ap.add_argument("--dpsgd-noise", type=float, default=0.0,
+                    help="record-level DP-SGD: noise multiplier z (needs --dpsgd-clip; 0 = clipping only, no guarantee)")
+    ap.add_argument("--dpsgd-seed", type=int, default=None,
+                    help="DP-SGD noise seed for reproducible experiments (default: a private seed per client)")
     ap.add_argument("--dp-delta", type=float, default=1e-5, help="delta of the reported (epsilon, delta)")
     ap.add_argument("--dp-seed", type=int, default=None,
                     help="noise seed for reproducible experiments (default: a private seed per client)")
@@ -253,7 +260,8 @@ def _dataset(a, comm):
 
 
 def _dp_fields(a) -> dict:
-    return dict(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_seed=a.dp_seed)
+    return dict(dp_clip=a.dp_clip, dp_noise=a.dp_noise, dp_seed=a.dp_seed, dpsgd_clip=a.dpsgd_clip,
+                dpsgd_noise=a.dpsgd_noise, dpsgd_seed=a.dpsgd_seed)
 
 
 def _server_fields(a) -> dict:
@@ -294,6 +302,9 @@ def _print_privacy(a, rounds: int) -> None:
     if a.dp_clip > 0.0:
         from fedmi.privacy.accountant import privacy_statement
         print(privacy_statement(a.dp_noise, rounds, a.dp_delta), flush=True)
+    if a.dpsgd_clip > 0.0:
+        from fedmi.privacy.accountant import record_privacy_statement
+        print(record_privacy_statement(a.dpsgd_noise, rounds, a.local_steps, a.dp_delta), flush=True)
 
 
 def _print_heldout(a, h: dict) -> None:
@@ -372,6 +383,10 @@ def main(argv=None):
         raise SystemExit("--dp-noise needs --dp-clip > 0")
     if a.wide and a.dp_clip > 0.0:
         raise SystemExit("--dp-clip is not supported with --wide")
+    if a.dpsgd_noise > 0.0 and not a.dpsgd_clip > 0.0:
+        raise SystemExit("--dpsgd-noise needs --dpsgd-clip > 0")
+    if a.wide and a.dpsgd_clip > 0.0:
+        raise SystemExit("--dpsgd-clip is not supported with --wide")
     if a.wide and a.server_opt != "none":
         raise SystemExit("--server-opt is not supported with --wide")
     try:

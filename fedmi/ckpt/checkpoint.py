@@ -133,8 +133,11 @@ def save_checkpoint(path: str, trainer) -> None:
     dp = {} if "dp_seed" not in st else {
         "dp_seed": np.asarray([int(st["dp_seed"]) & 0xFFFFFFFF, int(st["dp_seed"]) >> 32], np.int64),
         "update_norm": np.asarray(st["history"]["update_norm"], np.float32)}
+    # record-level DP-SGD: the client's noise seed (two 32-bit words, as dp_seed)
+    if "dpsgd_seed" in st:
+        dp["dpsgd_seed"] = np.asarray([int(st["dpsgd_seed"]) & 0xFFFFFFFF, int(st["dpsgd_seed"]) >> 32], np.int64)
     # server optimizer: every rank holds the same replicated m / v; each client's file carries its copy
-    sv = {} if "server_m" not in st else {"server_m": np.asarray(st["server_m"], np.float32),
+    sv ={} if "server_m" not in st else {"server_m": np.asarray(st["server_m"], np.float32),
                                           "server_v": np.asarray(st["server_v"], np.float32)}
     # compression: the client's own residual (dense order) and its per-round statistic
     cp = {} if "compress_residual" not in st else {
@@ -238,6 +241,9 @@ def resume(path: str, trainer) -> int:
         lo, hi = (int(x) for x in np.asarray(c["dp_seed"]).reshape(-1)[:2])
         st["dp_seed"] = lo | (hi << 32)
         st["history"]["update_norm"] = np.asarray(c["update_norm"], np.float32)
+    if "dpsgd_seed" in c:
+        lo, hi = (int(x) for x in np.asarray(c["dpsgd_seed"]).reshape(-1)[:2])
+        st["dpsgd_seed"] = lo | (hi << 32)
     if "server_m" in c:
         st["server_m"], st["server_v"] = np.asarray(c["server_m"], np.float32), np.asarray(c["server_v"], np.float32)
     if "compress_residual" in c:

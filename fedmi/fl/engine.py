@@ -126,6 +126,21 @@ class EngineConfig:
     dp_clip: float = 0.0
     dp_noise: float = 0.0
     dp_seed: Optional[int] = None
+    # Record-level DP-SGD (Abadi et al. 2016; fedmi/privacy/dpsgd.py, fl_train_dpsgd.hip): in every local
+    # step each EXAMPLE's whole gradient is clipped to ||g_r||_2 <= dpsgd_clip, and N(0, (dpsgd_noise *
+    # dpsgd_clip)^2 I) is added to the sum before the 1 / n, so Adam sees sum_r min(1, C / ||g_r||) g_r / n +
+    # z C / n N(0, I).  Weight decay and the FedProx term are added after clipping (they do not depend on the
+    # data).  dpsgd_clip = 0: off (nothing of a round changes).  dpsgd_noise needs dpsgd_clip > 0; dpsgd_noise =
+    # 0 is clipping only (no guarantee).  dpsgd_seed: None = a private 64-bit seed per rank from os.urandom (kept
+    # in the portable state), an int = reproducible runs.  What the guarantee of
+    # fedmi.privacy.accountant.epsilon_record_level covers: the model updates, i.e. everything that leaves the
+    # client through the weights.  What it does NOT cover: the loss history, the confusion counts / metrics on
+    # the training shard, and row_grad_norms() -- exact functions of the rows; do not publish them.  The rounds
+    # keep their kind (fused one-client rounds included).  fp32 HIP kernels and the torch engine; not with
+    # dtype="bf16", trial batches (comm_buffers), fed_sweep, WideClient or the sklearn estimator.
+    dpsgd_clip: float = 0.0
+    dpsgd_noise: float = 0.0
+    dpsgd_seed: Optional[int] = None
     # Server optimizer (Hsu et al. 2019, FedAvgM; Reddi et al. 2021, FedAdagrad / FedAdam / FedYogi):
     # with x the image a round trained from and a its aggregated image (after the all-reduce, so
     # after DP clip + noise), d = a - x is a pseudo-gradient and the next global image is
@@ -270,6 +285,10 @@ class EngineConfig:
             # (another rule: a checkpoint's config record is what it was before the cclip fields existed)
             for k in ("cclip_tau", "cclip_iters"):
                 del d[k]
+        if not float(self.dpsgd_clip) > 0.0 and not float(self.dpsgd_noise) > 0.0 and self.dpsgd_seed is None:
+            # (off: a checkpoint's config record is what it was before the DP-SGD fields existed)
+            for k in ("dpsgd_clip", "dpsgd_noise", "dpsgd_seed"):
+                del d[k]
         if self.attack == "none":
             # (off: a checkpoint's config record is what it was before the attack fields existed)
             for k in ("attack", "attack_clients", "attack_scale", "attack_z", "attack_seed"):
@@ -307,6 +326,22 @@ def dp_enabled(cfg: EngineConfig) -> bool:
     if cfg.dp_seed is not None and not (0 <= int(cfg.dp_seed) < 2 ** 64):
         raise ValueError(f"dp_seed must be None or an integer in [0, 2**64), got {cfg.dp_seed!r}")
     return S > 0.0
+
+
+def dpsgd_enabled(cfg: EngineConfig) -> bool:
+    """Validate the DP-SGD fields; True when per-example clipping is on (``dpsgd_clip > 0``)."""
+    C, z = float(cfg.dpsgd_clip), float(cfg.dpsgd_noise)
+    if not (math.isfinite(C) and C >= 0.0):
+        raise ValueError(f"dpsgd_clip must be a finite number >= 0, got {cfg.dpsgd_clip!r}")
+    if not (math.isfinite(z) and z >= 0.0):
+        raise ValueError(f"dpsgd_noise must be a finite number >= 0, got {cfg.dpsgd_noise!r}")
+    if z > 0.0 and C == 0.0:
+        raise ValueError("dpsgd_noise > 0 needs dpsgd_clip > 0 (the noise is scaled by the clipping bound)")
+    if cfg.dpsgd_seed is not None and not (0 <= int(cfg.dpsgd_seed) < 2 ** 64):
+        raise ValueError(f"dpsgd_seed must be None or an integer in [0, 2**64), got {cfg.dpsgd_seed!r}")
+    if C > 0.0 and cfg.dtype == "bf16":
+        raise ValueError("dpsgd_clip > 0 does not run with dtype='bf16': the per-example clipping kernel is fp32")
+    return C > 0.0
 
 
 SERVER_OPTS = ("none", "sgd", "adagrad", "adam", "yogi")
@@ -567,6 +602,10 @@ class RoundEngineBase:
                  init_flat: np.ndarray, n_total: Optional[int] = None, client_sizes=None):
         self.cfg = cfg
         self.dp = dp_enabled(cfg)
+        self.dpsgd = dpsgd_enabled(cfg)    # record-level DP-SGD: per-example clipping inside every local step
+        if self.dpsgd:
+            self.dpsgd_seed = (int.from_bytes(os.urandom(8), "little") if cfg.dpsgd_seed is None
+                               else int(cfg.dpsgd_seed))
         self.server = server_opt_id(cfg)   # index in SERVER_OPTS; 0 = plain FedAvg
         self.compress = compress_id(cfg)   # index in ALL_COMPRESSORS; 0 = dense contributions
         # the stochastic kinds carry one more piece of state: the client's seed (config, or a private draw)
@@ -918,6 +957,20 @@ class RoundEngineBase:
     def _set_dp_seed(self, seed: int) -> None:
         self.dp_seed = int(seed)
 
+    def _load_dpsgd_seed(self, st: dict) -> None:
+        """A resumed DP-SGD engine continues the checkpoint's noise stream, as :meth:`_load_dp_seed`."""
+        if self.dpsgd and st.get("dpsgd_seed") is not None:
+            self._set_dpsgd_seed(int(st["dpsgd_seed"]))
+
+    def _set_dpsgd_seed(self, seed: int) -> None:
+        self.dpsgd_seed = int(seed)
+
+    def row_grad_norms(self) -> np.ndarray:
+        """fp32 ``[n_rows]``: every row's pre-clip gradient norm ``||g_r||_2`` in the last train launch of a
+        DP-SGD engine (``dpsgd_clip > 0``) -- the number to choose ``dpsgd_clip`` from (e.g. its median).
+        An exact function of the rows: NOT covered by the privacy guarantee."""
+        raise NotImplementedError
+
     def _load_compress_seed(self, st: dict) -> None:
         """A resumed engine with a stochastic compressor continues the checkpoint's stream (a private
         seed drawn at construction is replaced by the saved one)."""
@@ -1030,11 +1083,14 @@ class TorchRoundEngine(RoundEngineBase):
         self.model.train()
         anchor = self.model.flat.detach().clone() if self.cfg.prox_mu else None
         loss_v = 0.0
-        for _ in range(self.cfg.local_steps):
+        for ls in range(self.cfg.local_steps):
             self.optimizer.zero_grad()
-            out = self.model(self.X)
-            loss = self.criterion(out, self.y)
-            loss.backward()
+            if self.dpsgd:
+                loss = self._dpsgd_backward(ls)
+            else:
+                out = self.model(self.X)
+                loss = self.criterion(out, self.y)
+                loss.backward()
             if anchor is not None:
                 with torch.no_grad():
                     for (name, shape, off), p in zip(self.model.layout, self.model.parameters()):
@@ -1044,6 +1100,28 @@ class TorchRoundEngine(RoundEngineBase):
             loss_v = float(loss.detach())
         self._scheduler_step()
         return loss_v
+
+    def _dpsgd_backward(self, ls: int) -> torch.Tensor:
+        """Record-level DP-SGD: the parameters' ``.grad`` become the clipped per-example sum over ``n`` (ghost
+        norms, fedmi/privacy/dpsgd.py) plus ``z C / n`` times the device's noise stream of (round, local step,
+        rank); returns the mean loss."""
+        from ..privacy.dpsgd import ghost_clipped_grad
+        from ..privacy.philox import dpsgd_normals
+        C, z = float(self.cfg.dpsgd_clip), float(self.cfg.dpsgd_noise)
+        flat = self.model.flat.detach()
+        norms, grad, loss = ghost_clipped_grad(flat, self.dims, self.X, self.y, C)
+        self._row_norms = norms.detach().cpu().numpy().astype(np.float32)
+        if z > 0.0:
+            xi = dpsgd_normals(self.P, self.rounds_issued, ls, self.rank, self.dpsgd_seed)
+            grad = grad + torch.as_tensor(xi * (z * C / float(self.n_local))).to(grad.dtype).to(grad.device)
+        for (name, shape, off), p in zip(self.model.layout, self.model.parameters()):
+            p.grad = grad[off:off + int(np.prod(shape))].view(shape).clone()
+        return loss
+
+    def row_grad_norms(self) -> np.ndarray:
+        if not self.dpsgd or getattr(self, "_row_norms", None) is None:
+            raise RuntimeError("row_grad_norms: needs dpsgd_clip > 0 and a train step")
+        return self._row_norms.copy()
 
     def _scheduler_step(self) -> None:
         """StepLR follows the global round index (C:73 steps it once per round) for every
@@ -1459,6 +1537,7 @@ class TorchRoundEngine(RoundEngineBase):
                    "stopped": bool(sp.stopped), "stop_round": int(self.hist.stop_round)},
             "history": self.hist.as_dict(),
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
+            **({"dpsgd_seed": int(self.dpsgd_seed)} if self.dpsgd else {}),
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
             **self._compress_state_out(self.compress_residual.numpy().copy() if self.compress else None,
@@ -1513,6 +1592,7 @@ class TorchRoundEngine(RoundEngineBase):
         self.rounds_issued = r
         self._load_history(st["history"])
         self._load_dp_seed(st)
+        self._load_dpsgd_seed(st)
         self._load_compress_seed(st)
 
 
@@ -1544,6 +1624,8 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError(f"HipRoundEngine: at most {MAX_LOCAL_STEPS} local steps per round (got {cfg.local_steps})")
         if cfg.compress != "none" and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run compression (compress={cfg.compress!r})")
+        if dpsgd_enabled(cfg) and comm_buffers is not None:
+            raise ValueError("trial packing (comm_buffers) does not run record-level DP-SGD (dpsgd_clip > 0)")
         if screen_id(cfg, comm.size if comm is not None else 1) and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run client screening (screen={cfg.screen!r})")
         if cfg.aggregator != "mean" and comm_buffers is not None:
@@ -1674,6 +1756,12 @@ class HipRoundEngine(RoundEngineBase):
             ecfg.update({"dp_clip": float(cfg.dp_clip), "dp_noise": float(cfg.dp_noise) > 0.0,
                          "dp_seed": int(self.dp_seed)})
             bufs.update({"dp_sigma": self.dp_sigma_dev.data_ptr(), "dp_norm": self.dp_norm.data_ptr()})
+        if self.dpsgd:
+            # per-example clipping train kernel (fl_train_dpsgd.hip): every row's pre-clip norm of the last launch
+            self.dpsgd_row_norm = torch.zeros(self.n_local, **f32)
+            ecfg.update({"dpsgd_clip": float(cfg.dpsgd_clip), "dpsgd_noise": float(cfg.dpsgd_noise),
+                         "dpsgd_seed": int(self.dpsgd_seed)})
+            bufs["dpsgd_row_norm"] = self.dpsgd_row_norm.data_ptr()
         if self.compress:
             # residual: two image-shaped fp32 halves, round r reads half r & 1 and writes half (r + 1) & 1
             # (fl_compress.hip); the per-round statistic
@@ -1722,7 +1810,8 @@ class HipRoundEngine(RoundEngineBase):
             # rows sized for the longest row the engine may choose (the blocked row of the reference shape)
             # (an older library loaded through FEDMI_NATIVE_SO for an A/B knows the dense row only)
             row = self.m.slab_row_floats(self.dims, R) if hasattr(self.m, "slab_row_floats") else ((self.P + 1) + 3) & ~3
-            self.slab = torch.zeros(((self.n_local + R - 1) // R) * row, **f32)
+            # (DP-SGD: one row more, the noise workgroup's)
+            self.slab = torch.zeros(((self.n_local + R - 1) // R + int(self.dpsgd)) * row, **f32)
             ecfg["R"] = R
             bufs["slab"] = self.slab.data_ptr()
             bufs["slab_floats"] = self.slab.numel()
@@ -2503,6 +2592,7 @@ class HipRoundEngine(RoundEngineBase):
                    "stop_round": int(st["stop_round"])},
             "history": self.hist.as_dict(),
             **({"dp_seed": int(self.dp_seed)} if self.dp else {}),
+            **({"dpsgd_seed": int(self.dpsgd_seed)} if self.dpsgd else {}),
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
             **self._compress_state_out(self.compress_residual if self.compress else None,
@@ -2591,6 +2681,7 @@ class HipRoundEngine(RoundEngineBase):
                 self.ho_best.copy_(torch.as_tensor(words, device=dev))
         self.stream.synchronize()
         self._load_dp_seed(st)
+        self._load_dpsgd_seed(st)
         self._load_compress_seed(st)
         self.engine.invalidate()
         self.engine.reset_pending()
@@ -2601,6 +2692,17 @@ class HipRoundEngine(RoundEngineBase):
         self.dp_seed = int(seed)
         self.engine.set_dp_seed(int(seed))   # a kernel argument: the native engine drops its graphs
         self._graph_ready = False
+
+    def _set_dpsgd_seed(self, seed: int) -> None:
+        self.dpsgd_seed = int(seed)
+        self.engine.set_dpsgd_seed(int(seed))   # a kernel argument: the native engine drops its graphs
+        self._graph_ready = False
+
+    def row_grad_norms(self) -> np.ndarray:
+        if not self.dpsgd:
+            raise RuntimeError("row_grad_norms: needs dpsgd_clip > 0")
+        self.stream.synchronize()
+        return self.dpsgd_row_norm.cpu().numpy().copy()
 
     def _set_compress_seed(self, seed: int) -> None:
         self.compress_seed = int(seed)

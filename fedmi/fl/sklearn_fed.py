@@ -15,6 +15,14 @@ import numpy as np
 import torch
 
 
+def refuse_dpsgd(cfg) -> None:
+    """The scikit-learn-style estimators ([S] / [H] flows) train with their own float64 step kernels, which
+    have no per-example clipping: a configuration that asks for record-level DP-SGD is refused."""
+    if float(getattr(cfg, "dpsgd_clip", 0.0)) > 0.0 or float(getattr(cfg, "dpsgd_noise", 0.0)) > 0.0:
+        raise ValueError("the sklearn estimator does not run record-level DP-SGD (dpsgd_clip / dpsgd_noise); "
+                         "use the round engines (EngineConfig.dpsgd_clip)")
+
+
 def _allreduce_np(x: np.ndarray, comm) -> np.ndarray:
     if comm is None or comm.size == 1:
         return x

@@ -43,7 +43,12 @@ class WideClient:
                  step_size: int = 30, gamma: float = 0.5, seed: int = 0, dtype: str = "bf16",
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
                  fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
-                 compress: str = "none", secagg: bool = False, screen: str = "none", attack: str = "none"):
+                 compress: str = "none", secagg: bool = False, screen: str = "none", attack: str = "none",
+                 dpsgd_clip: float = 0.0):
+        if float(dpsgd_clip) > 0.0:
+            # the wide path's layered GEMMs never hold a row's whole gradient, nor all layers' operands at once
+            raise ValueError(f"WideClient does not run record-level DP-SGD (dpsgd_clip={dpsgd_clip!r}); "
+                             "use the round engines (EngineConfig.dpsgd_clip)")
         if attack != "none":
             # the wide path all-reduces its buckets: nothing holds the individual contributions, and its
             # caller hands it the shard as it is, so nothing flips a bad client's labels either

@@ -85,6 +85,10 @@ class FedTrialGroup:
             # the trials of a group share launches and one collective; a private sweep would also
             # have to account for every trial's rounds (fedmi/privacy/accountant.py)
             raise ValueError("fed_sweep does not run differentially private trials (dp_clip / dp_noise)")
+        if float(getattr(base, "dpsgd_clip", 0.0)) > 0.0 or float(getattr(base, "dpsgd_noise", 0.0)) > 0.0:
+            # the batched train kernels have no per-example clipping, and a private sweep would have to
+            # account for every trial's steps
+            raise ValueError("fed_sweep does not run record-level DP-SGD trials (dpsgd_clip / dpsgd_noise)")
         if base.server_opt != "none":
             # the trials share launches and one collective; a server step per trial is not batched
             raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")

@@ -289,6 +289,18 @@ struct FLDp {
     float* norm_hist;    // [max_rounds] pre-clip ||local - input||_2 of this client (0: not sampled)
 };
 
+// Record-level DP-SGD (fl_train_dpsgd.hip): parameters of the per-example clipping train kernel, passed to
+// that kernel alone.  Its launch has one workgroup more than the shard has row blocks (FLConfig::n_slabs
+// counts it): the last one writes a slab row of noise, dense parameter p taking lane p % 4 of the Box-Muller
+// pairs of Philox4x32-10 at counter (p / 4, round, rank | local_step << 16, FL_DPSGD_STREAM).
+#define FL_DPSGD_STREAM 0x53504452u  // "RDPS": distinct from the DP, compressor, attack, MX and pair-mask streams
+struct FLDpSgd {
+    float clip;          // L2 bound C of one example's whole gradient (> 0)
+    float noise;         // noise multiplier z (>= 0): the noise row is z C / n N(0, I)
+    uint32_t key0, key1; // Philox key: the engine's 64-bit DP-SGD seed, low and high word
+    float* row_norm;     // [n_rows] pre-clip ||g_r||_2 of the last train launch
+};
+
 // Server optimizer (fl_server.hip): parameters of the per-round server step, passed to that
 // kernel alone, as FLDp is.  With x the image the round trained from, a the aggregated image and
 // d = a - x, the kernel keeps m (and, adaptive kinds, v) across rounds and replaces a by
@@ -595,6 +607,12 @@ hipError_t fl_launch_train_spec(const FLConfig& c, const FLBuffers& b, const flo
                                 FLState* st_out, int local_step, hipStream_t s, int mode, float* cm_out,
                                 int fold_mask);
 hipError_t fl_set_lds_limit_spec(size_t bytes);
+// (fl_train_dpsgd.hip: the fp32 train kernel with per-example clipping and a noise row; c.n_slabs counts
+// the noise workgroup, the slab has that many rows)
+hipError_t fl_launch_train_dpsgd(const MLPDesc& d, const FLConfig& c, const FLBuffers& b, const FLDpSgd& p,
+                                 const float* pg, const FLState* st_in, FLState* st_out, int local_step,
+                                 hipStream_t s, int mode, float* cm_out, int fold_mask);
+hipError_t fl_set_lds_limit_dpsgd(size_t bytes);
 // `st` = state the step runs under; with `fold` (FL_EVAL_FUSED rounds, first local step) it
 // is the previous round's state: every block folds pg's tail into it, block 0 writes the
 // round's state to `st_out`.

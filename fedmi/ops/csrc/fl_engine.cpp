@@ -300,6 +300,27 @@ class FLEngine {
             if (dp_.sigma == nullptr || dp_.norm_hist == nullptr)
                 throw std::runtime_error("FLEngine: DP needs the sigma table and the norm history");
         }
+        // Record-level DP-SGD (fl_train_dpsgd.hip): every train launch is the per-example clipping kernel, with
+        // one workgroup and one slab row more (the noise row); the Adam kernels reduce c_.n_slabs rows as ever.
+        // The round kind does not change: what the optimizer sees is still a gradient.
+        std::memset(&ds_, 0, sizeof(ds_));
+        ds_.clip = cfg.contains("dpsgd_clip") ? cfg["dpsgd_clip"].cast<float>() : 0.f;
+        if (ds_.clip > 0.f) {
+            if (dtype_ != 0) throw std::runtime_error("FLEngine: record-level DP-SGD runs the fp32 kernels only");
+            const unsigned long long seed = cfg["dpsgd_seed"].cast<unsigned long long>();
+            ds_.noise = cfg["dpsgd_noise"].cast<float>();
+            ds_.key0 = (uint32_t)seed;
+            ds_.key1 = (uint32_t)(seed >> 32);
+            ds_.row_norm = as_ptr<float>(bufs["dpsgd_row_norm"].cast<uintptr_t>());
+            if (!(ds_.noise >= 0.f) || ds_.row_norm == nullptr)
+                throw std::runtime_error("FLEngine: DP-SGD needs a noise multiplier >= 0 and the row-norm buffer");
+            if (c_.rank > 0xFFFF) throw std::runtime_error("FLEngine: DP-SGD packs the rank into 16 bits of the noise counter");
+            const long long have = bufs.contains("slab_floats") ? bufs["slab_floats"].cast<long long>() : 0;
+            if (have < (long long)(c_.n_slabs + 1) * c_.slab_stride)
+                throw std::runtime_error("FLEngine: DP-SGD needs one slab row more than the shard has row blocks");
+            c_.n_slabs += 1;
+            HIP_CHECK(fl_set_lds_limit_dpsgd((size_t)lds * 4));
+        }
         std::memset(&lr_, 0, sizeof(lr_));
         std::memset(&mx_, 0, sizeof(mx_));
         if (cp_.kind == FL_COMPRESS_POWERSGD) {
@@ -689,6 +710,15 @@ class FLEngine {
         drop_graph();
     }
 
+    // Noise key of a DP-SGD engine (resume: the checkpoint's stream continues); a kernel argument, so
+    // captured graphs are dropped.
+    void set_dpsgd_seed(unsigned long long seed) {
+        if (!(ds_.clip > 0.f)) throw std::runtime_error("set_dpsgd_seed: record-level DP-SGD is off");
+        ds_.key0 = (uint32_t)seed;
+        ds_.key1 = (uint32_t)(seed >> 32);
+        drop_graph();
+    }
+
     // Philox key of a stochastic compressor (resume: the checkpoint's stream continues); a kernel
     // argument, so captured graphs are dropped.
     void set_compress_seed(unsigned long long seed) {
@@ -989,7 +1019,7 @@ class FLEngine {
         o["plain_fwd"] = c_.plain_fwd != 0;              // plain-bf16 training forward (several clients)
         o["split_score"] = c_.split_score != 0;          // lagged scoring on workgroups of its own
         // the train kernel of classic / fused rounds is the reference shape's specialised one
-        o["shape_spec"] = shape_spec_on_ && (dtype_ == 1 ? fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED)
+        o["shape_spec"] = shape_spec_on_ && !(ds_.clip > 0.f) && (dtype_ == 1 ? fl_train_bf16_spec_ok(d_, e_, c_, FL_EVAL_FUSED)
                                                          : fl_train_spec_ok(d_, c_, FL_EVAL_FUSED));
         o["adam_spec"] = adam_spec_ok();  // the Adam kernel of those rounds is the specialised one
         o["eval_fedavg"] = peer_ != nullptr && !tr_.fused && tr_.eval_fedavg_fits;
@@ -1009,6 +1039,7 @@ class FLEngine {
         o["tail_len"] = c_.tail_len;
         o["comm_len"] = comm_len_;
         o["lagged_eval"] = lagged();
+        o["dpsgd"] = ds_.clip > 0.f;                       // per-example clipping train kernel + noise slab row
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
         {
             // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
@@ -1111,7 +1142,9 @@ class FLEngine {
                 HIP_CHECK(fl_launch_pack_bf16(d_, e_, F(0), (char*)F(1), s));
                 break;
             case FLLaunchRec::TRAIN:
-                if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3],
+                if (ds_.clip > 0.f)  // (fp32 only; never the shape-specialised kernel)
+                    HIP_CHECK(fl_launch_train_dpsgd(d_, c_, b_, ds_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3]));
+                else if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3],
                                                               shape_spec_on_));
                 else
                     HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
@@ -1246,6 +1279,7 @@ class FLEngine {
     PeerSelect sel_;                 // mode != 0: the peer call selects (robust rule) or opens (secure aggregation)
     uint32_t* sa_clamp_ = nullptr;   // secure aggregation: this client's clamp history [max_rounds] (caller-owned)
     void** sa_tab_ = nullptr;        // ... device pointer tables of the mask launch: {send 0, send 1, clamp history}
+    FLDpSgd ds_;               // record-level DP-SGD (clip > 0): every TRAIN launch is fl_train_dpsgd_kernel
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLLowRank lr_;             // ... or, cp_.kind == FL_COMPRESS_POWERSGD, fl_lowrank_kernel in its place
@@ -1315,6 +1349,7 @@ class TrialBatch {
             if (e.tr_.server_on) throw std::runtime_error("TrialBatch: no server optimizer (server_opt)");
             if (e.tr_.compress_on) throw std::runtime_error("TrialBatch: no compression (compress)");
             if (e.tr_.heldout_on) throw std::runtime_error("TrialBatch: no held-out scoring (set_heldout)");
+            if (e.ds_.clip > 0.f) throw std::runtime_error("TrialBatch: no record-level DP-SGD (dpsgd_clip)");
             // the batch kernels write and read dense slab rows: from here on the engine's own launches do
             // too (the row stride stays; train / Adam pairs are issued together, so no pair is split)
             engs_[k]->slab_blocked_ = false;
@@ -1852,6 +1887,7 @@ PYBIND11_MODULE(_fedmi_hip, m) {
              py::arg("pred"), py::arg("stream"))
         .def("invalidate", &FLEngine::invalidate)
         .def("set_dp_seed", &FLEngine::set_dp_seed)
+        .def("set_dpsgd_seed", &FLEngine::set_dpsgd_seed)
         .def("set_compress_seed", &FLEngine::set_compress_seed)
         .def("packed_global", &FLEngine::packed_global)
         .def("packed_local", &FLEngine::packed_local)

@@ -74,3 +74,25 @@ def privacy_statement(noise_multiplier: float, rounds: int, delta: float) -> str
     eps = epsilon_closed_form(noise_multiplier, rounds, delta)
     return (f"Differential privacy: epsilon = {eps:.4g} at delta = {float(delta):g} over {int(rounds)} rounds "
             f"(noise multiplier {float(noise_multiplier):g}; client-level, no subsampling amplification)")
+
+
+def epsilon_record_level(noise_multiplier: float, rounds: int, local_steps: int, delta: float) -> float:
+    """Record-level epsilon of DP-SGD (``EngineConfig.dpsgd_clip`` / ``dpsgd_noise``): every optimizer step
+    is one Gaussian mechanism on the full-batch sum of the per-example gradients, each clipped to ``C``,
+    with noise of standard deviation ``z C``; adding or removing one row changes the sum by at most ``C``.
+    ``rounds * local_steps`` such steps compose (:func:`epsilon_rdp`).  Full batch: no subsampling
+    amplification.  Add/remove adjacency with the shard size ``n`` public (the mean divides by it)."""
+    if int(local_steps) < 1:
+        raise ValueError(f"local_steps must be >= 1, got {local_steps!r}")
+    return epsilon_rdp(noise_multiplier, int(rounds) * int(local_steps), delta)
+
+
+def record_privacy_statement(noise_multiplier: float, rounds: int, local_steps: int, delta: float) -> str:
+    """One line for the end of a DP-SGD run.  The figure covers the model updates -- what leaves the client
+    and everything computed from it.  It does NOT cover the loss history, the confusion counts on the
+    training shard or ``row_grad_norms()``: those are exact functions of the rows."""
+    eps = epsilon_record_level(noise_multiplier, rounds, local_steps, delta)
+    return (f"Record-level DP-SGD: epsilon = {eps:.4g} at delta = {float(delta):g} over "
+            f"{int(rounds) * int(local_steps)} steps (noise multiplier {float(noise_multiplier):g}; add/remove one "
+            f"row, n public, full batch; covers the model updates, not the loss history, training-shard "
+            f"metrics or row_grad_norms())")

@@ -24,7 +24,9 @@ RANDK_STREAM = 0x4B444E52
 ATTACK_STREAM = 0x4B435441
 # Stream of the block-scaled quantiser's stochastic rounding (fedmi/fl/compress.py "mx"; FL_MX_STREAM, "MXS4")
 MX_STREAM = 0x3453584D
-assert len({DP_STREAM, QSGD_STREAM, RANDK_STREAM, ATTACK_STREAM, MX_STREAM, 0x47414353}) == 6
+# Stream of the record-level DP-SGD noise row (fedmi/ops/csrc/fl_train_dpsgd.hip; FL_DPSGD_STREAM, "RDPS")
+DPSGD_STREAM = 0x53504452
+assert len({DP_STREAM, QSGD_STREAM, RANDK_STREAM, ATTACK_STREAM, MX_STREAM, DPSGD_STREAM, 0x47414353}) == 7
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9
@@ -96,4 +98,19 @@ def dp_normals(n_params: int, round_index: int, rank: int, seed: int) -> np.ndar
     ctr[:, 1] = int(round_index) & 0xFFFFFFFF
     ctr[:, 2] = int(rank) & 0xFFFFFFFF
     ctr[:, 3] = DP_STREAM
+    return box_muller(philox4x32_10(ctr, seed_key(seed))).reshape(-1)[:n_params]
+
+
+def dpsgd_normals(n_params: int, round_index: int, local_step: int, rank: int, seed: int) -> np.ndarray:
+    """Standard normals of the DP-SGD noise row (``fl_train_dpsgd.hip``) of dense parameters
+    ``0 .. n_params - 1`` for (round, local step, rank): parameter ``p`` takes lane ``p % 4`` of the
+    Box-Muller pairs of the block at counter ``(p // 4, round, rank | local_step << 16, DPSGD_STREAM)``
+    under ``seed_key(seed)``; float64.  Every local step of every round of every client is a fresh draw."""
+    n_params = int(n_params)
+    nq = (n_params + 3) // 4
+    ctr = np.empty((nq, 4), np.uint64)
+    ctr[:, 0] = np.arange(nq, dtype=np.uint64)
+    ctr[:, 1] = int(round_index) & 0xFFFFFFFF
+    ctr[:, 2] = ((int(rank) & 0xFFFF) | (int(local_step) << 16)) & 0xFFFFFFFF
+    ctr[:, 3] = DPSGD_STREAM
     return box_muller(philox4x32_10(ctr, seed_key(seed))).reshape(-1)[:n_params]
