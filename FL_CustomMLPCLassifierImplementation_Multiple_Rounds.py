@@ -67,6 +67,9 @@ def parse_args(argv=None):
                     help="differential privacy: L2 bound S of every client's round update (0 = off)")
     ap.add_argument("--dp-noise", type=float, default=0.0,
                     help="differential privacy: noise multiplier z (needs --dp-clip; 0 = clipping only)")
+    ap.add_argument("--scaffold", action="store_true",
+                    help="SCAFFOLD control variates (Karimireddy et al. 2020, option I): every local step's gradient gains "
+                         "c - c_i; several clients, fp32; also with --clients K (EngineConfig.scaffold)")
     ap.add_argument("--dpsgd-clip", type=float, default=0.0,
                     help="record-level DP-SGD: L2 bound C of every EXAMPLE's gradient in every local step (0 = off; "
                          "fp32 engines; not with --wide or --dtype bf16)")
@@ -345,6 +348,7 @@ def main_clients(a, comm):
     cfg = EngineConfig(hidden=tuple(a.hidden), lr=a.lr, step_size=a.step_size, gamma=a.gamma,
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds, seed=a.seed, dtype=a.dtype,
+                       scaffold=a.scaffold,
                        **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a), **_compress_fields(a),
                        **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a), **_attack_fields(a))
     backend = a.engine if a.engine != "auto" else ("hip" if comm.device.type == "cuda" else "torch")
@@ -387,6 +391,8 @@ def main(argv=None):
         raise SystemExit("--dpsgd-noise needs --dpsgd-clip > 0")
     if a.wide and a.dpsgd_clip > 0.0:
         raise SystemExit("--dpsgd-clip is not supported with --wide")
+    if a.wide and a.scaffold:
+        raise SystemExit("--scaffold is not supported with --wide")
     if a.wide and a.server_opt != "none":
         raise SystemExit("--server-opt is not supported with --wide")
     try:
@@ -453,7 +459,7 @@ def main(argv=None):
                        local_steps=a.local_steps, prox_mu=a.fedprox_mu, participation=a.participation, early_stop=not a.no_early_stop,
                        patience=a.patience, tolerance=a.tolerance, max_rounds=a.rounds,
                        rows_per_block=a.rows_per_block, graph_rounds=a.graph_rounds, seed=a.seed,
-                       debug=a.debug, dtype=a.dtype, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
+                       debug=a.debug, dtype=a.dtype, scaffold=a.scaffold, **_dp_fields(a), **_server_fields(a), **_aggregator_fields(a),
                        **_compress_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a),
                        **_attack_fields(a))
     trainer = FederatedMLPLearning(ds.X_train, ds.y_train, rank, size, comm=comm, hidden_sizes=a.hidden,

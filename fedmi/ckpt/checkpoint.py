@@ -139,6 +139,9 @@ def save_checkpoint(path: str, trainer) -> None:
     # server optimizer: every rank holds the same replicated m / v; each client's file carries its copy
     sv ={} if "server_m" not in st else {"server_m": np.asarray(st["server_m"], np.float32),
                                           "server_v": np.asarray(st["server_v"], np.float32)}
+    # SCAFFOLD: the replicated server variate c and the client's own control variate c_i (dense order)
+    if "scaffold_c" in st:
+        sv.update(scaffold_c=np.asarray(st["scaffold_c"], np.float32), scaffold_ci=np.asarray(st["scaffold_ci"], np.float32))
     # compression: the client's own residual (dense order) and its per-round statistic
     cp = {} if "compress_residual" not in st else {
         "compress_residual": np.asarray(st["compress_residual"], np.float32),
@@ -246,6 +249,10 @@ def resume(path: str, trainer) -> int:
         st["dpsgd_seed"] = lo | (hi << 32)
     if "server_m" in c:
         st["server_m"], st["server_v"] = np.asarray(c["server_m"], np.float32), np.asarray(c["server_v"], np.float32)
+    if "scaffold_c" in c:
+        st["scaffold_c"], st["scaffold_ci"] = np.asarray(c["scaffold_c"], np.float32), np.asarray(c["scaffold_ci"], np.float32)
+        if "scaffold_norm" in h:   # (the same on every rank: it rides the metadata's history)
+            st["history"]["scaffold_norm"] = np.asarray(h["scaffold_norm"], np.float32)
     if "compress_residual" in c:
         st["compress_residual"] = np.asarray(c["compress_residual"], np.float32)
         st["history"]["compress_stat"] = np.asarray(c["compress_stat"], np.float32)

@@ -219,6 +219,29 @@ class _AggLaunch:
                         self._n, *self._round(par), self._k * e.tail_stride, int(e.cfg.max_rounds), stream)
 
 
+class _ScaffoldLaunch:
+    """The SCAFFOLD control fold (``scaffold_fold``, fl_scaffold.hip) of one federation over buffers that keep
+    their addresses, launched after the model's aggregation.  ``lead``: the engine whose round state and ``rtab``
+    the launch uses; ``deltas``: the K clients' pending deltas in client order (a group's clients' buffers, or the
+    rows of a gathered stack); ``cs``: every replica of ``c`` the launch writes (the first is read); ``own``: the
+    engines whose ``c_i <- c_i + delta_i`` the launch commits, clients ``first ..``.  Owns the device pointer tables."""
+
+    def __init__(self, lead, deltas, cs, own, first: int = 0):
+        def table(ts):
+            return torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=lead.device)
+        self._lead, self._keep = lead, (deltas, cs, own)
+        self._k, self._n, self._first = len(deltas), len(cs), int(first)
+        self._src, self._dst = table(deltas), table(cs)
+        self._ci = table([e.sc_ci for e in own])
+        self._n_own = len(own)
+
+    def fold(self, par: int, stream: int) -> None:
+        e = self._lead
+        e.m.scaffold_fold(e.P, self._src.data_ptr(), self._k, e.world, self._dst.data_ptr(), self._n,
+                          self._ci.data_ptr(), self._n_own, self._first,
+                          e.state[par].data_ptr(), e.rtab.data_ptr(), int(e.cfg.max_rounds), stream)
+
+
 def _sort_keys(stack: torch.Tensor) -> torch.Tensor:
     """int64 keys whose order is the total order of the values: NaN above +inf, -0 == +0."""
     stack = stack.contiguous()

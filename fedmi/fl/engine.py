@@ -31,7 +31,7 @@ import torch
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
 from .aggregate import (AGGREGATOR_NAMES, AGGREGATORS, CCLIP_MAX_ITERS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS,
-                        _AggLaunch, cclip_torch, geomed_torch, mask_bits, pair_distances_torch,
+                        _AggLaunch, _ScaffoldLaunch, cclip_torch, geomed_torch, mask_bits, pair_distances_torch,
                         robust_aggregate_torch, screen_select)
 from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
                      attack_torch)
@@ -41,6 +41,7 @@ from .compress import (BLOCK_COMPRESSORS, COMPRESSORS, LOWRANK_COMPRESSORS, MX_F
 from .early_stop import EarlyStopper
 from .metrics import (METRIC_NAMES, auc_from_u2, auc_u2_model, confusion_matrix, metrics_from_confusion,
                       metric_vector)
+from .scaffold import scaffold_enabled, scaffold_fold
 from .secagg import (MAX_SECAGG_CLIENTS, SECAGG_STREAM, secagg_id, secagg_mask, secagg_open,
                      secagg_quantize)
 
@@ -276,11 +277,23 @@ class EngineConfig:
     attack_scale: float = 1.0
     attack_z: Optional[float] = None
     attack_seed: int = 0
+    # SCAFFOLD (Karimireddy et al. 2020, option I; fedmi/fl/scaffold.py, fl_scaffold.hip): every client keeps a
+    # control variate c_i, every replica the server variate c (both 0 at start); in every local step Adam sees
+    # g + (c - c_i), and after the model's aggregation, with delta_i = g0 - c_i of the sampled clients (g0: the full-batch
+    # gradient at the model the round trained from), c += (sum of the delta_i) / world and c_i += delta_i (g0 up to one rounding).  Weight decay and the FedProx term are
+    # added after the correction.  Rounds are classic and aggregated from Python; every client starts from one
+    # common model.  One client: off.  fp32 HIP kernels and the torch engines; not with dtype="bf16", dpsgd_clip,
+    # dp_clip, secagg, a robust aggregator, a screen, attack, compress, trial batches (comm_buffers), fed_sweep,
+    # WideClient, or more than 64 clients.  history()["scaffold_norm"]: ||c||_2 per round.
+    scaffold: bool = False
 
     def to_dict(self) -> dict:
         d = asdict(self)
         d["hidden"] = list(self.hidden)
         d["betas"] = list(self.betas)
+        if not self.scaffold:
+            # (off: a checkpoint's config record is what it was before the field existed)
+            del d["scaffold"]
         if self.aggregator != "cclip":
             # (another rule: a checkpoint's config record is what it was before the cclip fields existed)
             for k in ("cclip_tau", "cclip_iters"):
@@ -446,7 +459,9 @@ def attack_stage(cfg: EngineConfig, world: Optional[int] = None) -> bool:
 def common_init(cfg: EngineConfig) -> bool:
     """Every client starts from one model: a server optimizer, the attack stage and centered clipping all read
     the image a round trained from, which must be the same on every replica from round 0 on."""
-    return cfg.server_opt != "none" or cfg.attack in DEVICE_ATTACKS or cfg.aggregator == "cclip"
+    # (SCAFFOLD: the server variate c must mean the same thing on every replica from round 0 on)
+    return (cfg.server_opt != "none" or cfg.attack in DEVICE_ATTACKS or cfg.aggregator == "cclip"
+            or bool(getattr(cfg, "scaffold", False)))
 
 
 GATHER_PLANES = ("host", "xgmi")
@@ -532,6 +547,8 @@ class _History:
     # ... with auc=True: the doubled Mann-Whitney counts [max_rounds, C] and the set's positives per class
     ho_u2 = None
     ho_pos = None
+    # SCAFFOLD engines: the L2 norm of the server variate c after every round; None: off
+    scnorm = None
 
     def enable_heldout(self, n_classes: int, n_rows: int, auc_pos=None) -> None:
         if self.ho_cm is None:
@@ -581,6 +598,8 @@ class _History:
             out["secagg_clamped"] = self.clamped[:n].copy()
         if self.screen is not None:
             out["screen_kept"] = self.screen[:n].copy()
+        if self.scnorm is not None:
+            out["scaffold_norm"] = self.scnorm[:n].copy()
         if self.ho_cm is not None:
             out["heldout_cm"] = self.ho_cm[:n].copy()
             out["heldout_loss_sum"] = self.ho_loss[:n].copy()
@@ -673,6 +692,8 @@ class RoundEngineBase:
                                  "a screen, or ClientGroup")
         if self.attack_stage and client_sizes is not None:
             self._client_sizes = [int(n) for n in client_sizes]
+        # SCAFFOLD control variates (fedmi/fl/scaffold.py); one client: off
+        self.scaffold = scaffold_enabled(cfg, self.world)
         self.n_local = int(len(X))
         if self.n_local == 0:
             raise ValueError("client shard is empty (reference SURVEY Q12 would deadlock)")
@@ -687,6 +708,8 @@ class RoundEngineBase:
         self.tail_stride = self.n_classes * self.n_classes + 1
         self.hist = _History(cfg.max_rounds, self.world, dp=self.dp, compress=bool(self.compress),
                              secagg=bool(self.secagg), screen=bool(self.screen))
+        if self.scaffold:
+            self.hist.scnorm = np.zeros(max(1, int(cfg.max_rounds)), dtype=np.float32)
         # entries a contribution transmits (sign, dense: P; powersgd: factors and raw entries)
         self.compress_k = compress_k(cfg, self.P, self.dims)
         # the low-rank kind carries one more piece of state: Q of every compressed layer, from Q_0
@@ -939,6 +962,8 @@ class RoundEngineBase:
             self.hist.clamped[:n] = np.asarray(h["secagg_clamped"], dtype=np.int64).reshape(n)
         if self.hist.screen is not None and n and "screen_kept" in h:
             self.hist.screen[:n] = np.asarray(h["screen_kept"], dtype=np.uint64).reshape(n)
+        if self.hist.scnorm is not None and n and "scaffold_norm" in h:
+            self.hist.scnorm[:n] = np.asarray(h["scaffold_norm"], dtype=np.float32).reshape(n)
         if self.hist.ho_cm is not None:
             C = self.n_classes
             if n and "heldout_cm" in h:
@@ -970,6 +995,29 @@ class RoundEngineBase:
         DP-SGD engine (``dpsgd_clip > 0``) -- the number to choose ``dpsgd_clip`` from (e.g. its median).
         An exact function of the rows: NOT covered by the privacy guarantee."""
         raise NotImplementedError
+
+    def scaffold_variates(self):
+        """(c, c_i) of a SCAFFOLD engine as dense fp32 arrays: the server variate of this replica and the
+        client's own control variate."""
+        raise NotImplementedError
+
+    def _scaffold_state_out(self) -> dict:
+        if not self.scaffold:
+            return {}
+        c, ci = self.scaffold_variates()
+        return {"scaffold_c": c, "scaffold_ci": ci}
+
+    def _scaffold_state_in(self, st: dict):
+        """(c, c_i) of a state written by a SCAFFOLD engine, for this engine to adopt; None: this engine runs
+        without control variates."""
+        if not self.scaffold:
+            return None
+        if "scaffold_c" not in st or "scaffold_ci" not in st:
+            raise ValueError("load_portable_state: this engine runs SCAFFOLD, the state holds no control variates")
+        c, ci = (np.asarray(st[k], np.float32).reshape(-1) for k in ("scaffold_c", "scaffold_ci"))
+        if c.shape != (self.P,) or ci.shape != (self.P,):
+            raise ValueError(f"load_portable_state: control variates of {c.size} / {ci.size} floats, the model has {self.P}")
+        return c, ci
 
     def _load_compress_seed(self, st: dict) -> None:
         """A resumed engine with a stochastic compressor continues the checkpoint's stream (a private
@@ -1077,6 +1125,36 @@ class TorchRoundEngine(RoundEngineBase):
             self._compressed = (-1, None)   # (round, x + C(u)) of the last compressed round
             if self.compress_lowrank:
                 self.compress_q = torch.as_tensor(self._compress_q0.copy())
+        if self.scaffold:
+            # control variates in dense named_parameters() order; delta is pending until the fold
+            self.sc_c, self.sc_ci, self.sc_delta = (torch.zeros(self.P, dtype=torch.float32) for _ in range(3))
+
+    def _scaffold_correct(self, ls: int) -> None:
+        """SCAFFOLD: local step 0's gradient gives the pending ``delta = g0 - c_i``, and every step's
+        ``.grad`` gains ``c - c_i`` as they were at the round's start."""
+        params = list(self.model.parameters())
+        with torch.no_grad():
+            if ls == 0:
+                g0 = torch.cat([p.grad.detach().reshape(-1) for p in params]).to(torch.float32).cpu()
+                self.sc_delta = g0 - self.sc_ci
+            corr = self.sc_c - self.sc_ci
+            off = 0
+            for p in params:
+                p.grad.add_(corr[off:off + p.numel()].view_as(p).to(p.grad.dtype).to(p.device))
+                off += p.numel()
+
+    def scaffold_apply(self, r: int, deltas: Sequence[torch.Tensor]) -> None:
+        """The control fold of round ``r`` over every client's pending ``delta`` (client order; unsampled
+        clients' entries are not read): the new ``c``, and ``c_i <- c_i + delta_i`` when this client was sampled
+        (``g0`` up to one rounding, by the addition ``c`` takes: see fedmi/fl/scaffold.py)."""
+        part = set(int(k) for k in self.participants(r))
+        self.sc_c = scaffold_fold(self.sc_c, deltas, [k in part for k in range(self.world)], self.world)
+        if self.rank in part:
+            self.sc_ci = self.sc_ci + self.sc_delta
+        self.hist.scnorm[r] = float(torch.linalg.vector_norm(self.sc_c.to(torch.float64)))
+
+    def scaffold_variates(self):
+        return self.sc_c.numpy().copy(), self.sc_ci.numpy().copy()
 
     def train_one_epoch(self) -> float:
         """``local_steps`` full-batch Adam steps + one StepLR step (reference C:63-73)."""
@@ -1091,6 +1169,8 @@ class TorchRoundEngine(RoundEngineBase):
                 out = self.model(self.X)
                 loss = self.criterion(out, self.y)
                 loss.backward()
+            if self.scaffold:
+                self._scaffold_correct(ls)
             if anchor is not None:
                 with torch.no_grad():
                     for (name, shape, off), p in zip(self.model.layout, self.model.parameters()):
@@ -1431,6 +1511,10 @@ class TorchRoundEngine(RoundEngineBase):
         elif self.comm is not None:
             self.comm.allreduce_(buf)
         self.fedavg_apply(buf)
+        if self.scaffold:
+            # SCAFFOLD: every rank's pending delta is gathered, the fold applied on every rank alike
+            self.scaffold_apply(self.rounds_issued - 1,
+                                [torch.as_tensor(d) for d in self.comm.allgather(self.sc_delta.numpy())])
 
     def fedavg_apply(self, buf: torch.Tensor) -> None:
         """Adopt the all-reduced buffer: new global weights, metrics, early-stop rule."""
@@ -1540,6 +1624,7 @@ class TorchRoundEngine(RoundEngineBase):
             **({"dpsgd_seed": int(self.dpsgd_seed)} if self.dpsgd else {}),
             **({"server_m": self.server_m.numpy().copy(), "server_v": self.server_v.numpy().copy()}
                if self.server else {}),
+            **self._scaffold_state_out(),
             **self._compress_state_out(self.compress_residual.numpy().copy() if self.compress else None,
                                        self.compress_q.numpy() if self.compress and self.compress_lowrank else None),
             **self._heldout_state_out(None if not self.heldout or self._ho_best_flat is None
@@ -1553,6 +1638,9 @@ class TorchRoundEngine(RoundEngineBase):
         ce = self._compress_state_in(st)
         cq = self._compress_q_in(st)
         ho = self._heldout_state_in(st)
+        sc = self._scaffold_state_in(st)
+        if sc is not None:
+            self.sc_c, self.sc_ci = torch.as_tensor(sc[0].copy()), torch.as_tensor(sc[1].copy())
         if cq is not None:
             self.compress_q = torch.as_tensor(cq.copy())
         if ho is not None:
@@ -1633,6 +1721,8 @@ class HipRoundEngine(RoundEngineBase):
         if bool(cfg.secagg) and comm_buffers is not None:
             raise ValueError("trial packing (comm_buffers) does not run secure aggregation (secagg)")
         world = comm.size if comm is not None else 1
+        if scaffold_enabled(cfg, world) and comm_buffers is not None:
+            raise ValueError("trial packing (comm_buffers) does not run SCAFFOLD control variates (scaffold)")
         if attack_stage(cfg, world) and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run an attack stage (attack={cfg.attack!r})")
         if attack_stage(cfg, world) and cfg.gather_plane == "xgmi":
@@ -1762,6 +1852,14 @@ class HipRoundEngine(RoundEngineBase):
             ecfg.update({"dpsgd_clip": float(cfg.dpsgd_clip), "dpsgd_noise": float(cfg.dpsgd_noise),
                          "dpsgd_seed": int(self.dpsgd_seed)})
             bufs["dpsgd_row_norm"] = self.dpsgd_row_norm.data_ptr()
+        if self.scaffold:
+            # control variates in dense slab order (fl_scaffold.hip): c, c_i, and the pending cnew_i / delta_i the
+            # capture launch writes every round; ||c||_2 after every round's fold
+            self.sc_c, self.sc_ci, self.sc_cnew, self.sc_delta = (torch.zeros(self.P, **f32) for _ in range(4))
+            self.sc_norm = torch.zeros(mr, **f32)
+            ecfg["scaffold"] = True
+            bufs.update({"scaffold_c": self.sc_c.data_ptr(), "scaffold_ci": self.sc_ci.data_ptr(),
+                         "scaffold_cnew": self.sc_cnew.data_ptr(), "scaffold_delta": self.sc_delta.data_ptr()})
         if self.compress:
             # residual: two image-shaped fp32 halves, round r reads half r & 1 and writes half (r + 1) & 1
             # (fl_compress.hip); the per-round statistic
@@ -1810,8 +1908,8 @@ class HipRoundEngine(RoundEngineBase):
             # rows sized for the longest row the engine may choose (the blocked row of the reference shape)
             # (an older library loaded through FEDMI_NATIVE_SO for an A/B knows the dense row only)
             row = self.m.slab_row_floats(self.dims, R) if hasattr(self.m, "slab_row_floats") else ((self.P + 1) + 3) & ~3
-            # (DP-SGD: one row more, the noise workgroup's)
-            self.slab = torch.zeros(((self.n_local + R - 1) // R + int(self.dpsgd)) * row, **f32)
+            # (DP-SGD: one row more, the noise workgroup's; SCAFFOLD: one row more, the correction c - c_i)
+            self.slab = torch.zeros(((self.n_local + R - 1) // R + int(self.dpsgd) + int(self.scaffold)) * row, **f32)
             ecfg["R"] = R
             bufs["slab"] = self.slab.data_ptr()
             bufs["slab_floats"] = self.slab.numel()
@@ -1837,6 +1935,7 @@ class HipRoundEngine(RoundEngineBase):
             self.layout["secagg"] = {"bits": int(cfg.secagg_bits), "stream": SECAGG_STREAM}
         if self.attack:
             self.layout["attack"] = dict(self.attack_par)
+        self.layout["scaffold"] = bool(self.scaffold)   # (an older library loaded for an A/B does not report it)
         self.slab_f16 = bool(self.layout["slab_f16"])
         iw, ib, _ = image_layout(self.dims)
         if (self.layout["Pimg"], list(self.layout["iw_off"]), list(self.layout["ib_off"])) != (self.Pimg, iw, ib):
@@ -1853,8 +1952,11 @@ class HipRoundEngine(RoundEngineBase):
         # plane nor RCCL is set up; every rank shares the config, so that is collectively consistent -- or,
         # with gather_plane="xgmi", aggregate inside the peer kernel: the select set-up below)
         self._agg = None   # gathered stack + launcher of the aggregation kernels over it (_gather_launch)
+        self._sc_agg = None   # SCAFFOLD: gathered deltas + launcher of the control fold over them (scaffold_step)
+        # (SCAFFOLD: rounds are aggregated from Python, the model over the communicator's all-reduce and the
+        # control fold over a gather of every rank's delta: neither the peer plane nor RCCL is set up)
         if self.world > 1 and comm_buffers is None and getattr(comm, "peer_allreduce", False) and not self.robust \
-                and not self.secagg:
+                and not self.secagg and not self.scaffold:
             from ..parallel.peer import make_peer_allreduce
             torch.cuda.synchronize(dev)
             # lagged rounds reduce inside the Adam kernel: one chunk flag per Adam block + the
@@ -1879,7 +1981,7 @@ class HipRoundEngine(RoundEngineBase):
                               "aggregating over the host gather", RuntimeWarning, stacklevel=2)
         self.layout["gather_plane"] = "xgmi" if (want_select and self._peer is not None) else "host"
         if self.world > 1 and self._peer is None and comm_buffers is None and comm is not None \
-                and hasattr(comm, "rccl") and not self.robust and not self.secagg:
+                and hasattr(comm, "rccl") and not self.robust and not self.secagg and not self.scaffold:
             # RCCL only when the peer plane is off or fell back (every rank agreed on that above),
             # so this lazy, bounded bootstrap runs on every rank or on none; if it fails too, every
             # rank continues on the host plane (aggregation 'host') instead of raising
@@ -2016,6 +2118,7 @@ class HipRoundEngine(RoundEngineBase):
         else:
             with torch.cuda.stream(self.stream):
                 self._aggregate(r)
+                self.scaffold_step(r)
             self.server_step(r)
             self.heldout_step(r)
 
@@ -2064,6 +2167,30 @@ class HipRoundEngine(RoundEngineBase):
         agg.mask(par, s)
         self.comm.allgather_device(self.params[par], out=stack)
         agg.open(par, s)
+
+    def scaffold_step(self, r: int) -> None:
+        """SCAFFOLD control fold of round ``r`` of a multi-rank engine, after the model's aggregation, on the
+        current stream: a gather of every rank's pending delta over the host plane and one fl_scaffold fold
+        launch over the gathered stack (this rank's ``c``, and its ``c_i`` when sampled).  Nothing when off."""
+        if not self.scaffold:
+            return
+        if self._sc_agg is None:
+            stack = torch.empty((self.world, self.P), dtype=torch.float32, device=self.device)
+            self._sc_agg = (stack, _ScaffoldLaunch(self, [stack[k] for k in range(self.world)], [self.sc_c], [self],
+                                                   first=self.rank))
+        stack, agg = self._sc_agg
+        self.comm.allgather_device(self.sc_delta, out=stack)
+        agg.fold((r + 1) & 1, torch.cuda.current_stream(self.device).cuda_stream)
+        self.scaffold_norm_step(r)
+
+    def scaffold_norm_step(self, r: int) -> None:
+        """||c||_2 after round ``r``'s fold into the per-round device history (current stream)."""
+        if r < self.sc_norm.numel():
+            self.sc_norm[r] = torch.linalg.vector_norm(self.sc_c)
+
+    def scaffold_variates(self):
+        self.stream.synchronize()
+        return self.sc_c.cpu().numpy().copy(), self.sc_ci.cpu().numpy().copy()
 
     def server_step(self, r: int) -> None:
         """Server-optimizer step of round ``r`` on the aggregated image a caller summed into
@@ -2253,6 +2380,7 @@ class HipRoundEngine(RoundEngineBase):
                 for r in range(r0, r0 + n):
                     self.engine.run_local(r, s)
                     self._aggregate(r)
+                    self.scaffold_step(r)
                     self.server_step(r)
                     self.heldout_step(r)
             self.rounds_issued += n
@@ -2481,6 +2609,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.clamped[:n] = m["clamp"][:n].numpy().view(np.uint32)
             if self.screen:
                 self.hist.screen[:n] = m["screen"][:n].numpy().view(np.uint64)
+            if self.scaffold:   # (read in place: the mirror does not hold it)
+                self.hist.scnorm[:n] = self.sc_norm[:n].cpu().numpy()
         if self.heldout:
             self._read_heldout(n, m["ho_cm"], m["ho_loss"], m["ho_best"], m.get("ho_u2"))
         if st["stopped"]:
@@ -2517,6 +2647,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.clamped[:n] = self.sa_clamp[:n].cpu().numpy().view(np.uint32)
             if self.screen:
                 self.hist.screen[:n] = self.screen_hist[:n].cpu().numpy().view(np.uint64)
+            if self.scaffold:
+                self.hist.scnorm[:n] = self.sc_norm[:n].cpu().numpy()
         if self.heldout:
             self._read_heldout(n, self.ho_cm, self.ho_loss, self.ho_best, self.ho_u2)
         if st["stopped"]:
@@ -2595,6 +2727,7 @@ class HipRoundEngine(RoundEngineBase):
             **({"dpsgd_seed": int(self.dpsgd_seed)} if self.dpsgd else {}),
             **({"server_m": image_to_dense(self.server_m.cpu().numpy(), self.dims),
                 "server_v": image_to_dense(self.server_v.cpu().numpy(), self.dims)} if self.server else {}),
+            **self._scaffold_state_out(),
             **self._compress_state_out(self.compress_residual if self.compress else None,
                                        self.compress_q if self.compress and self.compress_lowrank else None),
             **self._heldout_state_out(None if not (self.heldout and self.keep_best and self._ho_best_words()[1] >= 0)
@@ -2609,6 +2742,7 @@ class HipRoundEngine(RoundEngineBase):
         ce = self._compress_state_in(st)
         cq = self._compress_q_in(st)
         ho = self._heldout_state_in(st)
+        sc = self._scaffold_state_in(st)
         self.stream.synchronize()
         dev = self.device
         img = lambda a: torch.as_tensor(dense_to_image(np.asarray(a, np.float32), self.dims), device=dev)
@@ -2627,6 +2761,9 @@ class HipRoundEngine(RoundEngineBase):
                 self.cp_res.copy_(img(ce).repeat(2))
             if cq is not None:
                 self.cp_q[:2 * self.compress_q_len].copy_(torch.as_tensor(cq, device=dev).repeat(2))
+            if sc is not None:   # (the slab's correction row is rewritten by the next live round's capture)
+                self.sc_c.copy_(torch.as_tensor(sc[0], device=dev))
+                self.sc_ci.copy_(torch.as_tensor(sc[1], device=dev))
             es = st["es"]
             rec = np.zeros(1, dtype=_STATE_DTYPE)
             rec["next_round"] = r
@@ -2650,6 +2787,8 @@ class HipRoundEngine(RoundEngineBase):
                 self.h_loss[:n].copy_(torch.as_tensor(self.hist.loss[:n], device=dev))
                 if self.dp:
                     self.dp_norm[:n].copy_(torch.as_tensor(self.hist.norm[:n], device=dev))
+                if self.scaffold:
+                    self.sc_norm[:n].copy_(torch.as_tensor(self.hist.scnorm[:n], device=dev))
                 if self.compress:
                     self.cp_stat[:n].copy_(torch.as_tensor(self.hist.cstat[:n], device=dev))
                 if self.secagg:

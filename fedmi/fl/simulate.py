@@ -38,6 +38,10 @@ With an attack model (``EngineConfig.attack``, ``fedmi/fl/attack.py``) the Byzan
 rewritten after the ``tamper`` hook and before all of the above: one ``fl_attack`` launch in place over the
 k buffers on the device, ``attack_torch`` on the CPU; ``"label_flip"`` flips the bad clients' shard labels
 instead.  The launched kinds make every client start from one common model.
+
+With SCAFFOLD (``EngineConfig.scaffold``, ``fedmi/fl/scaffold.py``) the model's sum is followed by the control
+fold over the k clients' pending deltas: one ``fl_scaffold`` fold launch on the device (every client's ``c``, the
+sampled clients' ``c_i``), ``scaffold_fold`` on the CPU.
 """
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ import torch
 
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
-from .aggregate import _AggLaunch
+from .aggregate import _AggLaunch, _ScaffoldLaunch
 from .attack import attack_id, flip_labels
 from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, common_init, gather_plane_id, heldout_metrics
 
@@ -145,6 +149,11 @@ class ClientGroup:
             if lead.robust or lead.secagg or lead.attack_stage:   # in place over the k clients' buffers, client r = buffer r
                 bufs = [[e.params[q] for e in self.clients] for q in (0, 1)]
                 self._agg = _AggLaunch(lead, bufs, bufs, clamps=[e.sa_clamp for e in self.clients] if lead.secagg else ())
+            if lead.scaffold:   # the k clients' deltas are the sources, every client's c a destination
+                self._scaffold = _ScaffoldLaunch(lead, [e.sc_delta for e in self.clients], [e.sc_c for e in self.clients],
+                                                 self.clients)
+                for e in self.clients[1:]:
+                    e.sc_norm = lead.sc_norm
             self.stream = torch.cuda.Stream(device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             for e in self.clients:
@@ -181,6 +190,11 @@ class ClientGroup:
             self._agg.open(par, s)
         else:
             self._sum_hip(bufs)
+        if lead.scaffold:
+            # SCAFFOLD: one fold launch after the model's sum -- c of every client, c_i of the sampled ones
+            self._scaffold.fold(par, s)
+            with torch.cuda.stream(self.stream):
+                lead.scaffold_norm_step(r)   # (one replicated value: the lead takes it, every client reports it)
         for e in self.clients:
             e.server_step(r)              # server optimizer: every client steps its replica of the sum
             e.rounds_issued = r + 1
@@ -219,6 +233,10 @@ class ClientGroup:
                 tot += b
         for e in self.clients:
             e.fedavg_apply(tot.clone())
+        if self.clients[0].scaffold:
+            deltas = [e.sc_delta for e in self.clients]   # SCAFFOLD: the control fold, on every replica alike
+            for e in self.clients:
+                e.scaffold_apply(self.rounds, deltas)
 
     @property
     def stopped(self) -> bool:

@@ -44,7 +44,11 @@ class WideClient:
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
                  fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
                  compress: str = "none", secagg: bool = False, screen: str = "none", attack: str = "none",
-                 dpsgd_clip: float = 0.0):
+                 dpsgd_clip: float = 0.0, scaffold: bool = False):
+        if scaffold:
+            # the wide path's layered GEMMs accumulate gradients in place: no slab row carries a correction
+            raise ValueError("WideClient does not run SCAFFOLD control variates (scaffold=True); "
+                             "use the round engines (EngineConfig.scaffold)")
         if float(dpsgd_clip) > 0.0:
             # the wide path's layered GEMMs never hold a row's whole gradient, nor all layers' operands at once
             raise ValueError(f"WideClient does not run record-level DP-SGD (dpsgd_clip={dpsgd_clip!r}); "

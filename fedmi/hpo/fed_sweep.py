@@ -89,6 +89,9 @@ class FedTrialGroup:
             # the batched train kernels have no per-example clipping, and a private sweep would have to
             # account for every trial's steps
             raise ValueError("fed_sweep does not run record-level DP-SGD trials (dpsgd_clip / dpsgd_noise)")
+        if bool(getattr(base, "scaffold", False)):
+            # the batched launches have no capture launch, and every trial would need variates of its own
+            raise ValueError("fed_sweep does not run SCAFFOLD trials (scaffold)")
         if base.server_opt != "none":
             # the trials share launches and one collective; a server step per trial is not batched
             raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")

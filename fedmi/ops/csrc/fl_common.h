@@ -301,6 +301,26 @@ struct FLDpSgd {
     float* row_norm;     // [n_rows] pre-clip ||g_r||_2 of the last train launch
 };
 
+// SCAFFOLD control variates (fl_scaffold.hip; Karimireddy et al. 2020, option I): parameters of the per-round
+// capture launch (between local step 0's train and Adam launches) and of the fold launch after the model's
+// aggregation, passed to those kernels alone.  Everything is in dense slab order, P floats.  The capture
+// reads slab rows [0, n_blk) and writes row n_blk = c - c_i (its floats [P, slab_stride) exact 0); the Adam
+// launches of such an engine reduce n_blk + 1 rows, its train launches keep n_blk workgroups.
+#define FL_SCAFFOLD_MAX_K 64         // width of the rtab mask
+struct FLScaffold {
+    int P;               // dense parameter count (== MLPDesc::P)
+    int slab_stride;     // capture: floats per slab row (FLConfig::slab_stride)
+    int n_blk;           // capture: row blocks of the shard, ceil(n_rows / R); the correction row's index
+    int K;               // fold: delta sources, 1 .. FL_SCAFFOLD_MAX_K (source k is client k)
+    int N;               // fold: clients of the federation (the divisor; not the sampled count)
+    int max_rounds;      // rounds of rtab; rounds past it are not live
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): its weight, the sampled mask
+    const float* c;      // capture: [P] server variate of this replica
+    const float* ci;     // capture: [P] this client's variate
+    float* cnew;         // capture: [P] the round's g0 (what c_i becomes, up to the commit's one rounding)
+    float* delta;        // capture: [P] pending cnew - c_i
+};
+
 // Server optimizer (fl_server.hip): parameters of the per-round server step, passed to that
 // kernel alone, as FLDp is.  With x the image the round trained from, a the aggregated image and
 // d = a - x, the kernel keeps m (and, adaptive kinds, v) across rounds and replaces a by
@@ -744,6 +764,15 @@ hipError_t fl_launch_attack(const MLPDesc& d, const FLAttack& p, float* const* b
 hipError_t fl_launch_cclip(const MLPDesc& d, const FLCclip& p, const float* const* src, const float* x,
                            float* const* dst, int n_dst, const FLState* st, int tails_len, float* scratch,
                            hipStream_t s, const unsigned long long* keep, const unsigned long long* dst_host);
+// (fl_scaffold.hip) SCAFFOLD.  Capture: under the round's INPUT state `st` (the train kernel's tentative live
+// decision) and this client's rtab weight, the fixed-order column sums of slab rows [0, p.n_blk) into p.cnew,
+// p.delta = cnew - ci, and slab row p.n_blk = c - ci; `slab` holds p.n_blk + 1 rows.  Fold: under the round's
+// published state `st`, c += (left fold of the sampled clients' deltas `src`, device table of p.K [P] buffers) /
+// p.N, read from dst[0] and written to the `n_dst` replicas of the device table `dst`; clients first_own ..
+// first_own + n_own - 1 (device table `ci`) commit ci = add(ci, their delta) when sampled.  Both replayable.
+hipError_t fl_launch_scaffold_capture(const FLScaffold& p, float* slab, const FLState* st, hipStream_t s);
+hipError_t fl_launch_scaffold_fold(const FLScaffold& p, const float* const* src, float* const* dst, int n_dst,
+                                   float* const* ci, int n_own, int first_own, const FLState* st, hipStream_t s);
 // (fl_secagg.hip) secure aggregation of the round whose state is `st`.  Mask: quantises and pair-masks, in
 // place, the real parameters of the `n` buffers named by the device pointer table `bufs` (clients
 // first_client .. first_client + n - 1; unsampled ones and rounds that are not live are left alone);

@@ -277,6 +277,7 @@ class FLEngine {
         std::memset(&sv_, 0, sizeof(sv_));
         sv_.kind = cfg.contains("server_opt") ? cfg["server_opt"].cast<int>() : FL_SERVER_NONE;
         tr_.server_on = sv_.kind != FL_SERVER_NONE;
+        tr_.scaffold_on = cfg.contains("scaffold") && cfg["scaffold"].cast<bool>();
         // The round's output is not the aggregated local model, so rounds are classic:
         // differential privacy (fl_dp.hip) outputs the clipped, noised contribution, not the local
         // model a fused / lagged round's next train kernel would score and stage, and a discarded
@@ -284,7 +285,7 @@ class FLEngine {
         // update and keeps a residual a discarded round would have consumed; a server optimizer (fl_server.hip) outputs x + (a
         // server step), so a fused round would score the wrong model through the global image and a
         // lagged round's in-Adam exchange would publish an image the step then has to replace.
-        const bool classic_only = tr_.foreign_output();
+        const bool classic_only = tr_.classic_only();
         // Fused evaluation needs the round's input weights to BE the previous round's
         // post-step local model: one client (FedAvg of one is the identity, agg_scale 1).
         tr_.fused = !classic_only && cfg.contains("fused_eval") && cfg["fused_eval"].cast<bool>() && tr_.identity;
@@ -320,6 +321,31 @@ class FLEngine {
                 throw std::runtime_error("FLEngine: DP-SGD needs one slab row more than the shard has row blocks");
             c_.n_slabs += 1;
             HIP_CHECK(fl_set_lds_limit_dpsgd((size_t)lds * 4));
+        }
+        // SCAFFOLD (fl_scaffold.hip): the capture launch after every round's first train launch writes slab row
+        // n_blk = c - c_i, so the Adam kernels reduce c_.n_slabs = n_blk + 1 rows while the train launches keep
+        // n_blk workgroups (execute: TRAIN) -- no train launch of a later local step overwrites the row.
+        std::memset(&sc_, 0, sizeof(sc_));
+        if (tr_.scaffold_on) {
+            if (dtype_ != 0) throw std::runtime_error("FLEngine: SCAFFOLD runs the fp32 kernels only");
+            if (ds_.clip > 0.f || tr_.dp_on || tr_.compress_on)
+                throw std::runtime_error("FLEngine: SCAFFOLD does not combine with DP-SGD, differential privacy or compression");
+            if (c_.world > FL_SCAFFOLD_MAX_K) throw std::runtime_error("FLEngine: SCAFFOLD takes at most 64 clients");
+            sc_.P = d_.P;
+            sc_.slab_stride = c_.slab_stride;
+            sc_.n_blk = c_.n_slabs;
+            sc_.K = sc_.N = c_.world;
+            sc_.max_rounds = c_.max_rounds;
+            sc_.c = as_ptr<const float>(bufs["scaffold_c"].cast<uintptr_t>());
+            sc_.ci = as_ptr<const float>(bufs["scaffold_ci"].cast<uintptr_t>());
+            sc_.cnew = as_ptr<float>(bufs["scaffold_cnew"].cast<uintptr_t>());
+            sc_.delta = as_ptr<float>(bufs["scaffold_delta"].cast<uintptr_t>());
+            if (sc_.c == nullptr || sc_.ci == nullptr || sc_.cnew == nullptr || sc_.delta == nullptr)
+                throw std::runtime_error("FLEngine: SCAFFOLD needs its four control-variate buffers");
+            const long long have = bufs.contains("slab_floats") ? bufs["slab_floats"].cast<long long>() : 0;
+            if (have < (long long)(c_.n_slabs + 1) * c_.slab_stride)
+                throw std::runtime_error("FLEngine: SCAFFOLD needs one slab row more than the shard has row blocks");
+            c_.n_slabs += 1;
         }
         std::memset(&lr_, 0, sizeof(lr_));
         std::memset(&mx_, 0, sizeof(mx_));
@@ -507,6 +533,7 @@ class FLEngine {
         // host-built device tables owned by the caller
         b_.sched = as_ptr<const float>(bufs["sched"].cast<uintptr_t>());
         b_.rtab = as_ptr<const float>(bufs["rtab"].cast<uintptr_t>());
+        sc_.rtab = b_.rtab;
         b_.sat = bufs.contains("sat") ? as_ptr<int>(bufs["sat"].cast<uintptr_t>()) : nullptr;
         {
             // FL_EVAL_LAGGED: previous round's counts + loss (zero)
@@ -952,8 +979,8 @@ class FLEngine {
         HIP_CHECK(hipStreamSynchronize(s));
         constexpr int TR_N = FLLaunchRec::N_KINDS + 2;  // events are tagged with the launch kind (kTraceAuc: the AUC launches)
         static const char* names[TR_N] = {"pack", "train", "adam", "eval", "allreduce", "eval_fedavg", "dp",
-                                          "server", "finalize", "compress", "heldout", "heldout_auc_keys",
-                                          "heldout_auc_rank"};
+                                          "server", "finalize", "compress", "heldout", "scaffold",
+                                          "heldout_auc_keys", "heldout_auc_rank"};
         double us[TR_N] = {0};
         int cnt[TR_N] = {0};
         hipEvent_t prev = e0;
@@ -1041,6 +1068,7 @@ class FLEngine {
         o["lagged_eval"] = lagged();
         o["dpsgd"] = ds_.clip > 0.f;                       // per-example clipping train kernel + noise slab row
         o["dp"] = tr_.dp_on;                               // clipped (+ noised) contributions, classic rounds
+        o["scaffold"] = tr_.scaffold_on;                   // capture launch + correction slab row (n_slabs counts it)
         {
             // compression of every contribution (a simulated uplink: the exchange stays dense), classic rounds
             static const char* compress_names[] = {"none", "topk", "sign", "qsgd", "randk", "powersgd", "mx"};
@@ -1144,7 +1172,11 @@ class FLEngine {
             case FLLaunchRec::TRAIN:
                 if (ds_.clip > 0.f)  // (fp32 only; never the shape-specialised kernel)
                     HIP_CHECK(fl_launch_train_dpsgd(d_, c_, b_, ds_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3]));
-                else if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3],
+                else if (tr_.scaffold_on) {  // (fp32 only) the row-block count: slab row c_.n_slabs - 1 is the correction's
+                    FLConfig ct = c_;
+                    ct.n_slabs = sc_.n_blk;
+                    HIP_CHECK(fl_launch_train(d_, ct, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3], shape_spec_on_));
+                } else if (dtype_ == 0) HIP_CHECK(fl_launch_train(d_, c_, b_, F(0), S(1), S(2), i[0], s, i[2], F(3), i[3],
                                                               shape_spec_on_));
                 else
                     HIP_CHECK(fl_launch_train_bf16(d_, e_, c_, b_, F(0), S(1), S(2), i[0], s, i[1] != 0, i[2], F(3),
@@ -1214,6 +1246,9 @@ class FLEngine {
                     return;
                 }
                 break;
+            case FLLaunchRec::SCAFFOLD:
+                HIP_CHECK(fl_launch_scaffold_capture(sc_, b_.slab, S(0), s));
+                break;
             case FLLaunchRec::FINALIZE:
                 HIP_CHECK(fl_launch_finalize(d_, c_, b_, F(0), S(1), S(2), s, i[0],
                                              late_fold() ? pbuf_[m.par] : nullptr));
@@ -1280,6 +1315,7 @@ class FLEngine {
     uint32_t* sa_clamp_ = nullptr;   // secure aggregation: this client's clamp history [max_rounds] (caller-owned)
     void** sa_tab_ = nullptr;        // ... device pointer tables of the mask launch: {send 0, send 1, clamp history}
     FLDpSgd ds_;               // record-level DP-SGD (clip > 0): every TRAIN launch is fl_train_dpsgd_kernel
+    FLScaffold sc_;            // SCAFFOLD (tr_.scaffold_on): fl_scaffold_capture_kernel after every round's first TRAIN
     FLDp dp_;                  // differential privacy: fl_dp_kernel after every round's last Adam kernel
     FLCompress cp_;            // compression: fl_compress_kernel after every round's last Adam kernel
     FLLowRank lr_;             // ... or, cp_.kind == FL_COMPRESS_POWERSGD, fl_lowrank_kernel in its place
@@ -1350,6 +1386,7 @@ class TrialBatch {
             if (e.tr_.compress_on) throw std::runtime_error("TrialBatch: no compression (compress)");
             if (e.tr_.heldout_on) throw std::runtime_error("TrialBatch: no held-out scoring (set_heldout)");
             if (e.ds_.clip > 0.f) throw std::runtime_error("TrialBatch: no record-level DP-SGD (dpsgd_clip)");
+            if (e.tr_.scaffold_on) throw std::runtime_error("TrialBatch: no SCAFFOLD control variates (scaffold)");
             // the batch kernels write and read dense slab rows: from here on the engine's own launches do
             // too (the row stride stays; train / Adam pairs are issued together, so no pair is split)
             engs_[k]->slab_blocked_ = false;
@@ -1555,6 +1592,48 @@ static void robust_aggregate(std::vector<int> dims, int kind, double beta, uintp
     HIP_CHECK(fl_launch_robust(d, p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
                                as_ptr<const FLState>(state), tails_len, as_stream(stream),
                                as_ptr<const unsigned long long>(keep)));
+}
+
+// SCAFFOLD control fold (fl_scaffold.hip) across engines' buffers, as robust_aggregate is.  `src`: device table
+// of the K clients' delta buffers; `dst`: device table of the n_dst replicas of c (the first is read);
+// `ci`: device table of the variates of clients first_own .. first_own + n_own - 1 (committed as ci + delta);
+// every buffer P floats in dense order.  `N`: the federation's clients (the divisor).
+static void scaffold_fold(int P, uintptr_t src, int K, int N, uintptr_t dst, int n_dst, uintptr_t ci, int n_own,
+                          int first_own, uintptr_t state, uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    if (K < 1 || K > FL_SCAFFOLD_MAX_K)
+        throw std::runtime_error("scaffold_fold: 1.." + std::to_string(FL_SCAFFOLD_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    FLScaffold p;
+    std::memset(&p, 0, sizeof(p));
+    p.P = P;
+    p.K = K;
+    p.N = N;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    if (fl_launch_scaffold_fold(p, as_ptr<const float* const>(src), as_ptr<float* const>(dst), n_dst,
+                                as_ptr<float* const>(ci), n_own, first_own,
+                                as_ptr<const FLState>(state), as_stream(stream)) != hipSuccess)
+        throw std::runtime_error("scaffold_fold: bad arguments");
+}
+
+// SCAFFOLD capture launch (fl_scaffold.hip) on a caller's slab of n_blk + 1 rows of slab_stride floats, under
+// the round's input state `state` and the client's `rtab` -- the launch an engine issues itself every round
+// (tests, tools).
+static void scaffold_capture(int P, int slab_stride, int n_blk, uintptr_t slab, uintptr_t c, uintptr_t ci, uintptr_t cnew,
+                             uintptr_t delta, uintptr_t state, uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    FLScaffold p;
+    std::memset(&p, 0, sizeof(p));
+    p.P = P;
+    p.slab_stride = slab_stride;
+    p.n_blk = n_blk;
+    p.max_rounds = max_rounds;
+    p.rtab = as_ptr<const float>(rtab);
+    p.c = as_ptr<const float>(c);
+    p.ci = as_ptr<const float>(ci);
+    p.cnew = as_ptr<float>(cnew);
+    p.delta = as_ptr<float>(delta);
+    if (fl_launch_scaffold_capture(p, as_ptr<float>(slab), as_ptr<const FLState>(state), as_stream(stream)) != hipSuccess)
+        throw std::runtime_error("scaffold_capture: bad arguments");
 }
 
 // Byzantine attack stage (fl_attack.hip) across engines' buffers, as robust_aggregate is: one launch rewrites, in
@@ -1916,6 +1995,12 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     m.def("robust_aggregate", &robust_aggregate, py::arg("dims"), py::arg("kind"), py::arg("beta"), py::arg("src"),
           py::arg("K"), py::arg("dst"), py::arg("n_dst"), py::arg("state"), py::arg("rtab"), py::arg("tails_len"),
           py::arg("max_rounds"), py::arg("stream"), py::arg("keep") = (uintptr_t)0);
+    m.def("scaffold_fold", &scaffold_fold, py::arg("P"), py::arg("src"), py::arg("K"), py::arg("N"), py::arg("dst"),
+          py::arg("n_dst"), py::arg("ci"), py::arg("n_own"), py::arg("first_own"), py::arg("state"),
+          py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+    m.def("scaffold_capture", &scaffold_capture, py::arg("P"), py::arg("slab_stride"), py::arg("n_blk"), py::arg("slab"),
+          py::arg("c"), py::arg("ci"), py::arg("cnew"), py::arg("delta"), py::arg("state"), py::arg("rtab"),
+          py::arg("max_rounds"), py::arg("stream"));
     m.def("attack_apply", &attack_apply, py::arg("dims"), py::arg("kind"), py::arg("scale"), py::arg("z"), py::arg("seed"),
           py::arg("src"), py::arg("K"), py::arg("x"), py::arg("wtab"), py::arg("bad_mask"), py::arg("state"),
           py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));

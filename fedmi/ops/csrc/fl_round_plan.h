@@ -50,10 +50,10 @@ inline bool operator==(const FLSel& a, const FLSel& b) { return a.base == b.base
 
 // One launch of a round.  The kinds double as trace tags (FLEngine::trace).
 struct FLLaunchRec {
-    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, COMPRESS, HELDOUT, N_KINDS };
+    enum Kind { PACK, TRAIN, ADAM, EVAL, ALLREDUCE, EVAL_FEDAVG, DP, SERVER, FINALIZE, COMPRESS, HELDOUT, SCAFFOLD, N_KINDS };
     int kind;
     int i[4];     // TRAIN: ls, stage_local, mode, fold_mask | ADAM: ls, fold, tail_a, fold_mask |
-                  // FINALIZE: mask | others: 0
+                  // FINALIZE: mask | others: 0  (SCAFFOLD: p[0] = the round's input state)
     int peer;     // ADAM: 1 = takes the peer's exchange arguments, | 2 = wx, | 4 = afold
     int par;      // parity of the buffers the round writes, (r + 1) & 1 (peer arguments, late fold)
     FLSel p[5];   // buffer arguments in launcher order
@@ -110,6 +110,10 @@ struct RoundTraits {
     // its output image.  A round that a late fold may still discard must not leave a history row (or
     // take the best image) behind, so no rounds are lagged while it is on -- as with a foreign output.
     bool heldout_on = false;
+    // SCAFFOLD (fl_scaffold.hip): every round's first train launch is followed by the capture launch, which
+    // reads that launch's slab rows and writes the correction row the round's Adam launches reduce.  Rounds
+    // are classic, as with a server optimizer: the control fold follows the model's aggregation.
+    bool scaffold_on = false;
 
     // Lagged rounds: allowed by the layout, and either no early stopping (metrics may be
     // folded one round late), the Adam-fused exchange (which folds them in time) or an
@@ -125,6 +129,9 @@ struct RoundTraits {
     // compression: x + the compressed update; server optimizer: x + a server step), so rounds are
     // classic and always stage a fresh pack.
     bool foreign_output() const { return dp_on || compress_on || server_on; }
+    // Rounds are classic (never fused, never lagged): a foreign output, or SCAFFOLD, whose control fold follows
+    // the model's aggregation (its output IS the aggregated local model).
+    bool classic_only() const { return foreign_output() || scaffold_on; }
 };
 
 // Which metrics the last issued round left pending, and the state of the packed bf16 image.
@@ -260,6 +267,8 @@ inline void plan_train(const RoundTraits& t, RoundCarry& c, RoundPlan& out, int 
     for (int ls = 0; ls < t.local_steps; ++ls) {
         const bool first = ls == 0;
         plan_train_launch(t, c, out, par, pg, first ? si : so, so, ls, first ? mode : FL_EVAL_CLASSIC, cm_out, mask);
+        // SCAFFOLD: g0 from the slab rows just written, and the correction row, once per round
+        if (first && t.scaffold_on) out.push(FLLaunchRec::SCAFFOLD, 0, 0, 0, 0, par, si);
         if (first)
             out.push(FLLaunchRec::ADAM, ls, 1, score ? 1 : 0, mask, par, pg, pg, cb, si, so,
                      (xchg || afold) ? (1 | (xchg ? 2 : 0) | (afold ? 4 : 0)) : 0);
