@@ -242,6 +242,70 @@ class _ScaffoldLaunch:
                           e.state[par].data_ptr(), e.rtab.data_ptr(), int(e.cfg.max_rounds), stream)
 
 
+class _CoalitionLaunch:
+    """The coalition launches (``coalition_build``, ``coalition_score``, fl_coalition.hip) of one group, over the
+    clients' contribution buffers before the aggregation overwrites them.  ``lead``: the engine whose round state,
+    ``rtab`` and held-out rows the launches use; ``bufs[par]``: the K buffers of a round of output parity ``par``;
+    ``masks``: the coalition table; ``cw``: the ``[max_rounds, K]`` fp32 weights of the buffers.  Owns the pointer
+    tables, the mask and weight tables, the scratch and the device history (``loss`` NaN / ``correct`` -1 until a
+    round is scored)."""
+
+    def __init__(self, lead, bufs, masks: np.ndarray, cw: np.ndarray):
+        dev, mr = lead.device, max(1, int(lead.cfg.max_rounds))
+        self._lead, self._bufs = lead, bufs
+        self._k, self._m = len(bufs[0]), len(masks)
+        self._src = [torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=dev) for ts in bufs]
+        self._masks = torch.as_tensor(np.asarray(masks, np.uint64).view(np.int64).copy(), device=dev)
+        self._cw = torch.as_tensor(np.ascontiguousarray(cw, np.float32), device=dev)
+        self._R = int(lead.engine.heldout_rows_per_block)
+        self._n = int(lead.ho_X.shape[0])
+        self._scratch = torch.zeros(lead.m.coalition_scratch_floats(lead.dims, self._m, self._n, self._R),
+                                    dtype=torch.float32, device=dev)
+        self.loss = torch.full((mr * self._m,), float("nan"), dtype=torch.float32, device=dev)
+        self.correct = torch.full((mr * self._m,), -1, dtype=torch.int32, device=dev)
+
+    def launch(self, par: int, stream: int) -> None:
+        """Build, rows and fold of the round of output parity ``par``; ``x`` is the lead's other parity's image."""
+        e = self._lead
+        state, rtab, mr = e.state[par].data_ptr(), e.rtab.data_ptr(), int(e.cfg.max_rounds)
+        e.m.coalition_build(e.dims, self._src[par].data_ptr(), self._k, e.params[par ^ 1].data_ptr(),
+                            self._masks.data_ptr(), self._m, self._cw.data_ptr(), self._scratch.data_ptr(), state, rtab,
+                            mr, stream)
+        e.m.coalition_score(e.dims, self._R, self._k, self._m, self._scratch.data_ptr(), e.ho_X.data_ptr(),
+                            e.ho_y.data_ptr(), self._n, self.loss.data_ptr(), self.correct.data_ptr(), state, mr, stream)
+
+
+def coalition_utilities_torch(v: Sequence[torch.Tensor], w: Sequence[float], x: torch.Tensor, masks, sampled: int,
+                              dims: Sequence[int], X: torch.Tensor, y: torch.Tensor):
+    """``(loss_sum [M], correct [M])`` of the coalition models in ``x``'s dtype: per mask the fold from +0 in
+    client order of the dense contributions ``v`` and of their weights ``w`` over ``mask & sampled``, one division
+    (nobody: ``x``), then the forward on the rows ``X``, the softmax cross-entropy sum and the first-maximum
+    argmax hits.  fp32: what the torch group runs; float64: the oracle."""
+    dt = x.dtype
+    loss, hits = np.zeros(len(masks), np.float64), np.zeros(len(masks), np.int64)
+    Xt = X.to(dt)
+    for j, mk in enumerate(masks):
+        eff = int(mk) & int(sampled)
+        if eff == 0:
+            flat = x
+        else:
+            num, den = torch.zeros_like(x), torch.zeros((), dtype=dt)
+            for i in range(len(v)):
+                if (eff >> i) & 1:
+                    num, den = num + v[i].to(dt), den + torch.as_tensor(w[i], dtype=dt)
+            flat = num / den
+        a, off = Xt, 0
+        for l in range(len(dims) - 1):
+            K, N = dims[l], dims[l + 1]
+            a = torch.nn.functional.linear(a, flat[off:off + N * K].view(N, K), flat[off + N * K:off + N * K + N])
+            off += N * K + N
+            if l + 2 < len(dims):
+                a = torch.relu(a)
+        loss[j] = float((torch.logsumexp(a, 1) - a.gather(1, y.view(-1, 1)).squeeze(1)).sum().item())
+        hits[j] = int((torch.max(a, 1)[1] == y).sum().item())
+    return loss, hits
+
+
 def _sort_keys(stack: torch.Tensor) -> torch.Tensor:
     """int64 keys whose order is the total order of the values: NaN above +inf, -0 == +0."""
     stack = stack.contiguous()

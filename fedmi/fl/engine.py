@@ -38,6 +38,7 @@ from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients
 from .compress import (BLOCK_COMPRESSORS, COMPRESSORS, LOWRANK_COMPRESSORS, MX_FORMATS, RANDOM_COMPRESSORS, compress_id,
                        compress_k, compress_torch,
                        lowrank_layers, lowrank_q0, lowrank_torch, uplink_bytes)
+from .contribution import contribution_history, contribution_id
 from .early_stop import EarlyStopper
 from .metrics import (METRIC_NAMES, auc_from_u2, auc_u2_model, confusion_matrix, metrics_from_confusion,
                       metric_vector)
@@ -286,11 +287,32 @@ class EngineConfig:
     # dp_clip, secagg, a robust aggregator, a screen, attack, compress, trial batches (comm_buffers), fed_sweep,
     # WideClient, or more than 64 clients.  history()["scaffold_norm"]: ||c||_2 per round.
     scaffold: bool = False
+    # Client contribution scores (fedmi/fl/contribution.py, fl_coalition.hip): every contribution_every-th round,
+    # after tamper and the attack stage and before the aggregation, ClientGroup builds the FedAvg model each
+    # coalition of a static mask table would have produced alone (the weighted mean of its sampled members'
+    # contributions; the empty coalition: the image the round trained from; no server-optimizer step is applied
+    # to a coalition model) and scores it on the group's held-out rows: three launches, no per-coalition launch.
+    # "loo": K + 1 coalitions, leave-one-out scores; "shapley": exact Shapley values over all 2^K coalitions up
+    # to 8 clients, above that contribution_perms > 0 permutations drawn once from
+    # numpy.random.default_rng(contribution_seed), 1 + perms K coalitions (at most 4096).  The players of a round
+    # are its sampled clients; an unsampled client scores 0.  history() gains coalition_masks, coalition_loss_sum,
+    # coalition_correct, contribution (from the held-out loss) and contribution_acc (from the accuracy); rounds
+    # that are not scored hold NaN.  "none": off (nothing of a round changes); one client: off.  Needs
+    # ClientGroup(heldout=...).  Not with secagg, dp_clip > 0, compress, a robust aggregator, a screen, trial
+    # batches (comm_buffers), fed_sweep, WideClient, more than 64 clients, or a multi-rank engine.
+    contribution: str = "none"
+    contribution_perms: int = 0
+    contribution_seed: int = 0
+    contribution_every: int = 1
 
     def to_dict(self) -> dict:
         d = asdict(self)
         d["hidden"] = list(self.hidden)
         d["betas"] = list(self.betas)
+        if self.contribution == "none":
+            # (off: a checkpoint's config record is what it was before the contribution fields existed)
+            for k in ("contribution", "contribution_perms", "contribution_seed", "contribution_every"):
+                del d[k]
         if not self.scaffold:
             # (off: a checkpoint's config record is what it was before the field existed)
             del d["scaffold"]
@@ -549,6 +571,10 @@ class _History:
     ho_pos = None
     # SCAFFOLD engines: the L2 norm of the server variate c after every round; None: off
     scnorm = None
+    # contribution scores (ClientGroup, EngineConfig.contribution): the group's coalition record, shared by its
+    # clients -- mode, K, masks [M], perms, the held-out rows n, every round's sampled mask, and per round the
+    # coalitions' fp32 loss sums (NaN: not scored) and correct rows (-1); None: off
+    co = None
 
     def enable_heldout(self, n_classes: int, n_rows: int, auc_pos=None) -> None:
         if self.ho_cm is None:
@@ -608,6 +634,13 @@ class _History:
         if self.ho_u2 is not None:
             out["heldout_auc_u2"] = self.ho_u2[:n].copy()
             out["heldout_auc"] = auc_from_u2(self.ho_u2[:n], self.ho_pos[None, :], self.ho_n - self.ho_pos[None, :])
+        if self.co is not None:
+            c = self.co
+            out["coalition_masks"] = c["masks"].copy()
+            out["coalition_loss_sum"] = c["loss"][:n].copy()
+            out["coalition_correct"] = c["correct"][:n].copy()
+            out["contribution"], out["contribution_acc"] = contribution_history(
+                c["mode"], c["K"], c["perms"], c["loss"][:n], c["correct"][:n], c["n"], c["sampled"][:n])
         return out
 
     def global_metrics_dict(self) -> Dict[str, List[float]]:
@@ -694,6 +727,14 @@ class RoundEngineBase:
             self._client_sizes = [int(n) for n in client_sizes]
         # SCAFFOLD control variates (fedmi/fl/scaffold.py); one client: off
         self.scaffold = scaffold_enabled(cfg, self.world)
+        # client contribution scores (fedmi/fl/contribution.py): index in contribution.MODES, 0 = off; one client: off.
+        # The ClientGroup that owns this client scores the coalitions and hands its lead the device history
+        # (co_launch); a client outside a group trains as usual and records no coalition rows
+        self.contribution = contribution_id(cfg, self.world)
+        self.co_launch = None
+        if self.contribution and not getattr(comm, "in_process", False):
+            raise ValueError(f"contribution={cfg.contribution!r} does not run on a multi-rank engine: the coalitions need "
+                             "every client's contribution and one held-out set in one process; use ClientGroup")
         self.n_local = int(len(X))
         if self.n_local == 0:
             raise ValueError("client shard is empty (reference SURVEY Q12 would deadlock)")
@@ -1725,6 +1766,8 @@ class HipRoundEngine(RoundEngineBase):
             raise ValueError("trial packing (comm_buffers) does not run SCAFFOLD control variates (scaffold)")
         if attack_stage(cfg, world) and comm_buffers is not None:
             raise ValueError(f"trial packing (comm_buffers) does not run an attack stage (attack={cfg.attack!r})")
+        if contribution_id(cfg, world) and comm_buffers is not None:
+            raise ValueError(f"trial packing (comm_buffers) does not run contribution scores (contribution={cfg.contribution!r})")
         if attack_stage(cfg, world) and cfg.gather_plane == "xgmi":
             raise ValueError(f"attack={cfg.attack!r} does not run on gather_plane='xgmi': the one-shot select kernel never "
                              "holds the stack of contributions the stage rewrites; use gather_plane='host'")
@@ -2649,6 +2692,10 @@ class HipRoundEngine(RoundEngineBase):
                 self.hist.screen[:n] = self.screen_hist[:n].cpu().numpy().view(np.uint64)
             if self.scaffold:
                 self.hist.scnorm[:n] = self.sc_norm[:n].cpu().numpy()
+            if self.co_launch is not None:   # the group's coalition rows: the lead copies them into the shared record
+                co, M = self.hist.co, len(self.hist.co["masks"])
+                co["loss"][:n] = self.co_launch.loss[:n * M].cpu().numpy().reshape(n, M)
+                co["correct"][:n] = self.co_launch.correct[:n * M].cpu().numpy().reshape(n, M)
         if self.heldout:
             self._read_heldout(n, self.ho_cm, self.ho_loss, self.ho_best, self.ho_u2)
         if st["stopped"]:

@@ -42,6 +42,10 @@ instead.  The launched kinds make every client start from one common model.
 With SCAFFOLD (``EngineConfig.scaffold``, ``fedmi/fl/scaffold.py``) the model's sum is followed by the control
 fold over the k clients' pending deltas: one ``fl_scaffold`` fold launch on the device (every client's ``c``, the
 sampled clients' ``c_i``), ``scaffold_fold`` on the CPU.
+
+With contribution scores (``EngineConfig.contribution``, ``fedmi/fl/contribution.py``) the coalitions of a static mask
+table are built from the k buffers and scored on the held-out rows after the attack stage and before the aggregation:
+three ``fl_coalition`` launches on the device, ``coalition_utilities_torch`` on the CPU.
 """
 from __future__ import annotations
 
@@ -54,8 +58,9 @@ import torch
 
 from ..data.sharding import shard_indices
 from ..models.mlp import init_flat
-from .aggregate import _AggLaunch, _ScaffoldLaunch
+from .aggregate import _AggLaunch, _CoalitionLaunch, _ScaffoldLaunch, coalition_utilities_torch, mask_bits
 from .attack import attack_id, flip_labels
+from .contribution import EXACT_MAX_K, coalition_masks, coalition_perms
 from .engine import EngineConfig, HipRoundEngine, TorchRoundEngine, common_init, gather_plane_id, heldout_metrics
 
 
@@ -161,7 +166,62 @@ class ClientGroup:
         if heldout is not None:
             Xv, yv = heldout
             self.clients[0].set_heldout(Xv, yv, keep_best=keep_best, auc=heldout_auc)   # only the lead holds (and ranks) the set
+        if self.clients[0].contribution:
+            self._enable_contribution(heldout is not None)
         self.rounds = 0
+
+    def _enable_contribution(self, has_heldout: bool) -> None:
+        """Contribution scores (``EngineConfig.contribution``): the coalition table, every round's sampled mask and
+        the buffers' weights, built once; one record for the group (the lead's launches / rule write it, every
+        client reports it)."""
+        lead, K = self.clients[0], self.k
+        cfg = lead.cfg
+        if not has_heldout:
+            raise ValueError(f"contribution={cfg.contribution!r} needs a held-out set: the coalitions are scored on "
+                             "ClientGroup(heldout=(X, y))")
+        mode, m = cfg.contribution, int(cfg.contribution_perms)
+        masks = coalition_masks(mode, K, m, int(cfg.contribution_seed))
+        mr = max(1, int(cfg.max_rounds))
+        parts = [[int(q) for q in lead.participants(r)] for r in range(mr)]
+        # the weights the buffers carry, taken from where the clients take them: hip column 0 of each client's round
+        # table (_round_tables: n_i over the sampled clients' total, 0 when it sits out); torch the factor of
+        # fedavg_contribution -- agg_scale, or under client sampling the raw n_i (divided out after the sum)
+        cw = np.zeros((mr, K), np.float32)
+        sampling = float(cfg.participation) < 1.0
+        for q, e in enumerate(self.clients):
+            if self.backend == "hip":
+                cw[:, q] = e.rtab.cpu().numpy().view(np.uint32).reshape(mr, 4)[:, 0].view(np.float32)
+            else:
+                live = [q in part for part in parts]
+                cw[live, q] = float(e.n_local) if sampling else e.agg_scale
+        self._co_every, self._co_cw = max(1, int(cfg.contribution_every)), cw
+        self.contribution_dtype = torch.float32   # torch backend: torch.float64 scores the same buffers as the oracle
+        n = int(lead.ho_X.shape[0])
+        co = {"mode": mode, "K": K, "masks": masks, "n": n,
+              "perms": coalition_perms(K, m, int(cfg.contribution_seed)) if mode == "shapley" and K > EXACT_MAX_K else None,
+              "sampled": np.array([mask_bits(q in part for q in range(K)) for part in parts], dtype=np.uint64),
+              "loss": np.full((mr, len(masks)), np.nan, np.float32),
+              "correct": np.full((mr, len(masks)), -1, np.int32)}
+        if self.backend == "hip":
+            bufs = [[e.params[q] for e in self.clients] for q in (0, 1)]
+            self._coalition = _CoalitionLaunch(lead, bufs, masks, cw)
+            lead.co_launch = self._coalition   # (the device history: the lead's read_history copies it into the record)
+        for e in self.clients:
+            e.hist.co = co
+            if self.backend == "hip":
+                e.layout["contribution"] = {"mode": mode, "coalitions": int(len(masks)), "launches": 3}
+
+    def _coalitions_torch(self, r: int, bufs) -> None:
+        """The torch backend's coalition row of round ``r``: the same fold order and one division in fp32 torch, the
+        torch held-out forward (``contribution_dtype = torch.float64``: the oracle on the same buffers)."""
+        lead = self.clients[0]
+        co, dt, P = lead.hist.co, self.contribution_dtype, lead.P
+        loss, hits = coalition_utilities_torch([b[:P] for b in bufs], [float(w) for w in self._co_cw[r]],
+                                               lead.global_params.detach().cpu().to(dt), co["masks"], int(co["sampled"][r]),
+                                               lead.dims, lead.ho_X.cpu(), lead.ho_y.cpu())
+        if dt == torch.float64 and co["loss"].dtype != np.float64:
+            co["loss"] = co["loss"].astype(np.float64)
+        co["loss"][r], co["correct"][r] = loss, hits
 
     # ---- rounds ----
     def _round_hip(self, r: int) -> None:
@@ -177,6 +237,9 @@ class ClientGroup:
         if lead.attack_stage:
             # Byzantine attack model: one launch rewrites the bad sampled clients' buffers in place
             self._agg.attack(par, s)
+        if lead.contribution and r % self._co_every == 0:
+            # contribution scores: the coalition models of the buffers as they stand, before the sum overwrites them
+            self._coalition.launch(par, s)
         if lead.robust:
             # one launch, in place: every client's buffer is a source and a destination; the round's
             # live flag, index and sampled mask are the lead client's (identical on all)
@@ -219,6 +282,8 @@ class ClientGroup:
         if self.tamper is not None:
             self.tamper(self.rounds, bufs)
         self.clients[0].attack_rows(bufs)   # Byzantine attack model (nothing when off)
+        if self.clients[0].contribution and self.rounds % self._co_every == 0:
+            self._coalitions_torch(self.rounds, bufs)
         if self.clients[0].robust:
             tot = self.clients[0].robust_combine(bufs)
         elif self.clients[0].secagg:

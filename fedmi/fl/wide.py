@@ -44,7 +44,11 @@ class WideClient:
                  eval_rows: int = 0, allreduce_dtype: str = "fp32", warmup_rounds: int = 0,
                  fused_eval: Optional[bool] = None, server_opt: str = "none", aggregator: str = "mean",
                  compress: str = "none", secagg: bool = False, screen: str = "none", attack: str = "none",
-                 dpsgd_clip: float = 0.0, scaffold: bool = False):
+                 dpsgd_clip: float = 0.0, scaffold: bool = False, contribution: str = "none"):
+        if contribution != "none":
+            # the wide path all-reduces its buckets: nothing holds the individual contributions a coalition needs
+            raise ValueError(f"WideClient does not run contribution scores (contribution={contribution!r}); "
+                             "use ClientGroup (EngineConfig.contribution)")
         if scaffold:
             # the wide path's layered GEMMs accumulate gradients in place: no slab row carries a correction
             raise ValueError("WideClient does not run SCAFFOLD control variates (scaffold=True); "

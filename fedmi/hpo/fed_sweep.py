@@ -92,6 +92,9 @@ class FedTrialGroup:
         if bool(getattr(base, "scaffold", False)):
             # the batched launches have no capture launch, and every trial would need variates of its own
             raise ValueError("fed_sweep does not run SCAFFOLD trials (scaffold)")
+        if getattr(base, "contribution", "none") != "none":
+            # the trials share launches; a coalition table, scratch and held-out rows per trial are not batched
+            raise ValueError("fed_sweep does not run contribution-score trials (contribution)")
         if base.server_opt != "none":
             # the trials share launches and one collective; a server step per trial is not batched
             raise ValueError("fed_sweep does not run server-optimizer trials (server_opt)")

@@ -111,10 +111,11 @@ def _build_lock():
 # fl_mx.hip is held bit for bit to mx_quantize: the frame's four operations are one rounding each.
 # fl_train_dpsgd.hip's row norms, clip factors and noise are separate _rn operations in one fixed order.
 # fl_scaffold.hip's column sums, differences and the fold are held bit for bit to fedmi/fl/scaffold.py.
+# fl_coalition.hip's coalition images are held bit for bit to coalition_images_model: separate adds, one division.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _SOURCE_FLAGS = {"fl_lowrank.hip": _NO_PACKED_FP32, "fl_auc.hip": _NO_PACKED_FP32, "fl_cclip.hip": _NO_PACKED_FP32,
                  "fl_mx.hip": _NO_PACKED_FP32, "fl_train_dpsgd.hip": _NO_PACKED_FP32,
-                 "fl_scaffold.hip": _NO_PACKED_FP32}
+                 "fl_scaffold.hip": _NO_PACKED_FP32, "fl_coalition.hip": _NO_PACKED_FP32}
 
 
 def _compile(src: str, digest: str) -> str:

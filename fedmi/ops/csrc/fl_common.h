@@ -611,6 +611,42 @@ struct FLAuc {
     unsigned long long* hist_u2;  // [max_rounds][C]
 };
 
+// Coalition utilities (fl_coalition.hip): parameters of the build, row and fold launches that score the M
+// coalitions of a static mask table on the held-out rows before a round's aggregation, passed to those kernels
+// alone, as FLHeldout is.  Every buffer is caller-owned.  A live round r leaves hist_loss[r][m] = the fp32 SUM of
+// the rows' softmax cross-entropies and hist_correct[r][m] = the rows classified correctly (first-maximum argmax)
+// under coalition m's model: over T' = masks[m] & (the round's sampled clients), num = the left fold from +0 in
+// client order of the members' contribution images, den = the same fold of their weights cw[r][i], the model
+// num / den (one division); T' empty: the image x the round trained from; image padding exact 0.
+#define FL_COALITION_MAX_K 64        // width of the rtab mask
+#define FL_COALITION_MAX_M 4096
+#define FL_COALITION_THREADS 256     // build kernel: floats / float4s of the image per workgroup, masks per LDS tile
+struct FLCoalition {
+    int K;                            // sources, 1 .. FL_COALITION_MAX_K (source k is client k)
+    int M;                            // coalitions, 1 .. FL_COALITION_MAX_M
+    int max_rounds;                   // rounds of rtab / cw / the histories; rounds past it are not live
+    const float* rtab;                // a client's per-round table (FLBuffers::rtab): the sampled mask
+    const float* cw;                  // [max_rounds][K] fp32 FedAvg weights of the clients' buffers
+    const unsigned long long* masks;  // [M] coalition masks, bit k = client k
+    float* scratch;                   // [M][Pimg] coalition images, then [M][slices] {correct, loss-sum bits} partials
+    const float* X;                   // score: the held-out set's rows and labels (FLHeldout::X, ::y)
+    const int* y;
+    int n;                            // score: 1 .. FL_HELDOUT_MAX_ROWS
+    float* hist_loss;                 // score: [max_rounds][M] fp32 loss SUMS
+    int* hist_correct;                // score: [max_rounds][M]
+};
+// row slices per coalition of the row launch: a function of the shapes alone (never a device query), so the
+// loss sum's order is the same on every machine (fedmi/fl/contribution.py coalition_slices)
+__host__ __device__ constexpr int fl_coalition_slices(int M, int n_blocks) {
+    const int s = 256 / M > 1 ? 256 / M : 1;
+    return s < n_blocks ? s : n_blocks;
+}
+// floats of scratch the launches need: the M images, then one partial pair per (coalition, row block) -- room
+// for any slice count up to one slice per row block
+__host__ __device__ constexpr long long fl_coalition_scratch_floats(int Pimg, int M, int n_blocks) {
+    return (long long)M * Pimg + 2ll * M * n_blocks;
+}
+
 struct PeerArgs;  // peer_device.h
 struct PeerPack;
 // Launchers (fl_kernels.hip). `pg` = image the round trains from (the previous round's
@@ -806,6 +842,18 @@ hipError_t fl_launch_auc_rank(const uint32_t* keys, int n, int C, int max_rounds
                               unsigned long long* out, hipStream_t s);
 hipError_t fl_launch_heldout_predict(const MLPDesc& d, int R, const float* X, int n, const float* params,
                                      float* proba, int* pred, hipStream_t s);
+// (fl_coalition.hip) coalition utilities of the round whose state is `st`.  Build: over the K buffers named by
+// the device table `src` (their first Pimg floats) and the image `x` the round trained from, the p.M coalition
+// images into p.scratch; sources are read once, nothing but the scratch is written.  Score: the row launch over
+// (coalition, row slice) -- `d` built for R = 16 or 32 rows; `slices` 0: fl_coalition_slices(M, blocks), else
+// 1 .. blocks (blocks: one workgroup per coalition and row block) -- and the fold launch into row r of
+// p.hist_loss / p.hist_correct.  A round that is not live writes nothing.  No per-round host argument: all
+// three launches are replayable.  fl_set_lds_limit_coalition: before the first score launch (dynamic LDS).
+hipError_t fl_set_lds_limit_coalition(size_t bytes);
+hipError_t fl_launch_coalition_build(const MLPDesc& d, const FLCoalition& p, const float* const* src, const float* x,
+                                     const FLState* st, hipStream_t s);
+hipError_t fl_launch_coalition_score(const MLPDesc& d, int R, const FLCoalition& p, int slices, const FLState* st,
+                                     hipStream_t s);
 // `prev_out` (may be null): the other parameter buffer -- the round before pg's output.  When
 // the fold finds a late stop (FLState::late) pg's image is replaced by it.
 hipError_t fl_launch_finalize(const MLPDesc& d, const FLConfig& c, const FLBuffers& b,

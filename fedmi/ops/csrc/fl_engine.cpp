@@ -1737,6 +1737,70 @@ static void cclip_aggregate(std::vector<int> dims, int iters, double tau, uintpt
                               as_ptr<const unsigned long long>(keep), dst_addrs.data()));
 }
 
+// Coalition utilities (fl_coalition.hip) across engines' buffers, as robust_aggregate is.  Build: the M coalition
+// images of the mask table `masks` (M uint64 on the device) over the K buffers of the device table `src`, the
+// image `x` the round trained from and the weight table `cw` ([max_rounds, K] fp32), into `scratch`
+// (coalition_scratch_floats(dims, M, n, R) caller-owned floats: the images first).  Score: those images on the n
+// held-out rows (X, y) at R = 16 or 32 rows per block, round r's row of `hist_loss` / `hist_correct`
+// ([max_rounds, M] fp32 loss sums / int32 correct rows); `slices` 0: coalition_slices(M, blocks).
+static FLCoalition coalition_args(const char* who, int K, int M, int max_rounds, uintptr_t scratch) {
+    if (K < 1 || K > FL_COALITION_MAX_K)
+        throw std::runtime_error(std::string(who) + ": 1.." + std::to_string(FL_COALITION_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (M < 1 || M > FL_COALITION_MAX_M)
+        throw std::runtime_error(std::string(who) + ": 1.." + std::to_string(FL_COALITION_MAX_M) + " coalitions, got " +
+                                 std::to_string(M));
+    if (max_rounds < 1 || !scratch) throw std::runtime_error(std::string(who) + ": bad arguments");
+    FLCoalition p;
+    std::memset(&p, 0, sizeof(p));
+    p.K = K;
+    p.M = M;
+    p.max_rounds = max_rounds;
+    p.scratch = as_ptr<float>(scratch);
+    return p;
+}
+
+static void coalition_build(std::vector<int> dims, uintptr_t src, int K, uintptr_t x, uintptr_t masks, int M, uintptr_t cw,
+                            uintptr_t scratch, uintptr_t state, uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    const MLPDesc d = desc_of(dims, "coalition_build");
+    FLCoalition p = coalition_args("coalition_build", K, M, max_rounds, scratch);
+    if (!src || !x || !masks || !cw || !state || !rtab) throw std::runtime_error("coalition_build: bad arguments");
+    p.rtab = as_ptr<const float>(rtab);
+    p.cw = as_ptr<const float>(cw);
+    p.masks = as_ptr<const unsigned long long>(masks);
+    HIP_CHECK(fl_launch_coalition_build(d, p, as_ptr<const float* const>(src), as_ptr<const float>(x),
+                                        as_ptr<const FLState>(state), as_stream(stream)));
+}
+
+static MLPDesc coalition_rows_desc(const std::vector<int>& dims, int R, const char* who) {
+    desc_of(dims, who);
+    if (R != 16 && R != 32) throw std::runtime_error(std::string(who) + ": R must be 16 or 32");
+    MLPDesc d;
+    fl_build_fp32_layout(dims.data(), (int)dims.size() - 1, R, &d);
+    return d;
+}
+
+static void coalition_score(std::vector<int> dims, int R, int K, int M, uintptr_t scratch, uintptr_t X, uintptr_t y, int n,
+                            uintptr_t hist_loss, uintptr_t hist_correct, uintptr_t state, int max_rounds,
+                            uintptr_t stream, int slices) {
+    // (the row kernels' dynamic LDS limit is set outside a capture: a captured sequence follows an eager one)
+    const MLPDesc d = coalition_rows_desc(dims, R, "coalition_score");
+    FLCoalition p = coalition_args("coalition_score", K, M, max_rounds, scratch);
+    if (!X || !y || !hist_loss || !hist_correct || !state) throw std::runtime_error("coalition_score: bad arguments");
+    const size_t bytes = (size_t)d.lds_floats * 4;
+    if (bytes > FL_LDS_DYNAMIC_MAX)
+        throw std::runtime_error("coalition_score: the fp32 forward pass of the row kernel exceeds LDS");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_CHECK(hipStreamIsCapturing(as_stream(stream), &cap));
+    if (cap == hipStreamCaptureStatusNone) HIP_CHECK(fl_set_lds_limit_coalition(bytes));
+    p.X = as_ptr<const float>(X);
+    p.y = as_ptr<const int>(y);
+    p.n = n;
+    p.hist_loss = as_ptr<float>(hist_loss);
+    p.hist_correct = as_ptr<int>(hist_correct);
+    HIP_CHECK(fl_launch_coalition_score(d, R, p, slices, as_ptr<const FLState>(state), as_stream(stream)));
+}
+
 // Multi-Krum screening (fl_screen.hip) across engines' buffers, as robust_aggregate is.  `src`: device table
 // of K buffer addresses (int64); `dist`: K x K floats; `keep`: one uint64; `hist`: max_rounds uint64, all
 // caller-owned; `f` / `m`: Byzantine clients assumed and clients kept (0: K_r - f).
@@ -2024,6 +2088,17 @@ PYBIND11_MODULE(_fedmi_hip, m) {
     });
     m.attr("CCLIP_SLOT") = (int)FL_CCLIP_SLOT;
     m.attr("CCLIP_MAX_ITERS") = (int)FL_CCLIP_MAX_ITERS;
+    m.def("coalition_build", &coalition_build, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("x"),
+          py::arg("masks"), py::arg("M"), py::arg("cw"), py::arg("scratch"), py::arg("state"), py::arg("rtab"),
+          py::arg("max_rounds"), py::arg("stream"));
+    m.def("coalition_score", &coalition_score, py::arg("dims"), py::arg("R"), py::arg("K"), py::arg("M"),
+          py::arg("scratch"), py::arg("X"), py::arg("y"), py::arg("n"), py::arg("hist_loss"), py::arg("hist_correct"),
+          py::arg("state"), py::arg("max_rounds"), py::arg("stream"), py::arg("slices") = 0);
+    m.def("coalition_scratch_floats", [](const std::vector<int>& dims, int M, int n, int R) {
+        return fl_coalition_scratch_floats(coalition_rows_desc(dims, R, "coalition_scratch_floats").Pimg, M, (n + R - 1) / R);
+    });
+    m.def("coalition_slices", [](int M, int n_blocks) { return fl_coalition_slices(M, n_blocks); });
+    m.attr("COALITION_MAX_M") = (int)FL_COALITION_MAX_M;
     m.def("screen_dist", &screen_dist, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("dist"), py::arg("state"),
           py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("tile") = 0);
     m.def("screen_select", &screen_select, py::arg("dist"), py::arg("K"), py::arg("f"), py::arg("m"), py::arg("keep"),
