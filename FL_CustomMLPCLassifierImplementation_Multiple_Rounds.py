@@ -104,14 +104,23 @@ def parse_args(argv=None):
                          "(times 1 / clients), > 0")
     ap.add_argument("--cclip-iters", type=int, default=3,
                     help="--aggregator cclip: clipping iterations from the previous global model, 1 .. 8")
-    ap.add_argument("--screen", choices=["none", "multi_krum"], default="none",
+    ap.add_argument("--screen", choices=["none", "multi_krum", "dnc"], default="none",
                     help="client screening in front of the aggregator: multi_krum (Blanchard et al. 2017) keeps the "
-                         "clients whose whole models lie closest to their neighbours; --aggregator mean then averages "
+                         "clients whose whole models lie closest to their neighbours; dnc (Shejwalkar and Houmansadr "
+                         "2021) drops the clients that project most strongly onto the top direction of the centred "
+                         "models; --aggregator mean then averages "
                          "the kept ones unweighted (not with --wide, --secagg, --dp-clip or --gather-plane xgmi)")
     ap.add_argument("--screen-byzantine", type=int, default=0,
-                    help="--screen: Byzantine clients assumed, f (every round needs 2 f + 3 sampled clients)")
+                    help="--screen: Byzantine clients assumed, f (multi_krum: every round needs 2 f + 3 sampled clients; "
+                         "dnc: sampled clients - iters * ceil(c f) >= 1)")
     ap.add_argument("--screen-keep", type=int, default=None,
-                    help="--screen: clients kept per round, m (default: sampled clients - f; 1 = Krum)")
+                    help="--screen multi_krum: clients kept per round, m (default: sampled clients - f; 1 = Krum)")
+    ap.add_argument("--screen-iters", type=int, default=1, help="--screen dnc: iterations, 1 .. 8")
+    ap.add_argument("--screen-subsample", type=float, default=1.0,
+                    help="--screen dnc: fraction of the parameters each iteration looks at, in (0, 1]")
+    ap.add_argument("--screen-filter", type=float, default=1.0,
+                    help="--screen dnc: c; an iteration drops ceil(c f) clients")
+    ap.add_argument("--screen-seed", type=int, default=0, help="--screen dnc: seed of the coordinate subsets")
     ap.add_argument("--attack", choices=["none", "sign_flip", "gauss", "alie", "ipm", "label_flip"], default="none",
                     help="Byzantine attack model of the --attack-clients: sign_flip = own update reversed and scaled; "
                          "gauss = own model plus Gaussian noise; alie = 'A Little Is Enough' (Baruch et al. 2019); "
@@ -278,7 +287,9 @@ def _aggregator_fields(a) -> dict:
 
 
 def _screen_fields(a) -> dict:
-    return dict(screen=a.screen, screen_byzantine=a.screen_byzantine, screen_keep=a.screen_keep)
+    return dict(screen=a.screen, screen_byzantine=a.screen_byzantine, screen_keep=a.screen_keep,
+                screen_iters=a.screen_iters, screen_subsample=a.screen_subsample, screen_filter=a.screen_filter,
+                screen_seed=a.screen_seed)
 
 
 def _attack_fields(a) -> dict:
@@ -413,7 +424,8 @@ def main(argv=None):
         from fedmi.fl.engine import screen_id
         screen_id(EngineConfig(**_dp_fields(a), **_secagg_fields(a), **_gather_fields(a), **_screen_fields(a)))
     except ValueError as e:
-        raise SystemExit(f"--screen / --screen-byzantine / --screen-keep: {e}")
+        raise SystemExit(f"--screen / --screen-byzantine / --screen-keep / --screen-iters / --screen-subsample / "
+                         f"--screen-filter / --screen-seed: {e}")
     if a.wide and a.attack != "none":
         raise SystemExit("--attack is not supported with --wide")
     try:

@@ -66,6 +66,47 @@ the ``CENTERED_AGGREGATORS`` entry, id 4 in ``AGGREGATOR_NAMES``.  With ``T = cc
 the sum in client order from ``+0``, the divisor ``K_r`` whoever is included; nobody included: ``z`` stays.
 :func:`cclip_model` is the bit-exact fp32 model of the launches (``fedmi/ops/csrc/fl_cclip.hip``), with the
 geometric median's distance order; :func:`cclip_torch` the rule in the tensor's dtype.
+
+Spectral screening, DnC (``screen="dnc"``, the ``SPECTRAL_SCREENS`` entry, id 2 in ``SCREEN_NAMES``;
+Shejwalkar and Houmansadr 2021, "Manipulating the Byzantine", Algorithm 2) judges DIRECTIONS, which neither the
+coordinate rules nor the distance rules do: colluders that agree with each other (ALIE, IPM) stay inside the
+honest spread in every coordinate and at an ordinary distance from everybody, but put variance into one
+direction of update space.  With ``S`` the sampled clients, ``K_r = |S|``, ``f = screen_byzantine``,
+``q = ceil(screen_filter * f)`` (:func:`dnc_drop_count`) and ``v_i`` client i's parameter image, per round:
+
+1. *Coordinate subset.*  For iteration ``t = 0 .. screen_iters - 1``, ``R_t`` is a subset of the image
+   positions that hold a real parameter.  ``screen_subsample == 1``: all of them, no draw.  Otherwise position
+   ``p`` is in ``R_t`` iff lane ``p % 4`` of Philox4x32-10 at counter ``(p // 4, round, t, DNC_STREAM)`` under
+   the key ``screen_seed`` is ``< floor(screen_subsample * 2**32)`` (:func:`dnc_subset`).
+2. *Centred values.*  For ``p`` in ``R_t``, ``mu[p]`` is the mean over the clients of ``S`` whose value at
+   ``p`` is finite, the sum in client order from ``+0`` with one division; ``c_i[p] = v_i[p] - mu[p]``.  A
+   non-finite ``v_i[p]`` gives ``c_i[p] = 0`` and marks client i *bad*.  "Finite" is ``|v| < 2**60``
+   (``DNC_HUGE``): the square of anything larger leaves fp32, and one such client inside the mean would push
+   every honest client's centred values out of range with it.  Unsampled clients and positions outside ``R_t``
+   give 0.
+3. *Gram matrix.*  ``G_t[i][j] = sum_p c_i[p] c_j[p]``.  A client is also bad if ``G_t[i][i]`` is not a
+   finite fp32 number.
+4. *Score.*  Power iteration on ``G_t`` restricted to the sampled clients that are not bad: ``w_0 = G_t e_j``
+   with ``j`` the client of largest ``G_t[j][j]`` (lowest index on ties) -- the all-ones vector is in the null
+   space of a centred Gram matrix and must not be the start -- scaled by ``1 / max|w_0|``; then
+   ``DNC_POWER = 32`` times ``w <- G_t w`` (client order), ``w <- w / max|w|``; a zero vector stays zero.
+   ``score_i = w_i^2``, the squared projection on the top right singular vector of the centred matrix up to
+   one common factor.  Bad clients score ``+inf``.
+5. *Keep.*  The ``K_r - q`` lowest scores are kept, compared on the sortable key with ties to the lower
+   index; bad clients are always removed, even when there are more than ``q`` of them.  The kept word is the
+   AND over ``t`` of the iterations' kept sets, ANDed with ``S``.  If that word is empty the screen abstains and
+   the kept word is ``S``, as multi-Krum keeps everybody where its rule is undefined: an aggregator never runs
+   over no client.  This is reachable: the ``2**60`` cut only moves the cliff, and one finite colluder near
+   ``1e18`` shifts ``mu`` far enough that every honest diagonal overflows fp32 and every client is bad; what such
+   a round aggregates is then the configured rule's business (the median survives it, the mean does not).
+6. *Hand-off.*  The aggregator runs over the kept word exactly as behind multi-Krum (unweighted mode);
+   ``"mean"`` is the unweighted mean of the kept, DnC as published.  Every round needs
+   ``K_r - screen_iters * q >= 1``.
+
+:func:`dnc_select_ref` is that text in numpy, in float32 what the torch engines run and in float64 the oracle
+of the kernels (``fedmi/ops/csrc/fl_dnc.hip``: an MFMA Gram kernel over image chunks and a one-workgroup
+select kernel).  The kernels' sums have their own order, so they are held to the oracle by a dot-product bound
+on the Gram entries and by equal words, not bit for bit.
 """
 from __future__ import annotations
 
@@ -87,7 +128,16 @@ CENTERED_AGGREGATORS = ("cclip",)
 AGGREGATOR_NAMES = ALL_AGGREGATORS + CENTERED_AGGREGATORS
 MAX_ROBUST_CLIENTS = 64   # width of the per-round sampled-client mask (fl_common.h FL_ROBUST_MAX_K)
 SCREENS = ("none", "multi_krum")
+# screens that judge directions (a Gram matrix and its top eigenvector); ids follow SCREENS'
+SPECTRAL_SCREENS = ("dnc",)
+# every screen: what the validators accept, and the order of the engines' ``screen`` ids (dnc: 2)
+SCREEN_NAMES = SCREENS + SPECTRAL_SCREENS
 _SCREEN_THREADS = 256     # workgroup of the distance kernel (fl_screen.hip FL_SCREEN_THREADS)
+DNC_MAX_ITERS = 8         # fl_common.h FL_DNC_MAX_ITERS
+DNC_POWER = 32            # power steps per iteration (fl_common.h FL_DNC_POWER)
+DNC_STREAM = 0x53434E44   # Philox stream of the coordinate subsets (fl_common.h FL_DNC_STREAM, "DNCS")
+DNC_HUGE = 2.0 ** 60      # a value of this magnitude or more counts as non-finite (fl_common.h FL_DNC_HUGE)
+DNC_SLOT = 192 + 64 * 64  # floats of one iteration's record in the scratch (fl_common.h FL_DNC_SLOT)
 GEOMED_MAX_ITERS = 32     # fl_common.h FL_GEOMED_MAX_ITERS
 GEOMED_BLOCK = 256        # floats of the image per block of a distance sum (fl_common.h FL_GEOMED_THREADS)
 GEOMED_SLOT = 192         # floats of one iteration's record in the scratch (fl_common.h FL_GEOMED_SLOT)
@@ -105,6 +155,37 @@ def cclip_scratch_floats(pimg: int, iters: int) -> int:
     """Floats of scratch the cclip launches need for an image of ``pimg`` floats (fl_common.h
     fl_cclip_scratch_floats): two sets of 64 distance partials per block of 256, then ``iters`` records."""
     return 2 * ((int(pimg) + GEOMED_BLOCK - 1) // GEOMED_BLOCK) * MAX_ROBUST_CLIENTS + int(iters) * CCLIP_SLOT
+
+
+def dnc_chunks(pimg: int, k: int) -> int:
+    """Workgroups per iteration of the DnC Gram kernel (fl_common.h fl_dnc_chunks): chunks of 256 image floats
+    up to 32 clients, of 128 above."""
+    w = 256 if int(k) <= 32 else 128
+    return (int(pimg) + w - 1) // w
+
+
+def dnc_partial_floats(k: int) -> int:
+    """Floats of one workgroup's Gram partial (fl_common.h fl_dnc_partial_floats): KB x KB and the bad word."""
+    kb = 16 if int(k) <= 16 else (32 if int(k) <= 32 else 64)
+    return kb * kb + 4
+
+
+def dnc_scratch_floats(pimg: int, iters: int, k: int) -> int:
+    """Floats of scratch the DnC launches need (fl_common.h fl_dnc_scratch_floats): ``iters`` x chunks Gram
+    partials, then ``iters`` iteration records of ``DNC_SLOT`` floats."""
+    return int(iters) * dnc_chunks(pimg, k) * dnc_partial_floats(k) + int(iters) * DNC_SLOT
+
+
+def dnc_drop_count(f: int, c: float) -> int:
+    """Clients one DnC iteration drops: ``ceil(c f)``."""
+    return int(math.ceil(float(c) * int(f)))
+
+
+def dnc_threshold(subsample: float) -> int:
+    """The subset test's Philox threshold ``floor(subsample * 2**32)``; 0 stands for ``subsample == 1``
+    (every coordinate, no draw)."""
+    s = float(subsample)
+    return 0 if s >= 1.0 else int(math.floor(s * 2.0 ** 32))
 
 
 def trim_count(kind: str, beta: float, k_r: int) -> int:
@@ -154,7 +235,13 @@ class _AggLaunch:
             # distance partials and the iterations' records (weights, distances, combined mask) of the geomed launches
             self._geomed = torch.zeros(geomed_scratch_floats(lead.Pimg, int(lead.cfg.geomed_iters)),
                                        dtype=torch.float32, device=lead.device)
-        if getattr(lead, "screen", 0):
+        self._dnc = None
+        if getattr(lead, "screen", 0) == 2:
+            # DnC: the Gram partials and the iterations' records (scores, diagonal, words, folded matrix)
+            self._dnc = torch.zeros(dnc_scratch_floats(lead.Pimg, int(lead.cfg.screen_iters), self._k),
+                                    dtype=torch.float32, device=lead.device)
+            self._keep = torch.zeros(2, dtype=torch.int64, device=lead.device)
+        elif getattr(lead, "screen", 0):
             self._dist = torch.zeros(self._k * self._k, dtype=torch.float32, device=lead.device)
             self._keep = torch.zeros(2, dtype=torch.int64, device=lead.device)
         self._wtab = None
@@ -174,7 +261,18 @@ class _AggLaunch:
         the rule takes the kept clients."""
         e = self._lead
         keep = ()   # (no screen: the call is the one it was before screening existed, argument for argument)
-        if self._keep is not None:
+        if self._dnc is not None:
+            # DnC (fl_dnc.hip): the Gram and select launches, whatever screen_iters is
+            word = self._keep.data_ptr() + 8 * par
+            keep = (word,)
+            c = e.cfg
+            f, iters = int(c.screen_byzantine), int(c.screen_iters)
+            q = dnc_drop_count(f, c.screen_filter)
+            e.m.dnc_gram(e.dims, self._src[par].data_ptr(), self._k, f, q, iters, dnc_threshold(c.screen_subsample),
+                         int(c.screen_seed), self._dnc.data_ptr(), *self._round(par), int(c.max_rounds), stream)
+            e.m.dnc_select(e.dims, self._k, f, q, iters, self._dnc.data_ptr(), word, e.screen_hist.data_ptr(),
+                           *self._round(par), int(c.max_rounds), stream)
+        elif self._keep is not None:
             word = self._keep.data_ptr() + 8 * par
             keep = (word,)
             e.m.screen_dist(e.dims, self._src[par].data_ptr(), self._k, self._dist.data_ptr(), *self._round(par),
@@ -661,6 +759,75 @@ def screen_select(dist, active: Sequence[bool], f: int, m: Optional[int] = None)
     skey = {i: int(_key32(np.array([scores[i]], np.float32))[0]) for i in S}
     kept = set(sorted(S, key=lambda i: (skey[i], i))[:want])
     return [i in kept for i in range(K)]
+
+
+def dnc_subset(real, subsample: float, seed: int, round: int, t: int) -> np.ndarray:
+    """``R_t`` as flags over the image positions (step 1 of the DnC rule of the module docstring)."""
+    from ..privacy.philox import param_words
+    real = np.asarray(real, bool).reshape(-1)
+    thr = dnc_threshold(subsample)
+    if thr == 0:
+        return real.copy()
+    return real & (param_words(real.shape[0], int(round), int(t), int(seed), DNC_STREAM).astype(np.uint64) < thr)
+
+
+def dnc_select_ref(stack, active: Sequence[bool], real, f: int, c: float, iters: int, subsample: float, seed: int,
+                   round: int, dtype=np.float64):
+    """The DnC rule of the module docstring over the parameter images ``stack`` [K, Pimg] (``real`` [Pimg]: the
+    positions that hold a parameter), in ``dtype``: float32 is what the torch engines run, float64 the oracle of
+    the kernels.  Returns ``(kept, records)``: the kept list of K bools and per iteration ``{"scores", "bad",
+    "kept", "gram"}`` -- scores [K] (``+inf``: bad, 0: not sampled), the bad and kept clients as lists of bools,
+    the K x K Gram matrix."""
+    a = np.ascontiguousarray(np.asarray(stack, np.float32))
+    real = np.asarray(real, bool).reshape(-1)
+    K, n = a.shape
+    act = [bool(x) for x in active]
+    if real.shape[0] != n or len(act) != K:
+        raise ValueError("dnc_select_ref: needs [K, Pimg] images, Pimg flags and K mask entries")
+    if not 1 <= int(iters) <= DNC_MAX_ITERS:
+        raise ValueError(f"dnc_select_ref: iters must be in [1, {DNC_MAX_ITERS}], got {iters!r}")
+    dt = np.dtype(dtype)
+    S = [i for i in range(K) if act[i]]
+    want = max(len(S) - dnc_drop_count(f, c), 0)
+    fmax = float(np.finfo(np.float32).max)
+    kept_all, records = set(S), []
+    with np.errstate(all="ignore"):
+        fin = np.abs(a) < np.float32(DNC_HUGE)     # (false for NaN)
+        for t in range(int(iters)):
+            sub = dnc_subset(real, subsample, seed, round, t)
+            cen = np.zeros((K, n), dt)
+            if S:
+                s, cnt = np.zeros(n, dt), np.zeros(n, dt)
+                for i in S:                        # client order from +0, one division
+                    s = np.where(fin[i], s + a[i].astype(dt), s)
+                    cnt = cnt + fin[i]
+                mu = np.where(cnt > 0, s / np.maximum(cnt, 1), 0).astype(dt)
+                for i in S:
+                    cen[i] = np.where(sub & fin[i], a[i].astype(dt) - mu, 0)
+            gram = cen @ cen.T
+            diag = np.diagonal(gram)
+            bad = [act[i] and (bool((sub & ~fin[i]).any()) or not abs(float(diag[i])) <= fmax) for i in range(K)]
+            good = [i for i in S if not bad[i]]
+            scores = np.zeros(K, dt)
+            scores[[i for i in range(K) if bad[i]]] = np.inf
+            if good:
+                g = gram[np.ix_(good, good)]
+                w = g[:, int(np.argmax(np.diagonal(g)))].copy()   # (argmax: the first of equal maxima)
+                for step in range(DNC_POWER + 1):
+                    if step:
+                        w = g @ w
+                    mx = np.abs(w).max()
+                    if mx > 0:
+                        w = w / mx
+                scores[good] = w * w
+            order = sorted(S, key=lambda i: (int(_key32(np.array([scores[i]], np.float32))[0])
+                                             if dt == np.float32 else float(scores[i]), i))
+            kept = set(i for i in order[:want] if not bad[i])
+            kept_all &= kept
+            records.append({"scores": scores, "bad": bad, "kept": [i in kept for i in range(K)], "gram": gram})
+    if not kept_all:
+        kept_all = set(S)     # nobody survives: the screen abstains
+    return [i in kept_all for i in range(K)], records
 
 
 def mask_bits(mask: Sequence[bool]) -> int:

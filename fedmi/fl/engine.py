@@ -30,8 +30,9 @@ import torch
 
 from ..models.mlp import (MLPModel, dense_to_image, flat_to_dict, image_layout, image_to_dense,
                           param_count)
-from .aggregate import (AGGREGATOR_NAMES, AGGREGATORS, CCLIP_MAX_ITERS, GEOMED_MAX_ITERS, MAX_ROBUST_CLIENTS, SCREENS,
-                        _AggLaunch, _ScaffoldLaunch, cclip_torch, geomed_torch, mask_bits, pair_distances_torch,
+from .aggregate import (AGGREGATOR_NAMES, AGGREGATORS, CCLIP_MAX_ITERS, DNC_MAX_ITERS, GEOMED_MAX_ITERS,
+                        MAX_ROBUST_CLIENTS, SCREEN_NAMES, _AggLaunch, _ScaffoldLaunch, cclip_torch, dnc_drop_count,
+                        dnc_select_ref, dnc_threshold, geomed_torch, mask_bits, pair_distances_torch,
                         robust_aggregate_torch, screen_select)
 from .attack import (ATTACKS, DEVICE_ATTACKS, MAX_ATTACK_CLIENTS, attack_clients, attack_id, attack_params,
                      attack_torch)
@@ -256,9 +257,20 @@ class EngineConfig:
     # history()["screen_kept"] holds each round's kept mask (bit k = client k).  "none": off (nothing of a
     # round changes); one client: off.  Not with secagg, dp_clip > 0, gather_plane="xgmi", more than 64
     # clients, trial batches (comm_buffers), fed_sweep or WideClient.
+    # "dnc" (Shejwalkar and Houmansadr 2021, Algorithm 2; the rule is specified in fedmi/fl/aggregate.py) screens
+    # by DIRECTION: screen_iters times it centres the sampled clients' models over a coordinate subset (the
+    # fraction screen_subsample of the parameters, drawn per round and iteration from screen_seed -- config, not
+    # state), finds the top eigenvector of their Gram matrix and drops the q = ceil(screen_filter *
+    # screen_byzantine) clients that project most strongly onto it; clients with non-finite values are always
+    # dropped.  A client is kept when every iteration keeps it.  The rule decides how many it keeps: screen_keep
+    # must be None, and every round needs K_r - screen_iters * q >= 1.  Everything else as for "multi_krum".
     screen: str = "none"
     screen_byzantine: int = 0
     screen_keep: Optional[int] = None
+    screen_iters: int = 1
+    screen_subsample: float = 1.0
+    screen_filter: float = 1.0
+    screen_seed: int = 0
     # Byzantine attack model (fedmi/fl/attack.py, the specification): the clients / ranks attack_clients are
     # Byzantine and publish, every round they are sampled in, "sign_flip": their own update reversed and scaled
     # by attack_scale; "gauss": their model plus attack_scale * N(0, I) (Philox words of (attack_seed, round,
@@ -316,6 +328,10 @@ class EngineConfig:
         if not self.scaffold:
             # (off: a checkpoint's config record is what it was before the field existed)
             del d["scaffold"]
+        if self.screen != "dnc":
+            # (another screen: a checkpoint's config record is what it was before the DnC fields existed)
+            for k in ("screen_iters", "screen_subsample", "screen_filter", "screen_seed"):
+                del d[k]
         if self.aggregator != "cclip":
             # (another rule: a checkpoint's config record is what it was before the cclip fields existed)
             for k in ("cclip_tau", "cclip_iters"):
@@ -446,18 +462,36 @@ def aggregator_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
 
 def screen_id(cfg: EngineConfig, world: Optional[int] = None) -> int:
     """Validate the screening fields and what a screen does not combine with; the screen's index in
-    ``SCREENS`` (0 = off).  ``world``: the federation's size when the caller knows it -- one client
+    ``SCREEN_NAMES`` (0 = off).  ``world``: the federation's size when the caller knows it -- one client
     switches the screen off, so nothing is refused there; None (the entry point, before the
     communicator exists) checks the combinations as for several clients.  The per-round bounds
     (``K_r >= 2 f + 3``, ``screen_keep <= K_r - f``) need the sampled counts: the engines check them."""
-    if not isinstance(cfg.screen, str) or cfg.screen not in SCREENS:
-        raise ValueError(f"screen must be one of {SCREENS}, got {cfg.screen!r}")
+    if not isinstance(cfg.screen, str) or cfg.screen not in SCREEN_NAMES:
+        raise ValueError(f"screen must be one of {SCREEN_NAMES}, got {cfg.screen!r}")
     f, m = cfg.screen_byzantine, cfg.screen_keep
     if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or int(f) < 0:
         raise ValueError(f"screen_byzantine must be an integer >= 0, got {f!r}")
     if m is not None and (isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1):
         raise ValueError(f"screen_keep must be None or an integer >= 1, got {m!r}")
-    kind = SCREENS.index(cfg.screen)
+    T = cfg.screen_iters
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 1 <= int(T) <= DNC_MAX_ITERS:
+        raise ValueError(f"screen_iters must be an integer in [1, {DNC_MAX_ITERS}], got {T!r}")
+    for name in ("screen_subsample", "screen_filter"):
+        x = getattr(cfg, name)
+        try:
+            x = math.nan if isinstance(x, bool) else float(x)
+        except (TypeError, ValueError):
+            x = math.nan
+        if name == "screen_subsample" and not (0.0 < x <= 1.0 and (x == 1.0 or dnc_threshold(x) >= 1)):
+            raise ValueError(f"screen_subsample must be a number in (0, 1] (at least 2**-32), got {cfg.screen_subsample!r}")
+        if name == "screen_filter" and not (math.isfinite(x) and x > 0.0):
+            raise ValueError(f"screen_filter must be a finite number > 0, got {cfg.screen_filter!r}")
+    sd = cfg.screen_seed
+    if isinstance(sd, bool) or not isinstance(sd, (int, np.integer)) or not 0 <= int(sd) < 2 ** 64:
+        raise ValueError(f"screen_seed must be an integer in [0, 2**64), got {sd!r}")
+    kind = SCREEN_NAMES.index(cfg.screen)
+    if cfg.screen == "dnc" and m is not None:
+        raise ValueError(f"screen_keep must be None with screen='dnc' (the rule decides how many it keeps), got {m!r}")
     if not kind or (world is not None and int(world) <= 1):
         return 0
     if bool(cfg.secagg):
@@ -677,7 +711,7 @@ class RoundEngineBase:
         if self.robust and self.world > MAX_ROBUST_CLIENTS:
             raise ValueError(f"aggregator={cfg.aggregator!r} takes at most {MAX_ROBUST_CLIENTS} clients "
                              f"(the width of the sampled-client mask), got {self.world}")
-        # index in SCREENS, 0 = no screening; one client: off.  A screen turns the unweighted mode on
+        # index in SCREEN_NAMES, 0 = no screening; one client: off.  A screen turns the unweighted mode on
         # whatever the aggregator: "mean" over the kept clients is the trimmed-mean kind with beta = 0
         self.screen = screen_id(cfg, self.world)
         self.robust_beta = float(cfg.trim_ratio)
@@ -689,7 +723,13 @@ class RoundEngineBase:
                 self.robust, self.robust_beta = AGGREGATORS.index("trimmed_mean"), 0.0
             f = int(cfg.screen_byzantine)
             k_min = self.sampled_count()   # every round samples that many: no round needs a look
-            if k_min < 2 * f + 3:
+            if cfg.screen == "dnc":
+                q = dnc_drop_count(f, cfg.screen_filter)
+                if k_min - int(cfg.screen_iters) * q < 1:
+                    raise ValueError(f"screen='dnc' with screen_byzantine={f} drops up to screen_iters * ceil(screen_filter"
+                                     f" * screen_byzantine) = {int(cfg.screen_iters) * q} clients a round and must keep "
+                                     f"one, a round has {k_min}")
+            elif k_min < 2 * f + 3:
                 raise ValueError(f"screen={cfg.screen!r} with screen_byzantine={f} needs at least 2 f + 3 = {2 * f + 3} "
                                  f"sampled clients in every round, a round has {k_min}")
             if cfg.screen_keep is not None and not 1 <= int(cfg.screen_keep) <= k_min - f:
@@ -1523,7 +1563,16 @@ class TorchRoundEngine(RoundEngineBase):
         for b in bufs[1:]:
             out += b[:-1]
         active = [float(b[-1]) != 0.0 for b in bufs]
-        if self.screen:
+        if self.screen == 2:
+            # DnC: the rule of fedmi/fl/aggregate.py in fp32 over the clients' parameter images
+            c = self.cfg
+            imgs = np.stack([dense_to_image(row.numpy(), self.dims) for row in stack])
+            real = dense_to_image(np.ones(self.P, np.float32), self.dims) != 0
+            active, _ = dnc_select_ref(imgs, active, real, int(c.screen_byzantine), float(c.screen_filter),
+                                       int(c.screen_iters), float(c.screen_subsample), int(c.screen_seed),
+                                       self.rounds_issued, np.float32)
+            self.hist.screen[self.rounds_issued] = mask_bits(active)
+        elif self.screen:
             # multi-Krum: the rule runs over the clients the screen keeps (fp32 distances in torch's order)
             active = screen_select(pair_distances_torch(stack, active), active, int(self.cfg.screen_byzantine),
                                    self.cfg.screen_keep)
@@ -1967,7 +2016,7 @@ class HipRoundEngine(RoundEngineBase):
         # the configured rule (one client: the identity -- "mean"); a screen runs "mean" as the unweighted
         # mean of the kept clients
         self.layout["aggregator"] = cfg.aggregator if self.robust else AGGREGATORS[0]
-        self.layout["screen"] = SCREENS[self.screen]
+        self.layout["screen"] = SCREEN_NAMES[self.screen]
         if AGGREGATOR_NAMES[self.robust] == "geomed":
             self.layout["geomed"] = {"iters": int(cfg.geomed_iters), "nu": float(np.float32(cfg.geomed_nu)),
                                      "launches": int(cfg.geomed_iters) + 1}

@@ -27,7 +27,8 @@ client's image of the model the round trained from; ``cclip_torch`` on the CPU.
 With a client screen (``EngineConfig.screen``, multi-Krum) two more launches run in front of that one
 -- the pairwise distances of the sampled clients' images and the selection of the kept clients
 (``fl_screen.hip``) -- and the rule takes the kept clients; ``pair_distances_torch`` and
-``screen_select`` on the CPU.
+``screen_select`` on the CPU.  ``screen="dnc"`` puts its own two launches there (``fl_dnc.hip``: the MFMA Gram
+kernel and the select kernel); ``dnc_select_ref`` on the CPU.
 
 With secure aggregation (``EngineConfig.secagg``, ``fedmi/fl/secagg.py``) the k buffers are
 quantised and pair-masked before they are summed: one ``fl_secagg_mask`` launch over the k buffers

@@ -471,6 +471,45 @@ struct FLScreen {
     const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
 };
 
+// Spectral screening, DnC (fl_dnc.hip; Shejwalkar and Houmansadr 2021, Algorithm 2; fedmi/fl/aggregate.py is
+// the specification): parameters of the per-round Gram and select launches, passed to those kernels alone.
+// Per iteration t the Gram matrix of the round's sampled clients' images, centred per coordinate over a
+// Philox coordinate subset, then power iteration on it; the q clients of largest squared projection on the
+// top direction are dropped, the kept word is the AND over the iterations.
+#define FL_DNC_MAX_K 64              // width of the rtab mask; one lane per client in the select kernel
+#define FL_DNC_MAX_ITERS 8
+#define FL_DNC_POWER 32              // power steps per iteration
+#define FL_DNC_STREAM 0x53434E44u    // "DNCS": distinct from the DP, QSGD, rand-k, secagg, attack, MX and DP-SGD streams
+#define FL_DNC_HUGE 0x1p60f          // a value of this magnitude or more counts as non-finite: its square leaves fp32
+// rows of the LDS tile and of a Gram partial: the 16-wide MFMA tiles that hold K clients
+__host__ __device__ constexpr int fl_dnc_bucket(int K) { return K <= 16 ? 16 : (K <= 32 ? 32 : 64); }
+// image floats per workgroup of the Gram kernel, from the LDS budget: the centred KB x chunk fp32 tile (row
+// stride chunk + 8) is 33 KB at 32 x 256 and at 64 x 128 -- four workgroups per CU beside the 40 KB cross-wave
+// fold of the 64 bucket; 64 x 256 would be 66 KB, past the 64 KB a workgroup gets without opting in
+__host__ __device__ constexpr int fl_dnc_chunk(int K) { return K <= 32 ? 256 : 128; }
+__host__ __device__ constexpr int fl_dnc_chunks(int Pimg, int K) { return (Pimg + fl_dnc_chunk(K) - 1) / fl_dnc_chunk(K); }
+// one workgroup's partial record in the caller's scratch, floats: the KB x KB matrix (row-major; only the
+// 16 x 16 tiles of the upper triangle are written), then the bad-client word (two 32-bit halves) and 2 pad
+__host__ __device__ constexpr int fl_dnc_partial_floats(int K) { return fl_dnc_bucket(K) * fl_dnc_bucket(K) + 4; }
+// one iteration's record behind the partials, floats: [0, 64) scores (+inf: bad; 0: not sampled), [64, 128) the
+// Gram diagonal, [128, 130) the iteration's kept word, [130, 132) its bad word (32-bit halves), [192, 192 + 64 * 64)
+// the folded Gram matrix, row stride 64
+#define FL_DNC_SLOT (192 + 64 * 64)
+struct FLDnc {
+    int K;               // sources, 1 .. FL_DNC_MAX_K (source k is client k)
+    int f;               // Byzantine clients assumed, >= 0
+    int q;               // clients an iteration drops: ceil(c f), >= 0
+    int iters;           // iterations, 1 .. FL_DNC_MAX_ITERS
+    int max_rounds;      // rounds of rtab / entries of the kept-mask history; rounds past it are not live
+    uint32_t thresh;     // a position is in the subset iff its Philox word < thresh; 0: every position, no draw
+    uint32_t key0, key1; // Philox key: screen_seed, low and high word
+    const float* rtab;   // a client's per-round table (FLBuffers::rtab): the sampled mask
+};
+// floats of scratch the launches need: iters x chunks partials, then iters iteration records
+__host__ __device__ constexpr long long fl_dnc_scratch_floats(int Pimg, int iters, int K) {
+    return (long long)iters * fl_dnc_chunks(Pimg, K) * fl_dnc_partial_floats(K) + (long long)iters * FL_DNC_SLOT;
+}
+
 // Geometric-median aggregation (fl_geomed.hip; Pillutla et al. 2022, RFA): parameters of the per-round
 // smoothed-Weiszfeld launches, passed to those kernels alone.  From the coordinate-wise median of the
 // round's sampled clients (rtab mask), T times: squared whole-model distances d_i to the estimate,
@@ -771,6 +810,15 @@ hipError_t fl_launch_screen_dist(const MLPDesc& d, const FLScreen& p, const floa
                                  const FLState* st, hipStream_t s, int tile = 0);
 hipError_t fl_launch_screen_select(const FLScreen& p, const float* dist, unsigned long long* keep,
                                    unsigned long long* hist, const FLState* st, hipStream_t s);
+// (fl_dnc.hip) DnC spectral screening of the round whose state is `st`, over the K images named by the device
+// pointer table `src` (rows may be dword-aligned only).  Gram: every iteration's per-chunk Gram partials and
+// bad-client words into the caller-owned `scratch` (fl_dnc_scratch_floats).  Select: folds them in chunk order,
+// scores and ranks, writes each iteration's record (FL_DNC_SLOT, behind the partials), the kept-client mask
+// into `*keep` and `hist[round]`.  A round that is not live writes nothing.  Both replayable.
+hipError_t fl_launch_dnc_gram(const MLPDesc& d, const FLDnc& p, const float* const* src, float* scratch,
+                              const FLState* st, hipStream_t s);
+hipError_t fl_launch_dnc_select(const MLPDesc& d, const FLDnc& p, float* scratch, unsigned long long* keep,
+                                unsigned long long* hist, const FLState* st, hipStream_t s);
 // (fl_geomed.hip) geometric-median aggregate of the round whose state is `st`: the T + 1 launches of the
 // smoothed Weiszfeld iteration over the K buffers of Pimg + tails_len floats named by `src`, the result
 // into the n_dst buffers named by `dst` (they may be the sources).  `scratch`: fl_geomed_scratch_floats

@@ -1839,6 +1839,58 @@ static void screen_select(uintptr_t dist, int K, int f, int m, uintptr_t keep, u
                                       as_stream(stream)));
 }
 
+// DnC spectral screening (fl_dnc.hip) across engines' buffers, as screen_dist / screen_select are.  `scratch`:
+// dnc_scratch_floats(dims, iters, K) caller-owned floats; `q`: clients an iteration drops (ceil(c f)); `thresh`:
+// floor(subsample 2^32), 0 for "every coordinate"; `seed`: the subsets' 64-bit Philox key.
+static FLDnc dnc_args(const char* who, int K, int f, int q, int iters, uint32_t thresh, uint64_t seed, uintptr_t rtab,
+                      int max_rounds) {
+    if (K < 1 || K > FL_DNC_MAX_K)
+        throw std::runtime_error(std::string(who) + ": 1.." + std::to_string(FL_DNC_MAX_K) +
+                                 " clients (the width of the sampled-client mask), got " + std::to_string(K));
+    if (f < 0 || q < 0) throw std::runtime_error(std::string(who) + ": f and q must be >= 0");
+    if (iters < 1 || iters > FL_DNC_MAX_ITERS)
+        throw std::runtime_error(std::string(who) + ": iters must be in [1, " + std::to_string(FL_DNC_MAX_ITERS) + "]");
+    if (max_rounds < 1 || !rtab) throw std::runtime_error(std::string(who) + ": bad arguments");
+    FLDnc p;
+    std::memset(&p, 0, sizeof(p));
+    p.K = K;
+    p.f = f;
+    p.q = q;
+    p.iters = iters;
+    p.max_rounds = max_rounds;
+    p.thresh = thresh;
+    p.key0 = (uint32_t)seed;
+    p.key1 = (uint32_t)(seed >> 32);
+    p.rtab = as_ptr<const float>(rtab);
+    return p;
+}
+
+static long long dnc_scratch_floats(std::vector<int> dims, int iters, int K) {
+    const MLPDesc d = desc_of(dims, "dnc_scratch_floats");
+    if (K < 1 || K > FL_DNC_MAX_K || iters < 1 || iters > FL_DNC_MAX_ITERS)
+        throw std::runtime_error("dnc_scratch_floats: bad arguments");
+    return fl_dnc_scratch_floats(d.Pimg, iters, K);
+}
+
+static void dnc_gram(std::vector<int> dims, uintptr_t src, int K, int f, int q, int iters, uint32_t thresh,
+                     uint64_t seed, uintptr_t scratch, uintptr_t state, uintptr_t rtab, int max_rounds,
+                     uintptr_t stream) {
+    const MLPDesc d = desc_of(dims, "dnc_gram");
+    const FLDnc p = dnc_args("dnc_gram", K, f, q, iters, thresh, seed, rtab, max_rounds);
+    if (!src || !scratch || !state) throw std::runtime_error("dnc_gram: bad arguments");
+    HIP_CHECK(fl_launch_dnc_gram(d, p, as_ptr<const float* const>(src), as_ptr<float>(scratch),
+                                 as_ptr<const FLState>(state), as_stream(stream)));
+}
+
+static void dnc_select(std::vector<int> dims, int K, int f, int q, int iters, uintptr_t scratch, uintptr_t keep,
+                       uintptr_t hist, uintptr_t state, uintptr_t rtab, int max_rounds, uintptr_t stream) {
+    const MLPDesc d = desc_of(dims, "dnc_select");
+    const FLDnc p = dnc_args("dnc_select", K, f, q, iters, 0, 0, rtab, max_rounds);
+    if (!scratch || !keep || !hist || !state) throw std::runtime_error("dnc_select: bad arguments");
+    HIP_CHECK(fl_launch_dnc_select(d, p, as_ptr<float>(scratch), as_ptr<unsigned long long>(keep),
+                                   as_ptr<unsigned long long>(hist), as_ptr<const FLState>(state), as_stream(stream)));
+}
+
 // Secure aggregation (fl_secagg.hip) across engines' buffers, as robust_aggregate is.  `bufs` / `clamp`:
 // device tables of n buffer / uint32 [max_rounds] clamp-history addresses (int64) of clients
 // first_client .. first_client + n - 1; `state` / `rtab`: a client's round state and per-round table.
@@ -2103,6 +2155,13 @@ PYBIND11_MODULE(_fedmi_hip, m) {
           py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"), py::arg("tile") = 0);
     m.def("screen_select", &screen_select, py::arg("dist"), py::arg("K"), py::arg("f"), py::arg("m"), py::arg("keep"),
           py::arg("hist"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"));
+    m.def("dnc_gram", &dnc_gram, py::arg("dims"), py::arg("src"), py::arg("K"), py::arg("f"), py::arg("q"),
+          py::arg("iters"), py::arg("thresh"), py::arg("seed"), py::arg("scratch"), py::arg("state"), py::arg("rtab"),
+          py::arg("max_rounds"), py::arg("stream"));
+    m.def("dnc_select", &dnc_select, py::arg("dims"), py::arg("K"), py::arg("f"), py::arg("q"), py::arg("iters"),
+          py::arg("scratch"), py::arg("keep"), py::arg("hist"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"),
+          py::arg("stream"));
+    m.def("dnc_scratch_floats", &dnc_scratch_floats, py::arg("dims"), py::arg("iters"), py::arg("K"));
     m.def("compress_launch", &compress_launch, py::arg("dims"), py::arg("kind"), py::arg("k"),
           py::arg("error_feedback"), py::arg("local"), py::arg("x"), py::arg("comm"), py::arg("residual"),
           py::arg("stat"), py::arg("state"), py::arg("rtab"), py::arg("max_rounds"), py::arg("stream"),

@@ -14,6 +14,20 @@ __device__ __forceinline__ uint32_t robust_key(float x) {
     return (u & 0x7fffffffu) > 0x7f800000u ? 0xfffffffeu : (u == 0x80000000u ? 0x80000000u : k);
 }
 
+// The client screens' ranking (fl_screen.hip, fl_dnc.hip): lane i's rank among the 64 keys of `skey`
+// (LDS, one per client; a lane that is no sampled client holds 0xffffffff) by counting, ties to the
+// lower client index.  Branch-free, so the reads pipeline.
+__device__ __forceinline__ int robust_rank64(const uint32_t* skey, int i) {
+    int rank = 0;
+    const uint32_t ki = skey[i];
+#pragma unroll 8
+    for (int q = 0; q < 64; ++q) {
+        const uint32_t kq = skey[q];
+        rank += (q != i && (kq < ki || (kq == ki && q < i))) ? 1 : 0;
+    }
+    return rank;
+}
+
 // Median / trimmed mean of column e: ranks in [lo, hi) are kept, n = float(hi - lo).
 template <int KB, int VEC>
 __device__ __forceinline__ float robust_select(const float (&v)[KB][VEC], int e, uint64_t mask, int lo, int hi,

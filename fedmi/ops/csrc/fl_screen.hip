@@ -167,14 +167,7 @@ fl_screen_select_kernel(FLScreen p, const float* __restrict__ dist, unsigned lon
         skey[i] = me ? robust_key(score) : none;   // an unsampled lane ranks behind every sampled one
         __syncthreads();
         const int want = p.m > 0 && p.m < kr - p.f ? p.m : kr - p.f;
-        int rank = 0;
-        const uint32_t ki = skey[i];
-#pragma unroll 8
-        for (int q = 0; q < 64; ++q) {
-            const uint32_t kq = skey[q];
-            rank += (q != i && (kq < ki || (kq == ki && q < i))) ? 1 : 0;
-        }
-        kept = __ballot(me && rank < want);
+        kept = __ballot(me && robust_rank64(skey, i) < want);
     }
     if (i == 0) {
         *keep = kept;

@@ -3,8 +3,8 @@
 ``ClientGroup(k=8)`` on the income CSV's 8000 training rows, iid shards, clients 1 and 4 Byzantine, 50 rounds
 of the default 14-50-200-2 model in fp32 without early stopping; every cell is the global model's accuracy on
 the held-out 20 % split after the last round (and, beside it, the best round's).  Rows: the weighted mean,
-the coordinate-wise median, the 0.25-trimmed mean, the geometric median, multi-Krum (f = 2) in front of the
-mean.  Columns: no attack, sign_flip (s = 1), gauss (sigma = 1), alie with the default z (for n = 8, f = 2
+the coordinate-wise median, the 0.25-trimmed mean, the geometric median, multi-Krum (f = 2) and DnC (f = 2, one
+iteration over every coordinate) in front of the mean.  Columns: no attack, sign_flip (s = 1), gauss (sigma = 1), alie with the default z (for n = 8, f = 2
 that is Phi^-1(0.5) = 0: the bad clients publish the honest mean) and with z = 1.5, ipm with eps = 0.1 and
 eps = 100, label_flip.  A cell whose model is not finite is recorded as null.
 
@@ -35,6 +35,7 @@ DEFENCES = {
     "trimmed_mean 0.25": dict(aggregator="trimmed_mean", trim_ratio=0.25),
     "geomed": dict(aggregator="geomed"),
     "multi_krum f=2 + mean": dict(aggregator="mean", screen="multi_krum", screen_byzantine=2),
+    "dnc f=2 + mean": dict(aggregator="mean", screen="dnc", screen_byzantine=2),
 }
 ATTACK_COLUMNS = {
     "none": dict(),
